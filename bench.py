@@ -1,17 +1,25 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of a full train step (600x1000 synthetic inputs) with the
-detection hot path on the HIP library, plus the hot path's roofline and a CPU baseline.
+detection hot path on the HIP library; with --full also the hot path's roofline and a CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one optimiser step of the workload on this rank's images (weak scaling: every
 rank runs the same per-GPU batch; gradients are averaged with one RCCL all-reduce).  W
 untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; the time is
-the max over ranks; rank 0 prints ONE JSON line.
+the max over ranks; rank 0 prints ONE JSON line.  Every step starts from the same state (initial
+parameters, fresh optimiser), so that with the same arguments the last step's inputs and outputs
+are the same in every run.
 
-`roofline` is measured on a FIXED RoI set (tools/roofline_leg.py: exactly n_sup*128 + n_ws*2000 =
+A plain run does only what that line's headline needs: set-up, warm-up, the K timed steps, the
+deferred device flags of those steps, and (--dump-outputs DIR) what the last timed step returned,
+as DIR/<name>.npy.  --full adds everything else, after the timed steps: the per-op hot-path times
+of the timed steps (HIP events around each C-ABI call), the scaling diagnostics, the roofline leg
+and the CPU baseline.
+
+`roofline` (--full) is measured on a FIXED RoI set (tools/roofline_leg.py: exactly n_sup*128 + n_ws*2000 =
 8512 rows for the default workload, profiles/roofline_rois_r8512.npy) right after the timed steps,
 with HIP events on the launch stream around each C-ABI call; `cpu_baseline` pools the same RoI set.
 
@@ -38,6 +46,14 @@ if ROOT not in sys.path:
 # plumbing: the per-RoI head is fp32 GEMMs; hipBLASLt picks better kernels for these shapes than
 # the default BLAS path (measured 192 -> 176 ms per step).  Must be set before torch is imported.
 os.environ.setdefault("TORCH_BLAS_PREFER_HIPBLASLT", "1")
+# plumbing: MIOpen's naive reference convolutions (ConvDirectNaiveConv*) are never the pick for these convolutions (no
+# record of the shipped find-db has them fastest or alone), yet a fresh process builds and times them for every new
+# convolution in the first step: ~30 s of the first warm-up step, against ~1.3 s without them; same step time after.
+for _d in ("FWD", "BWD", "WRW"):
+    os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_" + _d, "0")
+# plumbing: Tensile's stream-K GEMMs (hipBLASLt, the per-RoI head) size their grid from the CUs free at launch; a fixed
+# grid splits every K the same way in every run, so a step's losses repeat to ~1e-6 instead of ~1e-4
+os.environ.setdefault("TENSILE_STREAMK_DYNAMIC_GRID", "0")
 
 
 def seed_miopen_db():
@@ -79,9 +95,15 @@ def seed_miopen_db():
     dst = tempfile.mkdtemp(prefix="wssdl_miopen_db_")           # private (0700), unpredictable name
     atexit.register(shutil.rmtree, dst, True)
     try:
+        # contents only, never the source's mode bits: MIOpen writes to both databases (and sqlite puts its journal
+        # beside the kernel cache), so a read-only checkout must still give it writable files and directories
         for sub in ("config", "cache"):
             if os.path.isdir(os.path.join(src, sub)):
-                shutil.copytree(os.path.join(src, sub), os.path.join(dst, sub))
+                os.mkdir(os.path.join(dst, sub), 0o700)
+                for f in os.listdir(os.path.join(src, sub)):
+                    if os.path.isfile(os.path.join(src, sub, f)):
+                        shutil.copyfile(os.path.join(src, sub, f), os.path.join(dst, sub, f))
+                        os.chmod(os.path.join(dst, sub, f), 0o600)
     except OSError as e:
         return None, "could not copy the find-db: %s" % e
     os.environ["MIOPEN_USER_DB_PATH"] = os.path.join(dst, "config")
@@ -368,7 +390,16 @@ def main():
                     help="wssdl_set_tuning(KEY, INT) before the run, for A/B comparisons (e.g. nms_fused=0); repeatable")
     ap.add_argument("--roi-bwd-plan", type=int, default=-1,
                     help="force a plan of the list-driven RoI-pool backward (wssdl_set_tuning roi_bwd_plan; -1 = automatic)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also report the per-op hot-path times, the scaling diagnostics, the "
+                         "roofline leg and (one GPU) the CPU baseline; without it the run reports the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.save_fixed_rois and not args.full:
+        ap.error("--save-fixed-rois writes the roofline leg's RoI set: it needs --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -446,32 +477,103 @@ def main():
             return postprocess_detections(scores, boxes, scores.shape[1], thresh=0.05, max_per_image=300)
 
     net.train()
+    # Every step, warm-up and timed, starts from the same state: the initial parameters and batch-norm buffers, a fresh
+    # optimiser, global step 0.  Chained steps would carry the run-to-run rounding of the vendor GEMMs / convolutions
+    # into the next step's inputs and, through the discrete choices of the hot path (top-k, NMS, sampling, arg-max),
+    # grow it into different outputs; from the same state every run computes the last step from identical inputs.
+    # The restore is an in-place copy (~0.1 ms against a ~137 ms step).
+    state = list(net.state_dict().values())
+    initial = [t.detach().clone() for t in state]
+
+    def restore():
+        torch._foreach_copy_(state, initial)
+        for opt in (solver.optimizer, solver.optimizer_ws):
+            if opt is not None:
+                # Adam's moments and step count back to zero in place: the same as a fresh optimiser, no re-allocation
+                for st in opt.state.values():
+                    torch._foreach_zero_([v for v in st.values() if torch.is_tensor(v)])
+        solver.global_step = 0
+
     for _ in range(args.warmup):
+        restore()
         step()
-    _lib.timeline.reset(True)
-    if getattr(solver, "overlap", None) is not None:
+    _lib.timeline.reset(args.full)         # per-op hot-path times of the timed steps (--full)
+    if args.full and getattr(solver, "overlap", None) is not None:
         solver.overlap.start_timing()      # exposed all-reduce wait per optimiser step (scaling_diag)
     ctx.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        restore()
         out = step()
     torch.cuda.synchronize()
     ctx.barrier()
     elapsed = time.perf_counter() - t0
     _lib.timeline.enabled = False
-    # what a single SCALE line needs to explain a miss: every rank's own step time, the all-reduce wait backward did
-    # not hide (per optimiser step, per rank), the buckets and their bytes, buckets launched only after backward
-    my_ms = elapsed / max(args.steps, 1) * 1e3
+    # the deferred device flags of the timed steps (RoI-pool window / list overflow, NMS time-out): the polls
+    # inside the steps run one step late and never see the last one
+    from wssdl_bus_amd.roi_pooling_layer import roi_pooling_op
+    roi_pooling_op.check_flags()
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    scaling_diag = scaling_diagnostics(ctx, solver, elapsed, args.steps) if args.full else None
+    elapsed = ctx.max_over_ranks(elapsed)
+    n_ranks_seen = ctx.count_ranks()      # a sum of ones over the job's collective backend
+    loss_val = float(out["loss"].detach()) if isinstance(out, dict) and torch.is_tensor(out.get("loss")) else None
+    result = {
+        "metric": "images/sec (train step, 600x1000)" if mode != "test" else "images/sec (test forward, 1000x1600)",
+        "value": round(images_per_step * ctx.world_size * args.steps / elapsed, 3),
+        "unit": "images/s",
+        "n_gpus": ctx.world_size, "n_ranks_seen": n_ranks_seen, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": args.workload, "baseline_config_index": wl["baseline_config"],
+                   "backbone": "%s-%d" % ("ResNet" if wl["net"].startswith("Resnet") else "VGG", wl["depth"]),
+                   "image": "%dx%d" % (im_h, im_w), "images_per_gpu": images_per_step,
+                   "supervised_per_gpu": wl["n_sup"], "weak_per_gpu": wl["n_ws"], "mode": mode,
+                   "parallelism": "image-parallel dp%d, %s grad all-reduce" % (
+                       ctx.world_size, "RCCL" if (ctx.backend or "nccl") == "nccl" else ctx.backend),
+                   "sampling_rng": args.sampling_rng, "fused_rpn_softmax": bool(cfg.FUSED_RPN_SOFTMAX), "padded_rois": bool(cfg.PADDED_ROIS),
+                   "miopen_find": (not args.no_miopen_benchmark), "miopen_find_db": miopen_db_note,
+                   "miopen_searched": miopen_db_grew(miopen_db)},
+        "final_loss": loss_val,
+    }
+    if args.full:
+        full_report(result, args, ctx, wl, net, blobs_ws if mode == "alter" else blobs, scaling_diag)
+    if ctx.rank == 0:
+        print(json.dumps(result))
+    ctx.shutdown()
+
+
+def dump_outputs(path, out):
+    """What the last timed step returned, one DIR/<name>.npy per array (float64 stays float64, everything else is
+    written as float32): the loss terms of a train step (0-d arrays), the per-class detections [n, 5] of the test
+    forward (dets_class<j>)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    items = sorted(out.items(), key=lambda kv: str(kv[0])) if isinstance(out, dict) else [("output", out)]
+    for k, v in items:
+        name = "dets_class%d" % k if isinstance(k, int) else str(k)
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
+def scaling_diagnostics(ctx, solver, elapsed, steps):
+    """What a single SCALE line needs to explain a miss: every rank's own step time, the all-reduce wait backward did
+    not hide (per optimiser step, per rank), the buckets and their bytes, buckets launched only after backward.
+    Collective: every rank calls it."""
+    my_ms = elapsed / max(steps, 1) * 1e3
     ov = getattr(solver, "overlap", None)
     ov_stats = ov.stats() if ov is not None else None
-    scaling_diag = dict(
+    return dict(
         ms_per_step_per_rank=[round(v, 3) for v in ctx.gather_floats(my_ms)],
         exposed_allreduce_ms_per_optimizer_step_per_rank=[round(v, 4) for v in ctx.gather_floats(
             ov_stats["exposed_wait_ms_per_finish"] if ov_stats else 0.0)],
         exposed_allreduce_ms_max_per_rank=[round(v, 4) for v in ctx.gather_floats(
             ov_stats["exposed_wait_ms_max"] if ov_stats else 0.0)],
-        optimizer_steps_per_step=(round(ov_stats["finishes"] / max(args.steps, 1), 2) if ov_stats else None),
+        optimizer_steps_per_step=(round(ov_stats["finishes"] / max(steps, 1), 2) if ov_stats else None),
         buckets=(ov_stats["buckets"] if ov_stats else 0), bucket_bytes=(ov_stats["bucket_bytes"] if ov_stats else []),
         bucket_bytes_cap=(ov_stats["bucket_bytes_cap"] if ov_stats else None),
         allreduce_bytes_per_optimizer_step=(ov_stats["allreduce_bytes_per_finish"] if ov_stats else 0),
@@ -480,13 +582,18 @@ def main():
         note="exposed = the compute stream's wait in GradOverlap.finish() for collectives backward did not hide "
              "(events around the waits); late buckets = launched by finish(), never overlapped; one process per GPU, "
              "image-parallel, no data-path collective")
-    elapsed = ctx.max_over_ranks(elapsed)
-    # the deferred device flags of the timed steps (RoI-pool window / list overflow, NMS time-out): the polls
-    # inside the steps run one step late and never see the last one
-    from wssdl_bus_amd.roi_pooling_layer import roi_pooling_op
-    roi_pooling_op.check_flags()
-    n_ranks_seen = ctx.count_ranks()      # a sum of ones over the job's collective backend
-    loss_val = float(out["loss"].detach()) if isinstance(out, dict) and torch.is_tensor(out.get("loss")) else None
+
+
+def full_report(result, args, ctx, wl, net, leg_blobs, scaling_diag):
+    """--full: everything beyond the headline, measured after the timed steps and added to `result` (rank 0's line):
+    the per-op hot-path times of the timed steps, the scaling diagnostics, the roofline leg on the fixed RoI set,
+    a device-to-device copy, and on one GPU the CPU baseline.  Every rank calls it (the leg keeps ranks in step)."""
+    import numpy as np
+    import torch
+    from wssdl_bus_amd import _lib
+    from wssdl_bus_amd.fast_rcnn.config import cfg
+    mode = wl["mode"]
+    images_per_step = wl["n_sup"] + wl["n_ws"]
 
     def measured_copy_gbps():
         # device-to-device copy of 1 GiB (read + write counted), the practical HBM ceiling
@@ -509,7 +616,6 @@ def main():
     feat_key = "conv5_3" if wl["net"].startswith("VGG") else "group2/relu"
     # (alternating mode: the leg measures the WEAK step's launch -- all of its images' proposals through RoI pooling,
     # the heavier of the iteration's two -- not the supervised step's 128 rows)
-    leg_blobs = blobs_ws if mode == "alter" else blobs
     rois_fixed, roi_tag = fixed_roi_set(wl, net, leg_blobs, weak_step=(mode == "alter"))
     if args.save_fixed_rois and ctx.rank == 0:
         np.save(args.save_fixed_rois, rois_fixed)
@@ -583,31 +689,14 @@ def main():
                                 GBps=round(sum(alg_bytes(k, m) for m in v["metas"]) / v["calls"]
                                            / (v["avg_ms"] * 1e-3) / 1e9, 1))
                         for k, v in tl.items()})
-        result = {
-            "metric": "images/sec (train step, 600x1000)" if mode != "test" else "images/sec (test forward, 1000x1600)",
-            "value": round(images_per_step * ctx.world_size * args.steps / elapsed, 3),
-            "unit": "images/s",
-            "n_gpus": ctx.world_size, "n_ranks_seen": n_ranks_seen, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": args.workload, "baseline_config_index": wl["baseline_config"],
-                       "backbone": "%s-%d" % ("ResNet" if wl["net"].startswith("Resnet") else "VGG", wl["depth"]),
-                       "image": "%dx%d" % (im_h, im_w), "images_per_gpu": images_per_step,
-                       "supervised_per_gpu": wl["n_sup"], "weak_per_gpu": wl["n_ws"], "mode": mode,
-                       "parallelism": "image-parallel dp%d, %s grad all-reduce" % (
-                           ctx.world_size, "RCCL" if (ctx.backend or "nccl") == "nccl" else ctx.backend),
-                       "sampling_rng": args.sampling_rng, "fused_rpn_softmax": bool(cfg.FUSED_RPN_SOFTMAX), "padded_rois": bool(cfg.PADDED_ROIS),
-                       "miopen_find": (not args.no_miopen_benchmark), "miopen_find_db": miopen_db_note,
-                       "miopen_searched": miopen_db_grew(miopen_db),
-                       "roi_pool_argmax_bytes": leg_meta["argmax_bytes"]},
-            "roofline": roofline,
-            "scaling_diag": scaling_diag,
-            "hot_path": {"gpu_ms_per_step": round(hot_ms, 3),
-                         "gpu_images_per_s": round(images_per_step / (hot_ms * 1e-3), 1) if hot_ms > 0 else None,
-                         "loss_op_ms_per_step": round(loss_ms, 4), "fused_loss": bool(cfg.get("FUSED_LOSS", True))},
-            "final_loss": loss_val,
-        }
+        final_loss = result.pop("final_loss")
+        result["config"]["roi_pool_argmax_bytes"] = leg_meta["argmax_bytes"]
+        result["roofline"] = roofline
+        result["scaling_diag"] = scaling_diag
+        result["hot_path"] = {"gpu_ms_per_step": round(hot_ms, 3),
+                              "gpu_images_per_s": round(images_per_step / (hot_ms * 1e-3), 1) if hot_ms > 0 else None,
+                              "loss_op_ms_per_step": round(loss_ms, 4), "fused_loss": bool(cfg.get("FUSED_LOSS", True))}
+        result["final_loss"] = final_loss
         if ctx.world_size == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(wl, rois_fixed)
             result["cpu_baseline"] = cb
@@ -624,8 +713,6 @@ def main():
                 result["hot_path"]["cpu_ms_over_gpu_ms_roi_counts_differ"] = {
                     "ratio": round(cb["cpu_hot_path_ms_per_step"] / hot_ms, 1),
                     "cpu_rois": cb["roi_pool_rois"], "gpu_rois_per_step": [min(gpu_rois), max(gpu_rois)] if gpu_rois else None}
-        print(json.dumps(result))
-    ctx.shutdown()
 
 
 if __name__ == "__main__":

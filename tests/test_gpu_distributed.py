@@ -288,7 +288,7 @@ def test_bench_py_under_torch_distributed_run_two_ranks():
     --nproc-per-node 2 ... bench.py --gpus 2`), two ranks sharing the one GPU over gloo
     (WSSDL_DIST_BACKEND; RCCL refuses two ranks on one device).  The launcher starts fresh children
     before anything touches the GPU; this process only waits for it.  Checks the contract of the one
-    JSON line: n_gpus, whole-job value = ranks x images / max-rank time, roofline present, no
+    JSON line: n_gpus, whole-job value = ranks x images / max-rank time, roofline present (--full), no
     cpu_baseline at N > 1."""
     import json
     import subprocess
@@ -298,7 +298,7 @@ def test_bench_py_under_torch_distributed_run_two_ranks():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--workload", "resnet18_sup_b2", "--no-cpu-baseline", "--roofline-iters", "3"]
+           "--workload", "resnet18_sup_b2", "--no-cpu-baseline", "--roofline-iters", "3", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=840)
     out = p.stdout.decode()
     assert p.returncode == 0, out[-2000:] + p.stderr.decode()[-4000:]

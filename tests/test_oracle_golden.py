@@ -1,11 +1,19 @@
 """Pin the CPU oracle (oracle/) against golden vectors produced by the reference's
-own code (tests/golden/make_golden.py) and, where oracle/_ref is present, against
-the reference's own Cython kernels directly.  CPU only."""
+own code (tests/golden/make_golden.py, make_golden_ref_cython.py) and, where oracle/_ref is
+present, against the reference's own Cython kernels directly.  CPU only."""
+import importlib.util
+import os
+
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 from oracle import c_oracle, np_oracle as O, ref_kernels
+
+# the seeded inputs of the *_vs_reference_cython* tests, shared with the script that pinned the reference's outputs
+_spec = importlib.util.spec_from_file_location("make_golden_ref_cython", os.path.join(GOLDEN, "make_golden_ref_cython.py"))
+ref_cases = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(ref_cases)
 
 STRIDE = [16, ]
 SCALES = [8, 16, 32]
@@ -47,15 +55,18 @@ def test_bbox_overlaps_golden():
     assert g["iou"][5, 5] == 1.0 and np.all(g["iou"][:, 6] == 0)
 
 
-@pytest.mark.skipif(not ref_kernels.available(), reason="oracle/_ref not built")
 def test_bbox_overlaps_vs_reference_cython():
-    rs = np.random.RandomState(0)
-    for _ in range(5):
-        xy = rs.uniform(-50, 900, size=(3000, 2))
-        b = np.hstack((xy, xy + rs.uniform(0, 500, size=(3000, 2))))
-        q = b[rs.choice(3000, 20, replace=False)] + rs.uniform(-5, 5, size=(20, 4))
-        assert np.array_equal(O.bbox_overlaps(b, q), ref_kernels.bbox_overlaps(b, q))
-        assert np.array_equal(O.bbox_overlaps_ui(b, q), ref_kernels.bbox_overlaps_ui(b, q))
+    """The reference's own Cython IoU on random boxes: live where oracle/_ref is built, and always against its outputs
+    pinned in tests/golden/ref_cython_random.npz (digests; tests/golden/make_golden_ref_cython.py)."""
+    g = load_golden("ref_cython_random")
+    for i, (b, q) in enumerate(ref_cases.bbox_cases()):
+        assert ref_cases.digest(b, q) == str(g["bbox/%d/inputs" % i]), i
+        iou, ui = O.bbox_overlaps(b, q), O.bbox_overlaps_ui(b, q)
+        assert ref_cases.digest(iou) == str(g["bbox/%d/iou" % i]), i
+        assert ref_cases.digest(ui) == str(g["bbox/%d/ui" % i]), i
+        if ref_kernels.available():
+            assert np.array_equal(iou, ref_kernels.bbox_overlaps(b, q))
+            assert np.array_equal(ui, ref_kernels.bbox_overlaps_ui(b, q))
     assert O.bbox_overlaps(np.zeros((0, 4)), q).shape == (0, 20)
     assert O.bbox_overlaps(b, np.zeros((0, 4))).shape == (3000, 0)
 
@@ -84,15 +95,16 @@ def test_nms_threshold_is_double_compare():
         assert ref_kernels.cpu_nms(d, float(np.float32(0.7))) == [0]
 
 
-@pytest.mark.skipif(not ref_kernels.available(), reason="oracle/_ref not built")
 def test_nms_vs_reference_cython_random():
-    rs = np.random.RandomState(1)
-    for n in (1, 7, 200, 1500):
-        c = rs.uniform(0, 300, size=(n, 2))
-        wh = rs.uniform(5, 120, size=(n, 2))
-        d = np.hstack((c, c + wh, rs.permutation(n)[:, None] / float(n))).astype(np.float32)
-        for th in (0.3, 0.5, 0.7):
-            assert O.nms(d, th) == [int(k) for k in ref_kernels.cpu_nms(d, th)]
+    """cpu_nms.pyx on random boxes: live where oracle/_ref is built, and always against its pinned keep lists."""
+    g = load_golden("ref_cython_random")
+    for n, d in ref_cases.cpu_nms_cases():
+        assert np.array_equal(d, g["cpu_nms/n%d_dets" % n]), n
+        for th in ref_cases.NMS_THRESH:
+            got = O.nms(d, th)
+            assert got == g[ref_cases.keep_key("cpu_nms", n, th)].tolist(), (n, th)
+            if ref_kernels.available():
+                assert got == [int(k) for k in ref_kernels.cpu_nms(d, th)]
 
 
 def test_utils_nms_and_nms_new_golden():
@@ -113,16 +125,20 @@ def test_utils_nms_and_nms_new_golden():
     assert O.nms_new(d, 0.99) == [0]
 
 
-@pytest.mark.skipif(getattr(ref_kernels, "nms_new", None) is None, reason="oracle/_ref/cython_nms.so not built")
 def test_utils_nms_vs_reference_cython_random():
-    rs = np.random.RandomState(2)
-    for n in (1, 7, 200, 1500):
-        c = rs.uniform(0, 300, size=(n, 2))
-        wh = np.exp(rs.uniform(np.log(4), np.log(200), size=(n, 2)))          # nested boxes are common
-        d = np.hstack((c, c + wh, rs.permutation(n)[:, None] / float(n))).astype(np.float32)
-        for th in (0.3, 0.5, 0.7):
-            assert O.nms(d, th) == [int(k) for k in ref_kernels.nms(d, th)]
-            assert O.nms_new(d, th) == [int(k) for k in ref_kernels.nms_new(d, th)]
+    """utils/nms.pyx (`nms`, `nms_new`) on random, often nested boxes: live where oracle/_ref/cython_nms.so is built,
+    and always against its pinned keep lists."""
+    g = load_golden("ref_cython_random")
+    live = getattr(ref_kernels, "nms_new", None) is not None
+    for n, d in ref_cases.utils_nms_cases():
+        assert np.array_equal(d, g["utils_nms/n%d_dets" % n]), n
+        for th in ref_cases.NMS_THRESH:
+            got, got_new = O.nms(d, th), O.nms_new(d, th)
+            assert got == g[ref_cases.keep_key("utils_nms", n, th)].tolist(), (n, th)
+            assert got_new == g[ref_cases.keep_key("utils_nms_new", n, th)].tolist(), (n, th)
+            if live:
+                assert got == [int(k) for k in ref_kernels.nms(d, th)]
+                assert got_new == [int(k) for k in ref_kernels.nms_new(d, th)]
 
 
 # ------------------------------------------------------------ anchor target ---
