@@ -591,6 +591,24 @@ WSSDL_API int wssdl_post_detections(const float *scores, const float *boxes, int
                      float score_thresh, double nms_thresh, int max_per_image, float *dets,
                      int32_t *counts, void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
 
+/* The same step for a batch of images in one set of launches, no host read-back (test_net over a batch).
+ *   rois   [R, 5] f32: the blob fed to RoI pooling; only its batch column is read.  The rows of one image are
+ *          contiguous and the images come in ascending order (the compact blob and the cfg.PADDED_ROIS blob of
+ *          the proposal layer both are); rows with a batch index < 0 (or >= n_images) are ignored.
+ *   scores [R, num_classes] f32, boxes [R, 4 * num_classes] f32: the blob's class scores and decoded boxes;
+ *   dets   [n_images, num_classes-1, max_rows_per_image, 5] f32, counts [n_images, num_classes-1] i32:
+ *          dets[i, j-1, :counts[i, j-1]] = image i's class-j detections, best first, after image i's own cap.
+ * Every image's output is bit for bit that of wssdl_post_detections on its rows alone.  An image with more
+ * rows than max_rows_per_image is reported as counts[i, 0] = -1 (the other counts of the image 0).
+ * num_classes <= 65, n_images * (num_classes-1) * max_rows_per_image <= 2^24 and
+ * n_images * (num_classes-1) <= 65535; R == 0 or n_images == 0: zero counts, nothing else launched.
+ * wssdl_post_detections is the case n_images = 1, rois = NULL (rows 0 .. R-1), max_rows_per_image = R. */
+WSSDL_API size_t wssdl_post_detections_batched_workspace_bytes(int n_images, int max_rows_per_image, int num_classes);
+WSSDL_API int wssdl_post_detections_batched(const float *rois, const float *scores, const float *boxes, int R,
+                     int n_images, int max_rows_per_image, int num_classes, float score_thresh, double nms_thresh,
+                     int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
+                     wssdl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

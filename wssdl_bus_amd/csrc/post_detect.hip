@@ -1,4 +1,4 @@
-// f3: the post-detection step of the test path as ONE call, batched over the classes.
+// f3: the post-detection step of the test path as ONE call, batched over the classes and the images.
 //
 // Reference: code/lib/fast_rcnn/test_bus.py:360-401.  For every class j >= 1:
 //   inds = where(scores[:, j] > thresh); cls_dets = hstack(boxes[inds, 4j:4j+4], scores[inds, j]) (f32);
@@ -7,11 +7,18 @@
 // Then the cap (:389-396): if more than max_per_image detections are left over all classes,
 //   image_thresh = sort(all scores)[-max_per_image]  and every class keeps its rows with score >= image_thresh.
 //
-// Here the classes play the role the images play in the proposal layer: one set of launches ranks,
-// gathers and runs mask + sweep for all of them (nms.hip), the score filter is a zero key (no host
-// read-back of `inds`), and the cap is a radix select over the kept scores (select.hip.h).  A class's
-// kept rows are in descending score order, so "score >= image_thresh" keeps a PREFIX of them: the op
-// writes dets[c] = the kept rows in that order and counts[c] = the length of the prefix.
+// Here the (image, class) pairs play the role the images play in the proposal layer: one "segment" per pair, of
+// pitch P = max_rows_per_image, and one set of launches ranks, gathers and runs mask + sweep for all of them
+// (nms.hip); the score filter is a zero key (no host read-back of `inds`), and the cap is a radix select over the
+// kept scores of one image (select.hip.h), one workgroup per image.  A class's kept rows are in descending score
+// order, so "score >= image_thresh" keeps a PREFIX of them: the op writes dets[i, c] = the kept rows in that order
+// and counts[i, c] = the length of the prefix.
+//
+// The rows of image i are the contiguous run of the RoI blob whose batch index is i; a small kernel finds each run
+// on the device (post_segments_kernel).  Inside a segment a row is named by its index LOCAL to its image (row -
+// start): the keys' tie-break and the kept list are then those of the single-image call on that image's rows, so
+// every image's output is bit for bit the one wssdl_post_detections gives on its rows alone.
+// wssdl_post_detections itself is the one-image case (no RoI blob: rows 0 .. R-1, P = R).
 #include "nms.hip.h"
 #include "select.hip.h"
 
@@ -21,142 +28,252 @@ struct PostWs {
     unsigned long long *keys, *cand, *thresh, *mask, *summ;
     float *boxes, *sorted_boxes;
     int *sorted_index, *n_sorted, *cand_fill, *kept, *keep, *num_keep;
+    int *img_lo, *img_hi;       // per image: first and last row of its run in the RoI blob (batched calls)
 };
 
-static size_t carve_post(void *ws, int R, int nc, PostWs *out) {
+// nseg = n_images * (num_classes - 1) segments of P rows each
+static size_t carve_post(void *ws, int n_images, int P, int nc, PostWs *out) {
     Carver c(ws);
     PostWs w;
-    const int ncb = nms_mask_pitch(R);
-    w.keys = c.take<unsigned long long>((size_t)nc * R);
-    w.cand = c.take<unsigned long long>((size_t)nc * R);
-    w.thresh = c.take<unsigned long long>((size_t)nc + 32);
-    w.sorted_index = c.take<int>((size_t)nc * R);
-    w.n_sorted = c.take<int>((size_t)nc + 64);
-    w.cand_fill = c.take<int>((size_t)nc + 64);
-    w.kept = c.take<int>((size_t)nc * ((size_t)R + 64));
-    w.keep = c.take<int>((size_t)nc * R);
-    w.num_keep = c.take<int>((size_t)nc + 64);
-    w.boxes = c.take<float>((size_t)nc * R * 4);
-    w.sorted_boxes = c.take<float>((size_t)nc * R * 4);
-    w.mask = c.take<unsigned long long>((size_t)nc * R * ncb);
-    w.summ = c.take<unsigned long long>(nms_summary_alloc_words(nc, R));
+    const int ncb = nms_mask_pitch(P);
+    const size_t nseg = (size_t)n_images * nc;
+    w.keys = c.take<unsigned long long>(nseg * P);
+    w.cand = c.take<unsigned long long>(nseg * P);
+    w.thresh = c.take<unsigned long long>(nseg + 32);
+    w.sorted_index = c.take<int>(nseg * P);
+    w.n_sorted = c.take<int>(nseg + 64);
+    w.cand_fill = c.take<int>(nseg + 64);
+    w.kept = c.take<int>(nseg * ((size_t)P + 64));
+    w.keep = c.take<int>(nseg * P);
+    w.num_keep = c.take<int>(nseg + 64);
+    w.boxes = c.take<float>(nseg * P * 4);
+    w.sorted_boxes = c.take<float>(nseg * P * 4);
+    w.mask = c.take<unsigned long long>(nseg * P * ncb);
+    w.summ = c.take<unsigned long long>(nms_summary_alloc_words((int)nseg, P));
+    w.img_lo = c.take<int>((size_t)n_images + 64);
+    w.img_hi = c.take<int>((size_t)n_images + 64);
     if (out) *out = w;
     return c.off;
 }
 
-// keys of class c = j - 1: score_key(score, row) for rows above the score threshold, 0 otherwise;
-// the class's box columns side by side; the initialisations the ranking expects
-__global__ __launch_bounds__(256) void post_keys_kernel(const float *__restrict__ scores, const float *__restrict__ boxes,
-                                                        int R, int K, float score_thresh,
-                                                        unsigned long long *__restrict__ keys, float *__restrict__ cboxes,
-                                                        int *__restrict__ sorted_index, int *__restrict__ n_sorted,
-                                                        int *__restrict__ cand_fill) {
+// image of RoI row r: its batch index if in [0, n_images), -1 otherwise (dead padding rows, NaN, foreign images)
+__device__ __forceinline__ int roi_image(const float *__restrict__ rois, int r, int n_images) {
+    const float b = rois[(size_t)r * 5];
+    return (b >= 0.0f && b < (float)n_images) ? (int)b : -1;
+}
+
+// (start, count) of image img's rows: its run [lo, hi] in the blob, or rows 0 .. R-1 without a blob (lo == NULL)
+__device__ __forceinline__ void image_rows(const int *__restrict__ lo, const int *__restrict__ hi, int img, int R,
+                                           int &start, int &count) {
+    if (!lo) {
+        start = 0;
+        count = R;
+        return;
+    }
+    const int l = lo[img], h = hi[img];
+    start = h >= 0 ? l : 0;
+    count = h >= 0 ? h - l + 1 : 0;
+}
+
+// One workgroup: the first and last row of every image's run (the ends of a run are the rows whose neighbour
+// belongs to another image or to none).  Images without rows keep lo = INT_MAX, hi = -1.
+constexpr int SEG_BLOCK = 1024;
+
+__global__ __launch_bounds__(SEG_BLOCK) void post_segments_kernel(const float *__restrict__ rois, int R, int n_images,
+                                                                   int *__restrict__ lo, int *__restrict__ hi) {
+    const int t = threadIdx.x;
+    for (int i = t; i < n_images; i += SEG_BLOCK) {
+        lo[i] = 0x7fffffff;
+        hi[i] = -1;
+    }
+    __syncthreads();
+    for (int r = t; r < R; r += SEG_BLOCK) {
+        const int b = roi_image(rois, r, n_images);
+        if (b < 0) continue;
+        if (r == 0 || roi_image(rois, r - 1, n_images) != b) atomicMin(&lo[b], r);
+        if (r == R - 1 || roi_image(rois, r + 1, n_images) != b) atomicMax(&hi[b], r);
+    }
+}
+
+// keys of segment (img, c = j - 1): score_key(score, local row) for the image's rows above the score threshold,
+// 0 otherwise; the class's box columns side by side; the initialisations the ranking expects
+__global__ __launch_bounds__(256) void post_keys_kernel(const float *__restrict__ rois, const int *__restrict__ lo,
+                                                        const int *__restrict__ hi, const float *__restrict__ scores,
+                                                        const float *__restrict__ boxes, int R, int K, int n_images, int P,
+                                                        float score_thresh, unsigned long long *__restrict__ keys,
+                                                        float *__restrict__ cboxes, int *__restrict__ sorted_index,
+                                                        int *__restrict__ n_sorted, int *__restrict__ cand_fill) {
     const int nc = K - 1;
+    const long long nseg = (long long)n_images * nc;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nc) { n_sorted[i] = 0;  cand_fill[i] = 0; }
-    if (i >= (long long)nc * R) return;
-    const int c = (int)(i / R), r = (int)(i - (long long)c * R);
-    const float s = scores[(size_t)r * K + c + 1];
-    keys[i] = (s > score_thresh) ? score_key(s, (unsigned)r) : 0ull;        // NaN fails the test like np.where
+    if (i < nseg) { n_sorted[i] = 0;  cand_fill[i] = 0; }
+    if (i >= nseg * P) return;
+    const int seg = (int)(i / P), p = (int)(i - (long long)seg * P);
+    const int img = seg / nc, c = seg - img * nc;
+    int start, count;
+    image_rows(lo, hi, img, R, start, count);
     sorted_index[i] = -1;
+    const int r = start + p;
+    if (p >= count || (rois && roi_image(rois, r, n_images) != img)) {
+        keys[i] = 0ull;
+        return;
+    }
+    const float s = scores[(size_t)r * K + c + 1];
+    keys[i] = (s > score_thresh) ? score_key(s, (unsigned)p) : 0ull;        // NaN fails the test like np.where
     const float *b = boxes + (size_t)r * 4 * K + 4 * (c + 1);
     float *o = cboxes + (size_t)i * 4;
     o[0] = b[0];  o[1] = b[1];  o[2] = b[2];  o[3] = b[3];
 }
 
 __global__ __launch_bounds__(256) void post_gather_kernel(const float *__restrict__ cboxes, const int *__restrict__ sorted_index,
-                                                          const int *__restrict__ n_sorted, int R, int nc,
+                                                          const int *__restrict__ n_sorted, int P, int nseg,
                                                           float *__restrict__ sorted_boxes) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)nc * R) return;
-    const int c = (int)(i / R), p = (int)(i - (long long)c * R);
-    if (p >= n_sorted[c]) return;
-    const float *b = cboxes + ((size_t)c * R + sorted_index[i]) * 4;
+    if (i >= (long long)nseg * P) return;
+    const int seg = (int)(i / P), p = (int)(i - (long long)seg * P);
+    if (p >= n_sorted[seg]) return;
+    const float *b = cboxes + ((size_t)seg * P + sorted_index[i]) * 4;
     float *o = sorted_boxes + (size_t)i * 4;
     o[0] = b[0];  o[1] = b[1];  o[2] = b[2];  o[3] = b[3];
 }
 
-// One workgroup: the max_per_image-th largest kept score over all classes (test_bus.py:389-392), then the rows.
+// One workgroup per image: the max_per_image-th largest kept score over the image's classes
+// (test_bus.py:389-392), then its rows.  An image with more rows than P reports counts[i, 0] = -1.
 constexpr int CAP_BLOCK = 1024;
 constexpr int CAP_LIST = 512;
 
-__global__ __launch_bounds__(CAP_BLOCK) void post_cap_kernel(const float *__restrict__ scores, const float *__restrict__ cboxes,
+__global__ __launch_bounds__(CAP_BLOCK) void post_cap_kernel(const int *__restrict__ lo, const int *__restrict__ hi,
+                                                             const float *__restrict__ scores, const float *__restrict__ cboxes,
                                                              const int *__restrict__ keep, const int *__restrict__ num_keep,
-                                                             int R, int K, int max_per_image, float *__restrict__ dets,
+                                                             int R, int K, int P, int max_per_image, float *__restrict__ dets,
                                                              int *__restrict__ counts) {
     __shared__ SelectScratch<CAP_LIST> sc;
     __shared__ int s_count[64];
-    const int nc = K - 1, t = threadIdx.x;
+    const int nc = K - 1, t = threadIdx.x, img = blockIdx.x;
+    int start, count;
+    image_rows(lo, hi, img, R, start, count);
+    const size_t seg0 = (size_t)img * nc;
+    if (count > P) {            // the same for the whole workgroup: no barrier is skipped by part of it
+        if (t < nc) counts[seg0 + t] = t == 0 ? -1 : 0;
+        return;
+    }
+    const int *nk = num_keep + seg0;
+    const int *kp = keep + seg0 * P;
+    const float *cb = cboxes + seg0 * P * 4;
+    const float *sc_rows = scores + (size_t)start * K;
+    float *d = dets + seg0 * P * 5;
     if (t < 64) s_count[t] = 0;
     // item i = (class c, kept position p); its key: score bits over a unique low word
     auto key_at = [&](int i, unsigned long long &v) -> bool {
-        const int c = i / R, p = i - c * R;
-        if (p >= num_keep[c]) return false;
-        const int row = keep[(size_t)c * R + p];
-        v = score_key(scores[(size_t)row * K + c + 1], (unsigned)i);
+        const int c = i / P, p = i - c * P;
+        if (p >= nk[c]) return false;
+        const int row = kp[(size_t)c * P + p];
+        v = score_key(sc_rows[(size_t)row * K + c + 1], (unsigned)i);
         return true;
     };
     int members = 0;
     const unsigned long long kth = block_radix_select<CAP_BLOCK, CAP_LIST, true>(
-        key_at, nc * R, [max_per_image](int m) { return (max_per_image > 0 && m > max_per_image) ? max_per_image : 0; }, sc,
+        key_at, nc * P, [max_per_image](int m) { return (max_per_image > 0 && m > max_per_image) ? max_per_image : 0; }, sc,
         &members);
     // image_thresh as order-preserving score bits (0: no cap -- every kept row passes)
     const unsigned cut = (unsigned)(kth >> 32);
     __syncthreads();
-    for (int i = t; i < nc * R; i += CAP_BLOCK) {
-        const int c = i / R, p = i - c * R;
-        if (p >= num_keep[c]) continue;
-        const int row = keep[(size_t)c * R + p];
-        const float s = scores[(size_t)row * K + c + 1];
-        const float *b = cboxes + ((size_t)c * R + row) * 4;
-        float *o = dets + (size_t)i * 5;
+    for (int i = t; i < nc * P; i += CAP_BLOCK) {
+        const int c = i / P, p = i - c * P;
+        if (p >= nk[c]) continue;
+        const int row = kp[(size_t)c * P + p];
+        const float s = sc_rows[(size_t)row * K + c + 1];
+        const float *b = cb + ((size_t)c * P + row) * 4;
+        float *o = d + (size_t)i * 5;
         o[0] = b[0];  o[1] = b[1];  o[2] = b[2];  o[3] = b[3];  o[4] = s;
         if ((unsigned)(score_key(s, 0u) >> 32) >= cut && c < 64) atomicAdd(&s_count[c], 1);     // a prefix: rows are in descending order
     }
     __syncthreads();
-    if (t < nc && t < 64) counts[t] = s_count[t];
+    if (t < nc && t < 64) counts[seg0 + t] = s_count[t];
+}
+
+// Limits of the batched form: the segments' rows are 32-bit item numbers of one select (<= 2^24), and the ranking
+// and mask grids put the segments on a grid dimension of at most 65535 blocks.
+constexpr long long POST_MAX_ITEMS = 1LL << 24;
+constexpr long long POST_MAX_SEGMENTS = 65535;
+
+static int post_detections_run(const float *rois, const float *scores, const float *boxes, int R, int n_images, int P,
+                               int num_classes, float score_thresh, double nms_thresh, int max_per_image, float *dets,
+                               int32_t *counts, void *workspace, hipStream_t st) {
+    const int nc = num_classes - 1;
+    const int nseg = n_images * nc;
+    PostWs w;
+    carve_post(workspace, n_images, P, nc, &w);
+    const int *lo = nullptr, *hi = nullptr;
+    if (rois) {
+        hipLaunchKernelGGL(post_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, w.img_lo, w.img_hi);
+        int rc = check_launch();
+        if (rc) return rc;
+        lo = w.img_lo;
+        hi = w.img_hi;
+    }
+    const int blocks = cdiv((long long)nseg * P, 256);
+    hipLaunchKernelGGL(post_keys_kernel, dim3(blocks), dim3(256), 0, st, rois, lo, hi, scores, boxes, R, num_classes, n_images,
+                       P, score_thresh, w.keys, w.boxes, w.sorted_index, w.n_sorted, w.cand_fill);
+    int rc = check_launch();
+    if (rc) return rc;
+    if ((rc = launch_rank_topk(w.keys, P, nseg, P, w.cand, w.thresh, w.cand_fill, w.sorted_index, w.n_sorted, w.mask,
+                               sizeof(unsigned long long) * (size_t)nseg * P * nms_mask_pitch(P), st)))
+        return rc;
+    hipLaunchKernelGGL(post_gather_kernel, dim3(blocks), dim3(256), 0, st, w.boxes, w.sorted_index, w.n_sorted, P, nseg,
+                       w.sorted_boxes);
+    if ((rc = check_launch())) return rc;
+    // w.cand is free once the ranking is done: it receives the transposed diagonal blocks of the mask
+    if ((rc = launch_nms_two_pass(w.sorted_boxes, P * 4, w.n_sorted, P, nseg, nms_thresh, w.mask, w.cand, w.summ, P,
+                                  w.sorted_index, P, w.keep, w.num_keep, nullptr, w.kept, nullptr, st)))
+        return rc;
+    hipLaunchKernelGGL(post_cap_kernel, dim3(n_images), dim3(CAP_BLOCK), 0, st, lo, hi, scores, w.boxes, w.keep, w.num_keep,
+                       R, num_classes, P, max_per_image, dets, counts);
+    return check_launch();
 }
 
 }  // namespace wssdl
 
 using namespace wssdl;
 
+extern "C" size_t wssdl_post_detections_batched_workspace_bytes(int n_images, int max_rows_per_image, int num_classes) {
+    if (n_images < 1 || max_rows_per_image < 1 || num_classes < 2) return 256;
+    return carve_post(nullptr, n_images, max_rows_per_image, num_classes - 1, nullptr);
+}
+
 extern "C" size_t wssdl_post_detections_workspace_bytes(int R, int num_classes) {
-    if (R < 1 || num_classes < 2) return 256;
-    return carve_post(nullptr, R, num_classes - 1, nullptr);
+    return wssdl_post_detections_batched_workspace_bytes(1, R, num_classes);
+}
+
+extern "C" int wssdl_post_detections_batched(const float *rois, const float *scores, const float *boxes, int R,
+                                             int n_images, int max_rows_per_image, int num_classes, float score_thresh,
+                                             double nms_thresh, int max_per_image, float *dets, int32_t *counts,
+                                             void *workspace, size_t workspace_bytes, wssdl_stream_t stream) {
+    const int nc = num_classes - 1;
+    const int P = max_rows_per_image;
+    if (R < 0 || n_images < 0 || num_classes < 2 || nc > 64) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (R > 0 && (P < 1 || (long long)n_images * nc * P > POST_MAX_ITEMS || (long long)n_images * nc > POST_MAX_SEGMENTS))
+        return WSSDL_ERR_INVALID_ARGUMENT;
+    if (n_images == 0) return WSSDL_OK;
+    if (!counts) return WSSDL_ERR_INVALID_ARGUMENT;
+    hipStream_t st = as_stream(stream);
+    if (R == 0) {
+        if (hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)n_images * nc, st) != hipSuccess) return WSSDL_ERR_LAUNCH;
+        return WSSDL_OK;
+    }
+    if (!scores || !boxes || !dets || !workspace || (!rois && n_images != 1)) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < wssdl_post_detections_batched_workspace_bytes(n_images, P, num_classes)) return WSSDL_ERR_WORKSPACE;
+    return post_detections_run(rois, scores, boxes, R, n_images, P, num_classes, score_thresh, nms_thresh, max_per_image,
+                               dets, counts, workspace, st);
 }
 
 extern "C" int wssdl_post_detections(const float *scores, const float *boxes, int R, int num_classes,
                                      float score_thresh, double nms_thresh, int max_per_image, float *dets,
                                      int32_t *counts, void *workspace, size_t workspace_bytes,
                                      wssdl_stream_t stream) {
-    const int nc = num_classes - 1;
-    if (R < 0 || num_classes < 2 || nc > 64 || !counts) return WSSDL_ERR_INVALID_ARGUMENT;
-    hipStream_t st = as_stream(stream);
-    if (R == 0) {
-        if (hipMemsetAsync(counts, 0, sizeof(int32_t) * nc, st) != hipSuccess) return WSSDL_ERR_LAUNCH;
-        return WSSDL_OK;
-    }
-    if (!scores || !boxes || !dets || !workspace || (long long)nc * R > (1LL << 24)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (workspace_bytes < wssdl_post_detections_workspace_bytes(R, num_classes)) return WSSDL_ERR_WORKSPACE;
-    PostWs w;
-    carve_post(workspace, R, nc, &w);
-    const int blocks = cdiv((long long)nc * R, 256);
-    hipLaunchKernelGGL(post_keys_kernel, dim3(blocks), dim3(256), 0, st, scores, boxes, R, num_classes, score_thresh, w.keys,
-                       w.boxes, w.sorted_index, w.n_sorted, w.cand_fill);
-    int rc = check_launch();
-    if (rc) return rc;
-    if ((rc = launch_rank_topk(w.keys, R, nc, R, w.cand, w.thresh, w.cand_fill, w.sorted_index, w.n_sorted, w.mask,
-                               sizeof(unsigned long long) * (size_t)nc * R * nms_mask_pitch(R), st)))
-        return rc;
-    hipLaunchKernelGGL(post_gather_kernel, dim3(blocks), dim3(256), 0, st, w.boxes, w.sorted_index, w.n_sorted, R, nc,
-                       w.sorted_boxes);
-    if ((rc = check_launch())) return rc;
-    // w.cand is free once the ranking is done: it receives the transposed diagonal blocks of the mask
-    if ((rc = launch_nms_two_pass(w.sorted_boxes, R * 4, w.n_sorted, R, nc, nms_thresh, w.mask, w.cand, w.summ, R,
-                                  w.sorted_index, R, w.keep, w.num_keep, nullptr, w.kept, nullptr, st)))
-        return rc;
-    hipLaunchKernelGGL(post_cap_kernel, dim3(1), dim3(CAP_BLOCK), 0, st, scores, w.boxes, w.keep, w.num_keep, R, num_classes,
-                       max_per_image, dets, counts);
-    return check_launch();
+    if (R < 0 || num_classes < 2 || num_classes - 1 > 64 || !counts) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (R == 0) return wssdl_post_detections_batched(nullptr, scores, boxes, 0, 1, 1, num_classes, score_thresh, nms_thresh,
+                                                     max_per_image, dets, counts, workspace, workspace_bytes, stream);
+    return wssdl_post_detections_batched(nullptr, scores, boxes, R, 1, R, num_classes, score_thresh, nms_thresh,
+                                         max_per_image, dets, counts, workspace, workspace_bytes, stream);
 }

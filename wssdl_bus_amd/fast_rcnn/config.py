@@ -69,6 +69,8 @@ __C.TRAIN.RPN_BBOX_INSIDE_WEIGHTS = (1.0, 1.0, 1.0, 1.0)   # :214
 __C.TRAIN.RPN_POSITIVE_WEIGHT = -1.0                # :218
 
 __C.TEST = AttrDict()
+__C.TEST.SCALES = (600,)                            # :231
+__C.TEST.MAX_SIZE = 1000                            # :234
 __C.TEST.NMS = 0.3                                  # :238
 __C.TEST.CLS_AGNOSTIC_NMS = False                   # :241
 __C.TEST.BBOX_REG = True                            # :248

@@ -1,0 +1,170 @@
+"""Batched test-time detection: the detection half of test_net (reference code/lib/fast_rcnn/test_bus.py:300-401)
+at N images per forward.
+
+The reference detects one image per forward (test_bus.py:208); so does ``test_bus.im_detect``.  Here
+get_test_blobs builds the blob of N images, im_detect_batch decodes every RoI with its own image's scale and
+bounds, postprocess_detections_batch runs the per-class NMS and max_per_image cap of all images as ONE device op
+(wssdl_post_detections_batched) with one read-back, and detect_images strings them together.  Every image's
+detections are bit for bit those of the single-image arithmetic (test_bus.im_detect's decode / clip,
+test_bus.postprocess_detections) on that image's rows of the same network outputs."""
+import numpy as np
+import torch
+
+from .bbox_transform import bbox_transform_inv
+from .config import cfg
+from .test_bus import postprocess_detections
+
+
+def get_test_blobs(planes, net_name):
+    """test_bus.py:28-64 (_get_image_blob) for a list of grey planes of any sizes, one scale
+    (cfg.TEST.SCALES[0], cfg.TEST.MAX_SIZE): returns (data [N, Hmax, Wmax, 3] f32, zero-padded like
+    im_list_to_blob, and im_info [N, 3] f32 = (h_i, w_i, scale_i) of each resized image), both on the GPU.
+    For one image (h, w) are the blob's own dimensions, as in the reference (test_bus.py:176-179)."""
+    from ..utils.blob import PIXEL_MEANS, PIXEL_STDS, im_list_to_blob, prep_im_for_blob
+    if len(planes) == 0:
+        raise ValueError("get_test_blobs needs at least one image")
+    ims, info = [], []
+    for g in planes:
+        im, s = prep_im_for_blob(g, net_name, PIXEL_MEANS, PIXEL_STDS, cfg.TEST.SCALES[0], cfg.TEST.MAX_SIZE,
+                                 is_training=False)
+        ims.append(im)
+        info.append((int(im.shape[0]), int(im.shape[1]), s))
+    data = im_list_to_blob(ims)
+    return data, torch.tensor(info, dtype=torch.float32, device=data.device)
+
+
+@torch.no_grad()
+def im_detect_batch(net, data, im_info):
+    """im_detect for N images in one forward: data [N,H,W,3] NHWC, im_info [N,>=3] (h, w, scale, ...) per
+    image.  Returns (scores [R,K], pred_boxes [R,4K], rois [R,5]) for the RoI blob the network fed to RoI
+    pooling; row r belongs to image rois[r, 0] and is decoded with that image's scale and clipped to that
+    image's bounds.  Under cfg.PADDED_ROIS the blob has dead rows (batch index -1) whose values are
+    meaningless, and nothing here reads the device back.
+
+    Image i's rows are bit for bit what im_detect's arithmetic gives on them: its Python-scalar operations
+    are restated with per-row tensors that hold the same f32 values --
+      rois / scale        (GPU: PyTorch multiplies by the f32 reciprocal of a Python scalar divisor)
+                          -> rois * fl32(1 / fl32(scale)) on the GPU, rois / fl32(scale) on the CPU;
+      clamp(max=w/scale - 1)  (the bound computed in double, rounded to f32 by clamp)
+                          -> minimum with the f32-rounded double bound."""
+    was_training = net.training
+    net.eval()
+    try:
+        layers = net(data, im_info, None, None, is_training=False, is_ws=False, test_net=True)
+    finally:
+        net.train(was_training)
+    rois = layers['rpn_rois']
+    scores = layers['cls_prob']
+    n = int(data.shape[0])
+    from .. import _lib
+    info = _lib.to_device(im_info, torch.float64, rois.device)       # exact for an f32 or f64 im_info
+    if info.dim() != 2 or info.shape[0] != n or info.shape[1] < 3:
+        raise ValueError("im_info must be [N, >=3] for N = data.shape[0]")
+    img = rois[:, 0].to(torch.int64).clamp_(0, n - 1)                 # dead rows (-1): any image, ignored later
+    scale = info[:, 2].to(torch.float32)
+    if rois.is_cuda:
+        boxes = rois[:, 1:5] * torch.reciprocal(scale)[img].unsqueeze(1)
+    else:
+        boxes = rois[:, 1:5] / scale[img].unsqueeze(1)
+    if cfg.TEST.BBOX_REG:
+        pred = bbox_transform_inv(boxes, layers['bbox_pred'])
+        # test_bus._clip_boxes with (h / scale, w / scale) per row
+        xmax = (info[:, 1] / info[:, 2] - 1.0).to(torch.float32)[img].unsqueeze(1)
+        ymax = (info[:, 0] / info[:, 2] - 1.0).to(torch.float32)[img].unsqueeze(1)
+        pred[:, 0::4] = pred[:, 0::4].clamp_min(0)
+        pred[:, 1::4] = pred[:, 1::4].clamp_min(0)
+        pred[:, 2::4] = torch.minimum(pred[:, 2::4], xmax)
+        pred[:, 3::4] = torch.minimum(pred[:, 3::4], ymax)
+    else:
+        pred = boxes.repeat(1, scores.shape[1])
+    return scores, pred, rois
+
+
+def _device_post_detections_apply(scores, num_classes):
+    return scores.is_cuda and not cfg.TEST.CLS_AGNOSTIC_NMS and scores.shape[1] == num_classes and \
+        2 <= num_classes <= 65 and cfg.TEST.get("FUSED_POST_DETECTIONS", True)
+
+
+@torch.no_grad()
+def post_detections_batched_device(scores, boxes, rois, n_images, num_classes, thresh=0.05, max_per_image=300,
+                                   max_rows_per_image=None):
+    """The post-detection step of N images as one C-ABI call (wssdl_post_detections_batched: one set of
+    launches, no read-back).  rois [R,5] is the blob behind scores [R,K] / boxes [R,4K]; only its batch
+    column is read.  Returns (dets [N, K-1, P, 5] f32, counts [N, K-1] i32) on the GPU with
+    P = max_rows_per_image (default cfg.TEST.RPN_POST_NMS_TOP_N, or the largest image when that is <= 0);
+    dets[i, j-1, :counts[i, j-1]] are image i's class-j detections, best first; counts[i, 0] == -1 flags an
+    image with more than P rows."""
+    from .. import _lib
+    s = scores.to(torch.float32).contiguous()
+    b = boxes.to(torch.float32).contiguous()
+    r = rois.to(torch.float32).contiguous()
+    R, K = s.shape
+    N = int(n_images)
+    if K != num_classes or b.shape != (R, 4 * K) or r.shape != (R, 5):
+        raise ValueError("expected scores [R,K], boxes [R,4K], rois [R,5] with K = num_classes")
+    P = int(max_rows_per_image if max_rows_per_image is not None else cfg.TEST.RPN_POST_NMS_TOP_N)
+    if P <= 0:
+        live = r[:, 0][(r[:, 0] >= 0) & (r[:, 0] < N)].to(torch.int64)
+        P = int(torch.bincount(live, minlength=1).max()) if live.numel() else 1
+    L = _lib.lib()
+    dets = torch.empty((N, K - 1, max(P, 1), 5), dtype=torch.float32, device=s.device)
+    counts = torch.empty((N, K - 1), dtype=torch.int32, device=s.device)
+    with torch.cuda.device(s.device):
+        n = L.wssdl_post_detections_batched_workspace_bytes(N, P, K)
+        ws = torch.empty((n,), dtype=torch.uint8, device=s.device)
+        _lib.check(L.wssdl_post_detections_batched(_lib.ptr(r), _lib.ptr(s), _lib.ptr(b), R, N, P, K, float(thresh),
+                                                   float(cfg.TEST.NMS), int(max_per_image), _lib.ptr(dets),
+                                                   _lib.ptr(counts), _lib.ptr(ws), n, _lib.stream()),
+                   "wssdl_post_detections_batched")
+    return dets, counts
+
+
+@torch.no_grad()
+def postprocess_detections_batch(scores, boxes, rois, n_images, num_classes, thresh=0.05, max_per_image=300):
+    """postprocess_detections for every image of a batch: rows r of scores [R,K] / boxes [R,4K] belong to
+    image rois[r, 0] (rows with a negative index are dead and ignored).  Returns a list of n_images dicts
+    {j: dets [n,5]}, each equal to postprocess_detections on that image's rows.  On the GPU: one device op
+    (post_detections_batched_device) and ONE read-back of the counts [N, K-1] for the whole batch; the
+    class-agnostic variant, CPU tensors, more than 64 classes and FUSED_POST_DETECTIONS off loop over the
+    images with postprocess_detections."""
+    n_images = int(n_images)
+    if _device_post_detections_apply(scores, num_classes):
+        dets, counts = post_detections_batched_device(scores, boxes, rois, n_images, num_classes, thresh, max_per_image)
+        n = counts.cpu().tolist()
+        over = [i for i in range(n_images) if n[i][0] < 0]
+        if over:
+            raise ValueError("image(s) %s have more RoI rows than max_rows_per_image = %d (cfg.TEST.RPN_POST_NMS_TOP_N)"
+                             % (over, dets.shape[2]))
+        return [{j: dets[i, j - 1, :n[i][j - 1]] for j in range(1, num_classes)} for i in range(n_images)]
+    img = rois[:, 0]
+    out = []
+    for i in range(n_images):
+        rows = torch.nonzero(img == i).reshape(-1)
+        out.append(postprocess_detections(scores[rows], boxes[rows], num_classes, thresh, max_per_image))
+    return out
+
+
+def detect_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_image=300):
+    """The detection half of test_net (test_bus.py:300-401) at `batch_size` images per forward: returns
+    all_boxes[j][i] = numpy [n,5] (x1, y1, x2, y2, score) of image i, class j >= 1, in original-image
+    coordinates -- the structure the reference pickles (all_boxes[0] stays a list of empty lists)."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    all_boxes = None
+    for b0 in range(0, len(planes), batch_size):
+        data, info = get_test_blobs(planes[b0:b0 + batch_size], net_name)
+        scores, boxes, rois = im_detect_batch(net, data, info)
+        K = int(scores.shape[1])
+        if all_boxes is None:
+            all_boxes = [[[] for _ in range(len(planes))] for _ in range(K)]
+        dets = postprocess_detections_batch(scores, boxes, rois, data.shape[0], K, thresh, max_per_image)
+        # one read-back per batch
+        parts = [d[j] for d in dets for j in range(1, K)]
+        host = torch.cat(parts, 0).cpu().numpy() if parts else np.zeros((0, 5), np.float32)
+        off = 0
+        for i, d in enumerate(dets):
+            for j in range(1, K):
+                m = int(d[j].shape[0])
+                all_boxes[j][b0 + i] = host[off:off + m]
+                off += m
+    return all_boxes if all_boxes is not None else []
