@@ -218,7 +218,8 @@ WSSDL_API int wssdl_anchor_targets(const int8_t *labels, const int32_t *argmax_g
  *   rows with max_overlap >= fg_thresh and min(rois_per_image - n_fg, #bg) rows with
  *   bg_thresh_lo <= max_overlap < bg_thresh_hi, uniformly without replacement
  *   (counter-based hash of (seed, image, row); same distribution as npr.choice,
- *   not the same stream).  keep / is_fg [n_sample_images, rois_per_image]: rows of
+ *   not the same stream).  The two pools are independent: when fg_thresh < bg_thresh_hi
+ *   a row can be drawn once as fg and once as bg, as in the reference.  keep / is_fg [n_sample_images, rois_per_image]: rows of
  *   cand in candidate order, fg first, padded with -1; counts [n_sample_images, 2]
  *   = (n_fg, n_bg).  Rows of other images (batch index != images[s]) are ignored.
  * Stage 3  wssdl_roi_targets: for the kept rows: labels (bg clamped to 0, :265),

@@ -35,6 +35,29 @@ def groups(npz):
     return sorted({k.split("/")[0] for k in npz.files if "/" in k})
 
 
+@pytest.fixture
+def product_cfg():
+    """Set keys of the product's cfg (cfg.TRAIN, or the top-level SAMPLING_RNG / DEVICE_RNG_SEED) for one test:
+    ``product_cfg(FG_THRESH=0.4, ...)``.  Every key of cfg and cfg.TRAIN is restored afterwards, pass or fail."""
+    from wssdl_bus_amd.fast_rcnn.config import cfg
+    saved_top, saved_train = dict(cfg), dict(cfg.TRAIN)
+
+    def set_keys(**kw):
+        for k, v in kw.items():
+            if k in ("SAMPLING_RNG", "DEVICE_RNG_SEED"):
+                cfg[k] = v
+            else:
+                assert k in cfg.TRAIN, k            # a typo must not set a key no layer reads
+                cfg.TRAIN[k] = v
+    try:
+        yield set_keys
+    finally:
+        cfg.TRAIN.clear()
+        cfg.TRAIN.update(saved_train)
+        cfg.clear()
+        cfg.update(saved_top)
+
+
 def ulp_diff_f32(a, b):
     a = np.ascontiguousarray(a, np.float32).view(np.int32).astype(np.int64)
     b = np.ascontiguousarray(b, np.float32).view(np.int32).astype(np.int64)
@@ -371,6 +394,60 @@ def test_anchor_target_joint_ws_golden(torch_cuda):
     assert tuple(g["ws_shape"]) == ws[1].shape and not ws[1].any() and not ws[2].any() and not ws[3].any()
 
 
+@pytest.mark.parametrize("switch", ["clobber", "overlaps", "overlaps_clobber", "posw_030", "posw_075", "posw_clobber",
+                                    "inside_w", "fg_quarter_64"])
+def test_anchor_target_switches_golden(torch_cuda, switch, product_cfg):
+    """Non-default cfg.TRAIN switches of the anchor-target layer against the reference's outputs
+    (anchor_target_switches.npz, reference RNG with the stored seeds): labels before and after sub-sampling and both
+    weight blobs bit for bit, targets as in test_anchor_target_golden."""
+    g = load_golden("anchor_target_switches")
+    base = load_golden("anchor_target_res_38x63")
+    H, W = int(g["H"]), int(g["W"])
+    score = np.zeros((1, H, W, 18), np.float32)
+    over = {"clobber": dict(RPN_CLOBBER_POSITIVES=True),
+            "overlaps": dict(RPN_POSITIVE_OVERLAP=0.5, RPN_NEGATIVE_OVERLAP=0.6),
+            "overlaps_clobber": dict(RPN_POSITIVE_OVERLAP=0.5, RPN_NEGATIVE_OVERLAP=0.6, RPN_CLOBBER_POSITIVES=True),
+            "posw_030": dict(RPN_POSITIVE_WEIGHT=0.3),
+            "posw_075": dict(RPN_POSITIVE_WEIGHT=0.75),
+            "posw_clobber": dict(RPN_POSITIVE_WEIGHT=0.75, RPN_CLOBBER_POSITIVES=True),
+            "inside_w": dict(RPN_BBOX_INSIDE_WEIGHTS=(0.1, 1.0, 0.0, 2.5)),
+            "fg_quarter_64": dict(RPN_FG_FRACTION=0.25, RPN_BATCHSIZE=64)}[switch]
+    from wssdl_bus_amd.rpn_msr.anchor_target_layer_tf_bus import anchor_target_layer
+    cases = sorted({k.split("/")[1] for k in g.files if k.startswith(switch + "/")})
+    assert len(cases) == 5
+    for name in cases:
+        k = "%s/%s/" % (switch, name)
+        gt, ng, ii = base[name + "/gt_boxes"][None], base[name + "/num_gt"], base[name + "/im_info"][None]
+        ds = str(base[name + "/dataset"])
+        product_cfg(SAMPLING_RNG="reference", **dict(over, RPN_BATCHSIZE=10 ** 9))
+        pre = anchor_target_layer(score, gt, ng, ii, None, STRIDE, SCALES, ds)
+        assert np.array_equal(pre[0].astype(np.int8), g[k + "labels_pre"]), k
+        product_cfg(**dict(dict(RPN_BATCHSIZE=256), **over))
+        fin = anchor_target_layer(score, gt, ng, ii, None, STRIDE, SCALES, ds, rng=np.random.RandomState(int(g[k + "seed"])))
+        assert np.array_equal(fin[0].astype(np.int8), g[k + "labels"]), k
+        assert ulp_diff_f32(fin[1], base[name + "/targets"]).max() <= 1, k
+        t, e = fin[1].reshape(9, 4, H, W), base[name + "/targets"].reshape(9, 4, H, W)
+        assert np.array_equal(t[:, :2], e[:, :2]), k
+        assert np.array_equal(fin[2], g[k + "inside_w"]), k
+        assert np.array_equal(fin[3], g[k + "outside_w"]), k
+
+
+def test_anchor_target_joint_switches_golden(torch_cuda, product_cfg):
+    """Joint train batch (1 supervised + 2 weak images) with clobbering, RPN_POSITIVE_WEIGHT and inside weights set:
+    no label-0 anchor is left, so the reference's negative weight (a division by zero) reaches no output."""
+    from wssdl_bus_amd.rpn_msr.anchor_target_layer_tf_bus import anchor_target_layer_joint
+    g = load_golden("anchor_target_switches")
+    j = load_golden("anchor_target_joint")
+    product_cfg(SAMPLING_RNG="reference", IMS_PER_BATCH=1, WS_IMS_PER_BATCH=2, RPN_CLOBBER_POSITIVES=True,
+                RPN_POSITIVE_WEIGHT=0.75, RPN_BBOX_INSIDE_WEIGHTS=(0.1, 1.0, 0.0, 2.5))
+    score = np.zeros((3, 38, 63, 18), np.float32)
+    jt = anchor_target_layer_joint(score, j["gt_boxes"], j["num_gt"], j["im_info"], None, True, STRIDE, SCALES, "SNUBH",
+                                   rng=np.random.RandomState(int(g["joint/seed"])))
+    assert np.array_equal(jt[0].astype(np.int8), g["joint/labels"])
+    assert ulp_diff_f32(jt[1], j["train_targets"]).max() <= 1
+    assert np.array_equal(jt[2], g["joint/inside_w"]) and np.array_equal(jt[3], g["joint/outside_w"])
+
+
 def test_anchor_target_device_sampling_invariants(torch_cuda):
     torch = torch_cuda
     from wssdl_bus_amd.fast_rcnn.config import cfg
@@ -400,7 +477,8 @@ def test_anchor_target_device_sampling_invariants(torch_cuda):
             # the side-by-side form (fg and bg drawn by two workgroups, given the label stage's counts)
             # draws exactly what the sequential form draws
             from wssdl_bus_amd import _lib
-            pre_t = torch.from_numpy(np.stack([pre, pre[::-1].copy()])).cuda()          # two "images"
+            flat = pre.reshape(-1)                                                         # one label per anchor
+            pre_t = torch.from_numpy(np.stack([flat, flat[::-1].copy()])).cuda()        # two "images"
             cnt = torch.tensor([[0, int((pre == 1).sum()), int((pre == 0).sum()), 0]] * 2, dtype=torch.int32,
                                device="cuda")
             for fg_frac, batch in ((0.5, 256), (0.0, 256), (0.5, 40), (1.0, 256)):
@@ -552,3 +630,38 @@ def test_proposal_target_golden(torch_cuda):
         cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED = False
         cfg.TRAIN.BBOX_NORMALIZE_MEANS, cfg.TRAIN.BBOX_NORMALIZE_STDS = saved
         cfg.TRAIN.IMS_PER_BATCH, cfg.TRAIN.WS_IMS_PER_BATCH = 1, 2
+
+
+@pytest.mark.parametrize("switch", ["overlap", "gap", "fg_one", "half_64", "big_batch", "inside_w"])
+def test_proposal_target_switches_golden(torch_cuda, switch, product_cfg):
+    """Non-default thresholds (overlapping bands, a gap between them, FG_THRESH = 1.0), FG_FRACTION / BATCH_SIZE and
+    BBOX_INSIDE_WEIGHTS against the reference's outputs (proposal_target_switches.npz, reference RNG): rows, labels
+    and weights bit for bit, targets within 4 ulp; joint mode with precomputed normalisation on."""
+    from wssdl_bus_amd.rpn_msr.proposal_target_layer_tf_bus import (
+        proposal_target_layer, proposal_target_layer_joint)
+    g = load_golden("proposal_target_switches")
+    p = load_golden("proposal_target")
+    rois, gt, ng = p["rois_in"], p["gt_boxes"], p["num_gt"]
+    over = {"overlap": dict(FG_THRESH=0.4, BG_THRESH_HI=0.6, BG_THRESH_LO=0.1),
+            "gap": dict(FG_THRESH=0.6, BG_THRESH_HI=0.3, BG_THRESH_LO=0.1),
+            "fg_one": dict(FG_THRESH=1.0),
+            "half_64": dict(FG_FRACTION=0.5, BATCH_SIZE=64),
+            "big_batch": dict(BATCH_SIZE=4096),
+            "inside_w": dict(BBOX_INSIDE_WEIGHTS=(0.1, 0.0, 2.0, -0.5))}[switch]
+
+    def check(o, tag):
+        for k, nm in enumerate(("rois", "labels", "targets", "inside", "outside")):
+            e = g["%s/%s/%s" % (switch, tag, nm)]
+            assert o[k].shape == e.shape, (tag, nm, o[k].shape, e.shape)
+            if nm == "targets":
+                assert ulp_diff_f32(o[k], e).max() <= 4, (tag, nm)
+            else:
+                assert np.array_equal(o[k], e), (tag, nm)
+
+    product_cfg(SAMPLING_RNG="reference", **over)
+    check(proposal_target_layer(rois, gt, ng, 3, True, False, rng=np.random.RandomState(int(g["seed_alt"]))),
+          "alt_train")
+    product_cfg(IMS_PER_BATCH=1, WS_IMS_PER_BATCH=1, BBOX_NORMALIZE_TARGETS_PRECOMPUTED=True,
+                BBOX_NORMALIZE_MEANS=tuple(g["means"]), BBOX_NORMALIZE_STDS=tuple(g["stds"]))
+    check(proposal_target_layer_joint(rois, gt, ng, 3, True, rng=np.random.RandomState(int(g["seed_joint"]))),
+          "joint_train")

@@ -14,6 +14,11 @@ from oracle import c_oracle, np_oracle as O, ref_kernels
 _spec = importlib.util.spec_from_file_location("make_golden_ref_cython", os.path.join(GOLDEN, "make_golden_ref_cython.py"))
 ref_cases = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(ref_cases)
+# the switch sets of make_golden_switches.py (its names of the cfg keys and values; the script only runs the reference
+# when it is executed)
+_spec = importlib.util.spec_from_file_location("make_golden_switches", os.path.join(GOLDEN, "make_golden_switches.py"))
+switch_sets = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(switch_sets)
 
 STRIDE = [16, ]
 SCALES = [8, 16, 32]
@@ -167,6 +172,82 @@ def test_anchor_target_golden(shape):
         assert (lab == 1).sum() <= 128 and (lab >= 0).sum() <= 256
 
 
+def _switch_sets(npz):
+    """{switch set: [case, ...]} of a make_golden_switches.py file (keys 'set/case/array')."""
+    sets = {}
+    for k in npz.files:
+        parts = k.split("/")
+        if len(parts) == 3:
+            sets.setdefault(parts[0], set()).add(parts[1])
+    return {s: sorted(c) for s, c in sets.items()}
+
+
+def test_anchor_target_switches_golden():
+    """Non-default cfg.TRAIN switches of the anchor-target layer (make_golden_switches.py): clobbering, the two
+    overlap thresholds, the positive weight, the inside weights and the fg fraction / batch size -- the
+    reference's labels before and after sub-sampling and its weights, bit for bit; the targets depend on none
+    of them (those of anchor_target_res_38x63.npz)."""
+    ANCHOR_JOINT, ANCHOR_SWITCHES = switch_sets.ANCHOR_JOINT, switch_sets.ANCHOR_SWITCHES
+    g = load_golden("anchor_target_switches")
+    base = load_golden("anchor_target_res_38x63")
+    H, W = int(g["H"]), int(g["W"])
+    score = np.zeros((1, H, W, 18), np.float32)
+    sets = _switch_sets(g)
+    assert sorted(sets) == sorted(ANCHOR_SWITCHES)
+    for sname, cases in sets.items():
+        over = dict(ANCHOR_SWITCHES[sname])
+        for name in cases:
+            k = "%s/%s/" % (sname, name)
+            gt, ng, ii = base[name + "/gt_boxes"][None], base[name + "/num_gt"], base[name + "/im_info"][None]
+            ds = str(base[name + "/dataset"])
+            pre = O.anchor_target_layer(score, gt, ng, ii, None, STRIDE, SCALES, ds,
+                                        cfg=dict(over, RPN_BATCHSIZE=10 ** 9))
+            assert np.array_equal(pre[0].astype(np.int8), g[k + "labels_pre"]), k
+            rng = np.random.RandomState(int(g[k + "seed"]))
+            with np.errstate(divide="ignore"):
+                fin = O.anchor_target_layer(score, gt, ng, ii, None, STRIDE, SCALES, ds, rng=rng, cfg=over)
+            assert np.array_equal(fin[0].astype(np.int8), g[k + "labels"]), k
+            assert np.array_equal(fin[1], base[name + "/targets"]), k
+            assert np.array_equal(fin[2], g[k + "inside_w"]), k
+            assert np.array_equal(fin[3], g[k + "outside_w"]), k
+    # the switches reach the fixtures: each set changes something a default run does not produce
+    assert (base["FILE04254/labels_pre"] == 0).sum() > 0 and (g["clobber/FILE04254/labels_pre"] == 0).sum() == 0
+    assert ((g["overlaps/twenty_fg/labels_pre"] == 1).sum() != (g["overlaps_clobber/twenty_fg/labels_pre"] == 1).sum())
+    iw = g["inside_w/twenty/inside_w"].reshape(9, 4, H, W)
+    lab = g["inside_w/twenty/labels"].reshape(9, H, W)
+    for j, w in enumerate((0.1, 1.0, 0.0, 2.5)):
+        assert np.all(iw[:, j][lab == 1] == np.float32(w)) and not iw[:, j][lab != 1].any()
+    assert len(np.unique(g["posw_030/FILE04254/outside_w"])) == 3                  # 0, pos and neg weights
+    # joint train batch (1 supervised + 2 weak images) with clobbering, a positive weight and inside weights
+    j = load_golden("anchor_target_joint")
+    score3 = np.zeros((3, H, W, 18), np.float32)
+    with np.errstate(divide="ignore"):
+        jt = O.anchor_target_layer_joint(score3, j["gt_boxes"], j["num_gt"], j["im_info"], None, True, STRIDE, SCALES,
+                                         "SNUBH", rng=np.random.RandomState(int(g["joint/seed"])), cfg=ANCHOR_JOINT)
+    assert np.array_equal(jt[0].astype(np.int8), g["joint/labels"])
+    assert np.array_equal(jt[1], j["train_targets"])
+    assert np.array_equal(jt[2], g["joint/inside_w"]) and np.array_equal(jt[3], g["joint/outside_w"])
+    assert np.all(np.isfinite(g["joint/outside_w"])) and not (g["joint/labels"] == 0).any()
+
+
+def test_rpn_positive_weight_range():
+    """The reference asserts 0 < RPN_POSITIVE_WEIGHT < 1 unless it is negative (anchor_target_layer_tf_bus.py:237-238);
+    the product's layer checks the same before it launches anything."""
+    from wssdl_bus_amd.fast_rcnn.config import cfg
+    from wssdl_bus_amd.rpn_msr.anchor_target_layer_tf_bus import rpn_positive_weight
+    saved = cfg.TRAIN.RPN_POSITIVE_WEIGHT
+    try:
+        for w in (-1.0, -0.5, 1e-9, 0.3, 0.75, 0.999999):
+            cfg.TRAIN.RPN_POSITIVE_WEIGHT = w
+            assert rpn_positive_weight() == w
+        for w in (0.0, 1.0, 1.5, float("nan"), float("inf")):
+            cfg.TRAIN.RPN_POSITIVE_WEIGHT = w
+            with pytest.raises(ValueError):
+                rpn_positive_weight()
+    finally:
+        cfg.TRAIN.RPN_POSITIVE_WEIGHT = saved
+
+
 def test_anchor_target_zero_overlap_quirk():
     g = load_golden("anchor_target_res_38x63")
     pre = g["outside_quirk/labels_pre"]
@@ -261,6 +342,46 @@ def test_proposal_target_golden_with_precomputed_normalisation():
     fg = p["alt_train/targets"] != 0
     scaled = (p["alt_train/targets"].astype(np.float64).reshape(-1, 3, 4) / g["stds"]).reshape(p["alt_train/targets"].shape)
     assert np.array_equal(scaled.astype(np.float32)[fg], g["alt_train/targets"][fg])
+
+
+def test_proposal_target_switches_golden():
+    """Non-default thresholds, fractions, batch sizes and inside weights of the proposal-target layer
+    (make_golden_switches.py), alternating mode and joint mode (the latter with precomputed normalisation on):
+    the reference's outputs bit for bit.  'overlap' has FG_THRESH < BG_THRESH_HI, where a row can be drawn
+    twice, once as fg and once as bg."""
+    PROPOSAL_SWITCHES, PT_NAMES = switch_sets.PROPOSAL_SWITCHES, switch_sets.PT_NAMES
+    g = load_golden("proposal_target_switches")
+    p = load_golden("proposal_target")
+    rois, gt, ng = p["rois_in"], p["gt_boxes"], p["num_gt"]
+    norm = dict(BBOX_NORMALIZE_TARGETS_PRECOMPUTED=True, BBOX_NORMALIZE_MEANS=tuple(g["means"]),
+                BBOX_NORMALIZE_STDS=tuple(g["stds"]))
+    sets = _switch_sets(g)
+    assert sorted(sets) == sorted(PROPOSAL_SWITCHES)
+    for sname in sets:
+        over = dict(PROPOSAL_SWITCHES[sname])
+        o = O.proposal_target_layer(rois, gt, ng, 3, True, False, rng=np.random.RandomState(int(g["seed_alt"])),
+                                    cfg=over)
+        for k, nm in enumerate(PT_NAMES):
+            assert np.array_equal(o[k], g["%s/alt_train/%s" % (sname, nm)]), (sname, nm)
+        o = O.proposal_target_layer_joint(rois, gt, ng, 3, True, rng=np.random.RandomState(int(g["seed_joint"])),
+                                          cfg=dict(over, IMS_PER_BATCH=1, WS_IMS_PER_BATCH=1, **norm))
+        for k, nm in enumerate(PT_NAMES):
+            assert np.array_equal(o[k], g["%s/joint_train/%s" % (sname, nm)]), (sname, nm)
+    # what the fixtures pin: the repeat of the overlapping bands, the one fg row per image at FG_THRESH = 1.0,
+    # more rows than BATCH_SIZE 64 allows nowhere, and outside weights that follow `inside > 0` per channel
+    r = g["overlap/alt_train/rois"]
+    img1 = [tuple(x) for x in r[r[:, 0] == 1].tolist()]
+    assert len(img1) - len(set(img1)) == 6
+    lab = g["fg_one/alt_train/labels"][:, 0]
+    assert (lab > 0).sum() == 2
+    assert g["half_64/alt_train/labels"].shape[0] <= 2 * 64 and g["big_batch/alt_train/labels"].shape[0] > 2 * 128
+    fg = g["inside_w/alt_train/labels"][:, 0] > 0
+    iw = g["inside_w/alt_train/inside"][fg].reshape(-1, 3, 4)
+    ow = g["inside_w/alt_train/outside"][fg].reshape(-1, 3, 4)
+    cls = g["inside_w/alt_train/labels"][fg, 0].astype(int)
+    for q in range(cls.size):
+        assert np.array_equal(iw[q, cls[q]], np.float32([0.1, 0.0, 2.0, -0.5]))
+        assert np.array_equal(ow[q, cls[q]], np.float32([1, 0, 1, 0]))
 
 
 def test_oracle_roundtrip_c_binding_shapes():

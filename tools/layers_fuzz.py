@@ -2,7 +2,9 @@
 """Random anchor-target, proposal-target and IoU cases, product against the NumPy oracle (oracle/np_oracle.py, itself pinned by the reference's
 goldens at three map shapes): random map shapes and image sizes, 1 ... 20 ground-truth rows of classes 0 / 1 / 2 (boxes partly or
 wholly outside the image, tiny ones, duplicates), datasets SNUBH / SNUBH_FG, with the reference's NumPy RNG stream for the
-sub-sampling.  Labels, sampled rows and weights bit for bit, regression targets within 1 ulp (anchors) / 4 ulp (RoIs: np.log in f32), IoU tables
+sub-sampling.  Two cases in three draw their own cfg.TRAIN switches: for the anchor targets RPN_CLOBBER_POSITIVES, the two
+overlap thresholds (either order), RPN_POSITIVE_WEIGHT and RPN_BBOX_INSIDE_WEIGHTS; for the proposal targets the fg / bg bands
+(disjoint, overlapping or gapped), FG_FRACTION, BATCH_SIZE and BBOX_INSIDE_WEIGHTS.  Labels, sampled rows and weights bit for bit, regression targets within 1 ulp (anchors) / 4 ulp (RoIs: np.log in f32), IoU tables
 bit for bit.
     python3 tools/layers_fuzz.py [--cases 60] [--seed 0]"""
 import argparse
@@ -59,7 +61,22 @@ for k in range(args.cases):
     ds = "SNUBH_FG" if k % 3 == 0 else "SNUBH"
     score = np.zeros((1, H, W, 18), np.float32)
     seed = 1000 + k
-    want = O.anchor_target_layer(score, gt[None], ng, ii, None, (16,), (8, 16, 32), ds, rng=np.random.RandomState(seed))
+    sw = {}                                                   # this case's switches, on the product's cfg and the oracle's
+    if k % 3 != 2:
+        pos, neg = (float(x) for x in np.round(rs.uniform(0.2, 0.8, size=2), 2))
+        fg_t = float(np.round(rs.uniform(0.2, 0.8), 2))
+        hi = float(np.round(rs.uniform(0.15, 0.8), 2))
+        sw = dict(RPN_CLOBBER_POSITIVES=bool(rs.randint(2)), RPN_POSITIVE_OVERLAP=pos, RPN_NEGATIVE_OVERLAP=neg,
+                  RPN_POSITIVE_WEIGHT=float(rs.choice([-1.0, 0.3, 0.75, 0.1])),
+                  RPN_BBOX_INSIDE_WEIGHTS=tuple(float(x) for x in rs.choice([0.0, 0.1, 1.0, 2.5], size=4)),
+                  FG_THRESH=fg_t, BG_THRESH_HI=hi, BG_THRESH_LO=float(np.round(rs.uniform(0.0, min(hi, fg_t)), 2)),
+                  FG_FRACTION=float(rs.choice([0.25, 0.5])), BATCH_SIZE=int(rs.choice([128, 64, 32])),
+                  BBOX_INSIDE_WEIGHTS=tuple(float(x) for x in rs.choice([-0.5, 0.0, 0.1, 1.0, 2.0], size=4)))
+    defaults = {key: cfg.TRAIN[key] for key in sw}
+    cfg.TRAIN.update(sw)
+    with np.errstate(divide="ignore"):          # a positive weight with no label-0 anchor: the unused negative weight
+        want = O.anchor_target_layer(score, gt[None], ng, ii, None, (16,), (8, 16, 32), ds, rng=np.random.RandomState(seed),
+                                     cfg=sw)
     got = anchor_target_layer(score, gt[None], ng, ii, None, [16], [8, 16, 32], ds, rng=np.random.RandomState(seed))
     ok = np.array_equal(np.asarray(got[0]), want[0]) and ulp(got[1], want[1]).max() <= 1 and \
         np.array_equal(np.asarray(got[2]), want[2]) and np.array_equal(np.asarray(got[3]), want[3])
@@ -93,7 +110,7 @@ for k in range(args.cases):
     rois = np.concatenate(rl)
     ok_pt = True
     for tr, ws in ((True, False), (True, True), (False, False)):
-        w_ = O.proposal_target_layer(rois, gts, ngs, 3, tr, ws, rng=np.random.RandomState(seed))
+        w_ = O.proposal_target_layer(rois, gts, ngs, 3, tr, ws, rng=np.random.RandomState(seed), cfg=sw)
         g_ = proposal_target_layer(rois, gts, ngs, 3, tr, ws, rng=np.random.RandomState(seed))
         for j in range(5):
             a, e = np.asarray(g_[j]), w_[j]
@@ -102,7 +119,7 @@ for k in range(args.cases):
     n_s = int(rs.randint(1, Ni + 1))
     old_ims = (cfg.TRAIN.IMS_PER_BATCH, cfg.TRAIN.WS_IMS_PER_BATCH)
     cfg.TRAIN.IMS_PER_BATCH, cfg.TRAIN.WS_IMS_PER_BATCH = n_s, Ni - n_s
-    oc = dict(IMS_PER_BATCH=n_s, WS_IMS_PER_BATCH=Ni - n_s)
+    oc = dict(sw, IMS_PER_BATCH=n_s, WS_IMS_PER_BATCH=Ni - n_s)
     try:
         for tr in (True, False):
             w_ = O.proposal_target_layer_joint(rois, gts, ngs, 3, tr, rng=np.random.RandomState(seed), cfg=oc)
@@ -114,17 +131,20 @@ for k in range(args.cases):
         scoreN = np.zeros((Ni, H, W, 18), np.float32)
         for tr in (True, False):
             sc_in = scoreN if tr else scoreN[:n_s]
-            w_ = O.anchor_target_layer_joint(sc_in, gts[:len(sc_in)], ngs[:len(sc_in)], iis[:len(sc_in)], None, tr, (16,), (8, 16, 32), ds,
-                                             rng=np.random.RandomState(seed), cfg=oc)
+            with np.errstate(divide="ignore"):
+                w_ = O.anchor_target_layer_joint(sc_in, gts[:len(sc_in)], ngs[:len(sc_in)], iis[:len(sc_in)], None, tr, (16,), (8, 16, 32),
+                                                 ds, rng=np.random.RandomState(seed), cfg=oc)
             g_ = anchor_target_layer_joint(sc_in, gts[:len(sc_in)], ngs[:len(sc_in)], iis[:len(sc_in)], None, tr, [16], [8, 16, 32], ds,
                                            rng=np.random.RandomState(seed))
             ok = ok and np.array_equal(np.asarray(g_[0]), w_[0]) and ulp(g_[1], w_[1]).max() <= 1 and \
                 np.array_equal(np.asarray(g_[2]), w_[2]) and np.array_equal(np.asarray(g_[3]), w_[3])
     finally:
         cfg.TRAIN.IMS_PER_BATCH, cfg.TRAIN.WS_IMS_PER_BATCH = old_ims
+        cfg.TRAIN.update(defaults)
     if not (ok and ok_iou and ok_pt):
         bad += 1
-        print("MISMATCH case %d map %dx%d image %dx%d gt %d %s: anchor targets %s, IoU %s, proposal targets %s" % (k, H, W, im_h, im_w, n, ds, ok, ok_iou, ok_pt), flush=True)
+        print("MISMATCH case %d map %dx%d image %dx%d gt %d %s: anchor targets %s, IoU %s, proposal targets %s; switches %s" % (
+            k, H, W, im_h, im_w, n, ds, ok, ok_iou, ok_pt, sw), flush=True)
     if (k + 1) % 20 == 0:
         print("case %d ok so far (%d mismatches)" % (k + 1, bad), flush=True)
 print("cases %d mismatches %d" % (args.cases, bad))

@@ -2,8 +2,10 @@
 """Random cases for the DEVICE samplers (cfg.SAMPLING_RNG = 'device': wssdl_anchor_subsample_device, wssdl_roi_sample_device -- a
 counter-based device RNG, not NumPy's stream, so the checks are structural): the sub-sampled anchor labels are a subset of the
 oracle's pre-sub-sampling labels with the reference's quotas (:202-217) and weights; the sampled RoIs are candidates of their
-image, none more often than it occurs, within the fg / bg overlap bands and quotas (_sample_rois :228-280), with the oracle's labels,
-regression targets (4 ulp) and weights; the same seed gives the same draw.
+image, within the fg / bg overlap bands and quotas (_sample_rois :228-280), none more often IN ITS CLASS than it occurs (the fg and
+the bg pool are independent: with overlapping bands the reference may draw a row once as fg and once as bg), with the oracle's
+labels, regression targets (4 ulp) and weights; the same seed gives the same draw.  Each case draws its own RPN_FG_FRACTION /
+RPN_BATCHSIZE and FG_THRESH / BG_THRESH_HI / BG_THRESH_LO (disjoint, overlapping and gapped bands).
     python3 tools/sampler_fuzz.py [--cases 40] [--seed 0]"""
 import argparse
 import collections
@@ -35,11 +37,26 @@ ap.add_argument("--cases", type=int, default=40)
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 rs = np.random.RandomState(args.seed)
-old = cfg.SAMPLING_RNG, cfg.DEVICE_RNG_SEED, cfg.TRAIN.RPN_BATCHSIZE
+SWITCHES = ("RPN_BATCHSIZE", "RPN_FG_FRACTION", "FG_THRESH", "BG_THRESH_HI", "BG_THRESH_LO")
+old = cfg.SAMPLING_RNG, cfg.DEVICE_RNG_SEED, {key: cfg.TRAIN[key] for key in SWITCHES}
 bad = 0
 try:
     for k in range(args.cases):
         why = []
+        # the switches of this case: anchor quotas, and RoI overlap bands of the three kinds
+        cfg.TRAIN.update(old[2])
+        batch = int(rs.choice([256, 64, 40, 512]))
+        frac = float(rs.choice([0.5, 0.25, 0.0, 1.0]))
+        cfg.TRAIN.RPN_BATCHSIZE, cfg.TRAIN.RPN_FG_FRACTION = batch, frac
+        band = k % 3
+        if band == 1:                                                          # overlapping: FG_THRESH < BG_THRESH_HI
+            fg_t = float(rs.uniform(0.2, 0.5))
+            cfg.TRAIN.FG_THRESH, cfg.TRAIN.BG_THRESH_HI = fg_t, float(rs.uniform(fg_t + 0.05, 0.8))
+            cfg.TRAIN.BG_THRESH_LO = float(rs.uniform(0.0, fg_t))
+        elif band == 2:                                                        # a gap between the bands
+            hi = float(rs.uniform(0.15, 0.5))
+            cfg.TRAIN.FG_THRESH, cfg.TRAIN.BG_THRESH_HI = float(rs.uniform(hi + 0.05, 0.9)), hi
+            cfg.TRAIN.BG_THRESH_LO = float(rs.uniform(0.0, hi - 0.1))
         H, W = int(rs.randint(14, 64)), int(rs.randint(14, 101))
         im_h, im_w = H * 16 - int(rs.randint(0, 16)), W * 16 - int(rs.randint(0, 16))
         n = int(rs.randint(1, MAX_GT + 1))
@@ -63,7 +80,7 @@ try:
         lab = outs[0][0].cpu().numpy().astype(np.int8).reshape(-1)
         n_fg_pre, n_bg_pre = int((O_pre == 1).sum()), int((O_pre == 0).sum())
         n_fg, n_bg = int((lab == 1).sum()), int((lab == 0).sum())
-        if n_fg != min(n_fg_pre, 128) or n_bg != min(n_bg_pre, 256 - n_fg):
+        if n_fg != min(n_fg_pre, int(frac * batch)) or n_bg != min(n_bg_pre, batch - n_fg):
             why.append("anchor quotas %d/%d of %d/%d" % (n_fg, n_bg, n_fg_pre, n_bg_pre))
         if not (np.all(O_pre[lab == 1] == 1) and np.all(O_pre[lab == 0] == 0)):
             why.append("anchor labels not a subset of the pre-sub-sampling labels")
@@ -124,10 +141,13 @@ try:
             if not np.all(out_rois[pad, 0] == -1) or out_rois[pad, 1:].any() or not np.all(labels[pad, 0] == -1) or \
                     tg[pad].any() or inw[pad].any() or outw[pad].any():
                 why.append("padding rows of image %d" % i)
-            have = collections.Counter(tuple(r) for r in cand.tolist())
-            drawn = collections.Counter(tuple(r) for r in blk.tolist())
-            if any(drawn[t] > have.get(t, 0) for t in drawn):
-                why.append("a row drawn more often than it occurs among the candidates (image %d)" % i)
+            in_fg = mo >= cfg.TRAIN.FG_THRESH
+            in_bg = (mo < cfg.TRAIN.BG_THRESH_HI) & (mo >= cfg.TRAIN.BG_THRESH_LO)
+            for name, pool, part in (("fg", in_fg, blk[:n_fg]), ("bg", in_bg, blk[n_fg:])):
+                have = collections.Counter(tuple(r) for r in cand[pool].tolist())
+                drawn = collections.Counter(tuple(r) for r in part.tolist())
+                if any(drawn[t] > have.get(t, 0) for t in drawn):
+                    why.append("a %s row drawn more often than it occurs in its pool (image %d)" % (name, i))
             lookup = {}
             for j, r in enumerate(cand.tolist()):
                 lookup.setdefault(tuple(r), j)
@@ -157,10 +177,13 @@ try:
             why.append("row count %d against %d" % (out_rois.shape[0], Ni * rpi))
         if why:
             bad += 1
-            print("MISMATCH case %d map %dx%d gt %d images %d: %s" % (k, H, W, n, Ni, "; ".join(why[:3])), flush=True)
+            print("MISMATCH case %d map %dx%d gt %d images %d batch %d frac %g bands %g/%g/%g: %s" % (
+                k, H, W, n, Ni, batch, frac, cfg.TRAIN.FG_THRESH, cfg.TRAIN.BG_THRESH_HI, cfg.TRAIN.BG_THRESH_LO,
+                "; ".join(why[:3])), flush=True)
         if (k + 1) % 10 == 0:
             print("case %d ok so far (%d mismatches)" % (k + 1, bad), flush=True)
 finally:
-    cfg.SAMPLING_RNG, cfg.DEVICE_RNG_SEED, cfg.TRAIN.RPN_BATCHSIZE = old
+    cfg.SAMPLING_RNG, cfg.DEVICE_RNG_SEED = old[:2]
+    cfg.TRAIN.update(old[2])
 print("cases %d mismatches %d" % (args.cases, bad))
 sys.exit(1 if bad else 0)

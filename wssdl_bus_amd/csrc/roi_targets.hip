@@ -14,6 +14,8 @@
 //                 min(quota, #) fg and bg rows by 64-bit radix select on
 //                 counter-based hash keys; rows come out in candidate order
 //                 (fg first), so a run is reproducible from the seed alone.
+//                 The fg and bg bands are independent pools, as in :241,
+//                 :253-254: when they overlap, a row can be drawn twice.
 // roi_targets   : one lane per sampled RoI: label (background clamped to 0, :265),
 //                 all-f32 bbox_transform (:220), expansion into the 4*num_classes
 //                 layout with inside / outside weights (:199-209, :89).
@@ -196,23 +198,26 @@ __device__ __forceinline__ unsigned long long rs_key(unsigned long long seed, in
     return (h & 0xFFFFFFFF00000000ull) | (unsigned)i;
 }
 
+// class bits of a candidate row
+constexpr int RS_FG = 1, RS_BG = 2;
+
 struct RoiClassifier {          // _sample_rois :241, :253-254
     const float *cand;
     const double *ov;
     int img;
     double fg_thresh, bg_hi, bg_lo;
-    // 1 = fg, 0 = bg, -1 = neither / other image
+    // RS_FG | RS_BG, tested independently as in the reference: with FG_THRESH < BG_THRESH_HI a row is in both
+    // pools and may be drawn once as fg and once as bg; 0 = neither / other image
     __device__ __forceinline__ int operator()(int i) const {
-        if ((int)cand[(size_t)i * 5] != img) return -1;
+        if ((int)cand[(size_t)i * 5] != img) return 0;
         const double o = ov[i];
-        if (o >= fg_thresh) return 1;
-        return (o < bg_hi && o >= bg_lo) ? 0 : -1;
+        return (o >= fg_thresh ? RS_FG : 0) | ((o < bg_hi && o >= bg_lo) ? RS_BG : 0);
     }
 };
 
 constexpr int RS_LIST = 512;
 
-// key of the quota-th smallest among the candidates of class `which` (all of them when there
+// key of the quota-th smallest among the candidates of class bit `which` (all of them when there
 // are no more than quota: returns ~0)
 __device__ unsigned long long rs_select(const RoiClassifier &cls, int lo, int hi, int which, int n_have,
                                         int quota, unsigned long long seed,
@@ -221,7 +226,7 @@ __device__ unsigned long long rs_select(const RoiClassifier &cls, int lo, int hi
     return block_radix_select<RS_BLOCK, RS_LIST, false>(
         [=](int j, unsigned long long &v) {
             const int i = lo + j;
-            if (cls(i) != which) return false;
+            if (!(cls(i) & which)) return false;
             v = rs_key(seed, cls.img, i);
             return true;
         }, hi - lo, [quota](int) { return quota; }, sc);
@@ -282,8 +287,8 @@ __global__ __launch_bounds__(RS_BLOCK) void roi_sample_kernel(
     }
     __syncthreads();
     const int lo = min(s_lo, s_hi), hi = s_hi;
-    // each thread owns a contiguous slice of the span so that the output keeps the candidate order; the class
-    // of its rows is kept in two bit masks (slices of up to 32 rows; longer ones re-read)
+    // each thread owns a contiguous slice of the span so that the output keeps the candidate order; the classes
+    // of its rows are kept in two bit masks (slices of up to 32 rows; longer ones re-read)
     const int per = (hi - lo + RS_BLOCK - 1) / RS_BLOCK;
     const int i0 = min(lo + t * per, hi), i1 = min(i0 + per, hi);
     const bool masked = per <= 32;
@@ -291,11 +296,16 @@ __global__ __launch_bounds__(RS_BLOCK) void roi_sample_kernel(
     int cf = 0, cb = 0;
     for (int i = i0; i < i1; ++i) {
         const int c = cls(i);
-        cf += c == 1;
-        cb += c == 0;
-        if (masked) { m_fg |= (unsigned)(c == 1) << (i - i0);  m_bg |= (unsigned)(c == 0) << (i - i0); }
+        cf += (c & RS_FG) != 0;
+        cb += (c & RS_BG) != 0;
+        if (masked) {
+            m_fg |= (unsigned)((c & RS_FG) != 0) << (i - i0);
+            m_bg |= (unsigned)((c & RS_BG) != 0) << (i - i0);
+        }
     }
-    auto class_of = [&](int i) { return masked ? (int)((m_fg >> (i - i0)) & 1u) - (int)(1u & ~((m_fg | m_bg) >> (i - i0))) : cls(i); };
+    auto class_of = [&](int i) {
+        return masked ? (int)((m_fg >> (i - i0)) & 1u) * RS_FG | (int)((m_bg >> (i - i0)) & 1u) * RS_BG : cls(i);
+    };
     int have_fg, have_bg;
     rs_block_exclusive_scan(cf, s_wave, have_fg);
     rs_block_exclusive_scan(cb, s_wave, have_bg);
@@ -305,15 +315,15 @@ __global__ __launch_bounds__(RS_BLOCK) void roi_sample_kernel(
     // the fg rows, workgroup (s, 1) the bg rows (and the padding) -- half the latency of the chain
     const bool do_fg = gridDim.y == 1 || blockIdx.y == 0, do_bg = gridDim.y == 1 || blockIdx.y == 1;
     unsigned long long t_fg = 0ull, t_bg = 0ull;
-    if (do_fg) t_fg = rs_select(cls, lo, hi, 1, have_fg, n_fg, seed, sc);
-    if (do_bg) t_bg = rs_select(cls, lo, hi, 0, have_bg, n_bg, seed ^ 0x5bd1e995ull, sc);
+    if (do_fg) t_fg = rs_select(cls, lo, hi, RS_FG, have_fg, n_fg, seed, sc);
+    if (do_bg) t_bg = rs_select(cls, lo, hi, RS_BG, have_bg, n_bg, seed ^ 0x5bd1e995ull, sc);
     const bool emit_fg = do_fg && n_fg > 0, emit_bg = do_bg && n_bg > 0;
     cf = cb = 0;
     if (emit_fg || emit_bg)
         for (int i = i0; i < i1; ++i) {
             const int c = class_of(i);
-            if (c == 1) cf += (emit_fg && rs_key(seed, cls.img, i) <= t_fg);
-            else if (c == 0) cb += (emit_bg && rs_key(seed ^ 0x5bd1e995ull, cls.img, i) <= t_bg);
+            cf += (c & RS_FG) && emit_fg && rs_key(seed, cls.img, i) <= t_fg;
+            cb += (c & RS_BG) && emit_bg && rs_key(seed ^ 0x5bd1e995ull, cls.img, i) <= t_bg;
         }
     int tot;
     int pf = rs_block_exclusive_scan(cf, s_wave, tot);
@@ -323,8 +333,8 @@ __global__ __launch_bounds__(RS_BLOCK) void roi_sample_kernel(
     if (emit_fg || emit_bg)
         for (int i = i0; i < i1; ++i) {
             const int c = class_of(i);
-            if (c == 1 && emit_fg && rs_key(seed, cls.img, i) <= t_fg) { kp[pf] = i; fp[pf] = 1; ++pf; }
-            else if (c == 0 && emit_bg && rs_key(seed ^ 0x5bd1e995ull, cls.img, i) <= t_bg) { kp[pb] = i; fp[pb] = 0; ++pb; }
+            if ((c & RS_FG) && emit_fg && rs_key(seed, cls.img, i) <= t_fg) { kp[pf] = i; fp[pf] = 1; ++pf; }
+            if ((c & RS_BG) && emit_bg && rs_key(seed ^ 0x5bd1e995ull, cls.img, i) <= t_bg) { kp[pb] = i; fp[pb] = 0; ++pb; }
         }
     if (do_bg) {
         for (int p = n_fg + n_bg + t; p < rois_per_image; p += RS_BLOCK) { kp[p] = -1; fp[p] = 0; }

@@ -41,6 +41,16 @@ def _device_of(*xs):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def rpn_positive_weight():
+    """cfg.TRAIN.RPN_POSITIVE_WEIGHT, checked as the reference asserts it (:237-238): a negative value means uniform
+    weights 1/#examples; otherwise it must lie in (0, 1).  Raises ValueError before any launch."""
+    w = float(cfg.TRAIN.RPN_POSITIVE_WEIGHT)
+    if not (w < 0 or 0 < w < 1):
+        raise ValueError("cfg.TRAIN.RPN_POSITIVE_WEIGHT must be negative (uniform weights) or in (0, 1), got %r"
+                         % cfg.TRAIN.RPN_POSITIVE_WEIGHT)
+    return w
+
+
 def _subsample_reference(labels_pre, rng):
     """anchor_target_layer_tf_bus.py:202-217 on a host copy of the labels, consuming
     `rng` (numpy.random by default) exactly like the reference."""
@@ -96,6 +106,7 @@ def anchor_targets(labels, argmax, gt, anchors, n_images, n_out, height, width, 
                    device):
     """Stage 3: final labels -> the four output blobs for n_out images (images
     n_images..n_out-1 are all-ignore)."""
+    positive_weight = rpn_positive_weight()
     A = anchors.shape[0]
     stride = int(np.asarray(_feat_stride).ravel()[0])
     iw = np.ascontiguousarray(cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS, dtype=np.float32)
@@ -107,7 +118,7 @@ def anchor_targets(labels, argmax, gt, anchors, n_images, n_out, height, width, 
         _lib.check(_lib.lib().wssdl_anchor_targets(
             _lib.ptr(labels), _lib.ptr(argmax), _lib.ptr(gt), gt.shape[1] if gt is not None else 1,
             n_images, n_out, height, width, _lib.host_ptr(anchors), A, stride, _lib.host_ptr(iw),
-            float(cfg.TRAIN.RPN_POSITIVE_WEIGHT), _lib.ptr(rpn_labels), _lib.ptr(tg),
+            positive_weight, _lib.ptr(rpn_labels), _lib.ptr(tg),
             _lib.ptr(inw), _lib.ptr(outw), _lib.stream()), "wssdl_anchor_targets")
     return rpn_labels, tg, inw, outw
 
@@ -127,6 +138,7 @@ def _run(rpn_cls_score, gt_boxes, num_gt_boxes, im_info, n_images, n_out, _feat_
 
 def _run_device(gt_boxes, num_gt_boxes, im_info, n_images, n_out, height, width, _feat_stride,
                 anchor_scales, dataset, rng, dev):
+    rpn_positive_weight()               # before the label stage's launches
     if n_images > 0:
         labels, argmax, counts, gt, anchors = anchor_labels(
             gt_boxes, num_gt_boxes, im_info, n_images, height, width, _feat_stride, anchor_scales,
