@@ -16,6 +16,8 @@
 // loaded), the statistics are taken over the live rows (n = per * sum(mask), computed on the device:
 // no host read-back), and the layer writes zeros for dead rows in both directions, so the live rows
 // come out exactly as if the blob had been compacted first.
+// The *_masked_pm entry points take the same mask on POSITION-MAJOR rows (row r belongs to RoI
+// r % n_rois: the head's 4x4 section, networks/roi_head.py); statistics and outputs are the same.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,11 +30,18 @@ constexpr int MAX_PARTIAL_BLOCKS = 1024;
 
 typedef float float4v __attribute__((ext_vector_type(4)));
 
+// RoI of row r under the live-row mask: MASK 1 = roi-major rows (r / div, div = per),
+// MASK 2 = position-major rows (r % div, div = n_rois).  (M < 2^31 is checked by the entry points.)
+template <int MASK>
+__device__ __forceinline__ unsigned mask_roi(long long r, int div) {
+    return MASK == 2 ? (unsigned)r % (unsigned)div : (unsigned)r / (unsigned)div;
+}
+
 // Partial column sums of one row slab.  Thread t owns float4 column (t % L) + cc * L and the
 // rows r0 + t / L + k * RS; L = min(C/4, 256), RS = 256 / L.
 // MODE 0: s = sum x,  q = sum x*x
 // MODE 1: s = sum g,  q = sum g*x   with g = dy, masked by (x*scale + shift > 0) when RELU
-template <int MODE, bool RELU, bool MASKED>
+template <int MODE, bool RELU, int MASK>
 __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ scale,
     const float *__restrict__ shift, long long M, int C, long long rows_per_block,
@@ -59,9 +68,9 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
             // two rows in flight per step
             for (; r + RS < r1; r += 2 * RS) {
                 bool live0 = true, live1 = true;
-                if (MASKED) {
-                    live0 = mask[(unsigned)r / (unsigned)per] != 0.0f;
-                    live1 = mask[(unsigned)(r + RS) / (unsigned)per] != 0.0f;
+                if (MASK) {
+                    live0 = mask[mask_roi<MASK>(r, per)] != 0.0f;
+                    live1 = mask[mask_roi<MASK>(r + RS, per)] != 0.0f;
                     if (!live0 && !live1) continue;
                 }
                 const float4v zero4 = {0, 0, 0, 0};
@@ -83,7 +92,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
                             if (!(a0[j] * sc[j] + sh[j] > 0.0f)) u0 = 0.0f;
                             if (!(a1[j] * sc[j] + sh[j] > 0.0f)) u1 = 0.0f;
                         }
-                        if (MASKED) {               // a dead row adds nothing (x = 0 would still pass the ReLU test)
+                        if (MASK) {                 // a dead row adds nothing (x = 0 would still pass the ReLU test)
                             if (!live0) u0 = 0.0f;
                             if (!live1) u1 = 0.0f;
                         }
@@ -93,7 +102,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
                 }
             }
             for (; r < r1; r += RS) {
-                if (MASKED && mask[(unsigned)r / (unsigned)per] == 0.0f) continue;
+                if (MASK && mask[mask_roi<MASK>(r, per)] == 0.0f) continue;
                 const float4v a0 = reinterpret_cast<const float4v *>(x + (size_t)r * C)[c4];
                 float4v g0;
                 if (MODE == 1) g0 = reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4];
@@ -222,14 +231,14 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_kernel
     coef[2 * C + c] = (float)k1;
 }
 
-template <bool RELU, bool MASKED>
+template <bool RELU, int MASK>
 __global__ __launch_bounds__(BLOCK) void rowbn_apply_fwd_kernel(
     const float *__restrict__ x, const float *__restrict__ scale, const float *__restrict__ shift,
     long long total4, int C4, float *__restrict__ y, const float *__restrict__ mask, int per) {
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total4;
          i += (long long)gridDim.x * BLOCK) {
         const int c4 = (int)(i % C4);
-        if (MASKED && mask[(unsigned)(i / C4) / (unsigned)per] == 0.0f) {
+        if (MASK && mask[mask_roi<MASK>(i / C4, per)] == 0.0f) {
             const float4v zero4 = {0, 0, 0, 0};
             reinterpret_cast<float4v *>(y)[i] = zero4;
             continue;
@@ -248,7 +257,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_fwd_kernel(
     }
 }
 
-template <bool RELU, bool MASKED>
+template <bool RELU, int MASK>
 __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ scale,
     const float *__restrict__ shift, const float *__restrict__ coef, long long total4, int C4,
@@ -257,7 +266,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total4;
          i += (long long)gridDim.x * BLOCK) {
         const int c4 = (int)(i % C4);
-        if (MASKED && mask[(unsigned)(i / C4) / (unsigned)per] == 0.0f) {
+        if (MASK && mask[mask_roi<MASK>(i / C4, per)] == 0.0f) {
             const float4v zero4 = {0, 0, 0, 0};
             reinterpret_cast<float4v *>(dx)[i] = zero4;
             continue;
@@ -317,27 +326,32 @@ PLUMB_API int wsplumb_rowbn_supported(long long M, int C) { return shape_ok(M, C
 static int forward_impl(const float *x, long long M, int C, const float *weight, const float *bias, float eps,
                         int relu, float *y, float *mean, float *var, float *rstd, float *scale, float *shift,
                         const float *mask, int n_rois, int per, float *count, void *workspace,
-                        size_t workspace_bytes, void *stream) {
+                        size_t workspace_bytes, void *stream, bool pm = false) {
     if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
     if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nb = partial_blocks(M, C);
     const long long rpb = (M + nb - 1) / nb;
     double *partial = static_cast<double *>(workspace);
-    if (mask)
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, true>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
+    const int div = pm ? n_rois : per;          // row -> RoI divisor of the mask modes (mask_roi)
+    if (mask && pm)
+        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 2>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
+                           nullptr, nullptr, M, C, rpb, partial, mask, div);
+    else if (mask)
+        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 1>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
                            nullptr, nullptr, M, C, rpb, partial, mask, per);
     else
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, false>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
+        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 0>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
                            nullptr, nullptr, M, C, rpb, partial, nullptr, 1);
     hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st, partial, nb, C,
                        M, weight, bias, eps, mean, var, rstd, scale, shift, mask, n_rois, per, count);
     const long long total4 = M * (C / 4);
-#define WSPLUMB_APPLY(RELU, MASKED) \
-    hipLaunchKernelGGL((rowbn_apply_fwd_kernel<RELU, MASKED>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, scale, \
-                       shift, total4, C / 4, y, mask, per)
-    if (relu) { if (mask) WSPLUMB_APPLY(true, true); else WSPLUMB_APPLY(true, false); }
-    else { if (mask) WSPLUMB_APPLY(false, true); else WSPLUMB_APPLY(false, false); }
+#define WSPLUMB_APPLY(RELU, MASK) \
+    hipLaunchKernelGGL((rowbn_apply_fwd_kernel<RELU, MASK>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, scale, \
+                       shift, total4, C / 4, y, mask, div)
+    const int mode = mask ? (pm ? 2 : 1) : 0;
+    if (relu) { if (mode == 2) WSPLUMB_APPLY(true, 2); else if (mode) WSPLUMB_APPLY(true, 1); else WSPLUMB_APPLY(true, 0); }
+    else { if (mode == 2) WSPLUMB_APPLY(false, 2); else if (mode) WSPLUMB_APPLY(false, 1); else WSPLUMB_APPLY(false, 0); }
 #undef WSPLUMB_APPLY
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
@@ -372,10 +386,10 @@ PLUMB_API int wsplumb_rowbn_apply(const float *x, long long M, int C, const floa
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long total4 = M * (C / 4);
     if (relu)
-        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, false>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x,
+        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 0>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x,
                            scale, shift, total4, C / 4, y, nullptr, 1);
     else
-        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<false, false>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x,
+        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<false, 0>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x,
                            scale, shift, total4, C / 4, y, nullptr, 1);
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
@@ -383,27 +397,29 @@ PLUMB_API int wsplumb_rowbn_apply(const float *x, long long M, int C, const floa
 static int backward_impl(const float *x, const float *dy, long long M, int C, const float *weight,
                          const float *mean, const float *rstd, const float *scale, const float *shift, int relu,
                          float *dx, float *dweight, float *dbias, float *coef, const float *mask, int n_rois,
-                         int per, void *workspace, size_t workspace_bytes, void *stream) {
+                         int per, void *workspace, size_t workspace_bytes, void *stream, bool pm = false) {
     if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
     if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nb = partial_blocks(M, C);
     const long long rpb = (M + nb - 1) / nb;
     double *partial = static_cast<double *>(workspace);
-#define WSPLUMB_PARTIAL(RELU, MASKED) \
-    hipLaunchKernelGGL((rowbn_partial_kernel<1, RELU, MASKED>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M, C, \
-                       rpb, partial, mask, per)
-    if (relu) { if (mask) WSPLUMB_PARTIAL(true, true); else WSPLUMB_PARTIAL(true, false); }
-    else { if (mask) WSPLUMB_PARTIAL(false, true); else WSPLUMB_PARTIAL(false, false); }
+    const int div = pm ? n_rois : per;
+    const int mode = mask ? (pm ? 2 : 1) : 0;
+#define WSPLUMB_PARTIAL(RELU, MASK) \
+    hipLaunchKernelGGL((rowbn_partial_kernel<1, RELU, MASK>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M, C, \
+                       rpb, partial, mask, div)
+    if (relu) { if (mode == 2) WSPLUMB_PARTIAL(true, 2); else if (mode) WSPLUMB_PARTIAL(true, 1); else WSPLUMB_PARTIAL(true, 0); }
+    else { if (mode == 2) WSPLUMB_PARTIAL(false, 2); else if (mode) WSPLUMB_PARTIAL(false, 1); else WSPLUMB_PARTIAL(false, 0); }
 #undef WSPLUMB_PARTIAL
     hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st, partial, nb, C,
                        M, weight, mean, rstd, dweight, dbias, coef, mask, n_rois, per);
     const long long total4 = M * (C / 4);
-#define WSPLUMB_APPLY(RELU, MASKED) \
-    hipLaunchKernelGGL((rowbn_apply_bwd_kernel<RELU, MASKED>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy, scale, \
-                       shift, coef, total4, C / 4, dx, mask, per)
-    if (relu) { if (mask) WSPLUMB_APPLY(true, true); else WSPLUMB_APPLY(true, false); }
-    else { if (mask) WSPLUMB_APPLY(false, true); else WSPLUMB_APPLY(false, false); }
+#define WSPLUMB_APPLY(RELU, MASK) \
+    hipLaunchKernelGGL((rowbn_apply_bwd_kernel<RELU, MASK>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy, scale, \
+                       shift, coef, total4, C / 4, dx, mask, div)
+    if (relu) { if (mode == 2) WSPLUMB_APPLY(true, 2); else if (mode) WSPLUMB_APPLY(true, 1); else WSPLUMB_APPLY(true, 0); }
+    else { if (mode == 2) WSPLUMB_APPLY(false, 2); else if (mode) WSPLUMB_APPLY(false, 1); else WSPLUMB_APPLY(false, 0); }
 #undef WSPLUMB_APPLY
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
@@ -428,4 +444,27 @@ PLUMB_API int wsplumb_rowbn_backward_masked(const float *x, const float *dy, lon
     if (!mask) return 1;
     return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, mask, n_rois, per,
                          workspace, workspace_bytes, stream);
+}
+
+// the masked forward on position-major rows: row r belongs to RoI r % n_rois (M = n_rois * per)
+PLUMB_API int wsplumb_rowbn_forward_masked_pm(const float *x, long long M, int C, const float *weight,
+                                              const float *bias, float eps, int relu, const float *mask,
+                                              int n_rois, int per, float *y, float *mean, float *var,
+                                              float *rstd, float *scale, float *shift, float *count,
+                                              void *workspace, size_t workspace_bytes, void *stream) {
+    if (!mask || !count) return 1;
+    return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, mask, n_rois, per, count,
+                        workspace, workspace_bytes, stream, true);
+}
+
+// gradients of wsplumb_rowbn_forward_masked_pm
+PLUMB_API int wsplumb_rowbn_backward_masked_pm(const float *x, const float *dy, long long M, int C,
+                                               const float *weight, const float *mean, const float *rstd,
+                                               const float *scale, const float *shift, int relu,
+                                               const float *mask, int n_rois, int per, float *dx,
+                                               float *dweight, float *dbias, float *coef, void *workspace,
+                                               size_t workspace_bytes, void *stream) {
+    if (!mask) return 1;
+    return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, mask, n_rois, per,
+                         workspace, workspace_bytes, stream, true);
 }

@@ -44,6 +44,19 @@ def lib():
         L.wsplumb_rowbn_backward_masked.restype = _i
         L.wsplumb_rowbn_backward_masked.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
                                                     _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        for name in ("wsplumb_rowbn_forward_masked_pm", "wsplumb_rowbn_backward_masked_pm"):
+            base = getattr(L, name[:-3])
+            getattr(L, name).restype, getattr(L, name).argtypes = base.restype, base.argtypes
+        L.wsplumb_tap_table_ints.restype = _i
+        L.wsplumb_tap_table_ints.argtypes = []
+        for name in ("wsplumb_tap_gather", "wsplumb_tap_col2im"):
+            f = getattr(L, name)
+            f.restype = _i
+            f.argtypes = [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp]
+        for name in ("wsplumb_tap_weight_gather", "wsplumb_tap_weight_scatter"):
+            f = getattr(L, name)
+            f.restype = _i
+            f.argtypes = [_vp, _i, _i, _vp, _vp, _vp, _vp]
         for name in ("wsplumb_im2col3x3", "wsplumb_col2im3x3"):
             f = getattr(L, name)
             f.restype = _i
@@ -75,9 +88,10 @@ def _workspace(L, M, C, dev):
     return torch.empty((n,), dtype=torch.uint8, device=dev), n
 
 
-def rowbn_forward(x, weight, bias, eps, relu, mask=None):
-    """mask: [n_rois] f32 on x's device (0 = dead RoI), x = [n_rois * per, C]; returns (y, stats, count)
-    where count is None without a mask, else a [1] tensor holding the number of live rows."""
+def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False):
+    """mask: [n_rois] f32 on x's device (0 = dead RoI), x = [n_rois * per, C] with row r belonging to RoI
+    r // per, or r % n_rois when pos_major; returns (y, stats, count) where count is None without a mask,
+    else a [1] tensor holding the number of live rows."""
     L = lib()
     M, C = x.shape
     dev = x.device
@@ -94,9 +108,10 @@ def rowbn_forward(x, weight, bias, eps, relu, mask=None):
             n_rois = mask.shape[0]
             assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
             count = torch.empty((1,), dtype=torch.float32, device=dev)
-            rc = L.wsplumb_rowbn_forward_masked(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _p(mask),
-                                                n_rois, M // n_rois, _p(y), _p(stats[0]), _p(stats[1]), _p(stats[2]),
-                                                _p(stats[3]), _p(stats[4]), _p(count), _p(ws), n, _stream())
+            fn = L.wsplumb_rowbn_forward_masked_pm if pos_major else L.wsplumb_rowbn_forward_masked
+            rc = fn(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _p(mask), n_rois, M // n_rois, _p(y),
+                    _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _p(count), _p(ws), n,
+                    _stream())
     if rc:
         raise RuntimeError("wsplumb_rowbn_forward failed (%d)" % rc)
     return y, stats, count
@@ -113,7 +128,7 @@ def rowbn_apply(x, scale, shift, relu):
     return y
 
 
-def rowbn_backward(x, dy, weight, stats, relu, mask=None):
+def rowbn_backward(x, dy, weight, stats, relu, mask=None, pos_major=False):
     L = lib()
     M, C = x.shape
     dev = x.device
@@ -128,10 +143,9 @@ def rowbn_backward(x, dy, weight, stats, relu, mask=None):
                                           _p(dwb[1]), _p(coef), _p(ws), n, _stream())
         else:
             n_rois = mask.shape[0]
-            rc = L.wsplumb_rowbn_backward_masked(_p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]),
-                                                 _p(stats[3]), _p(stats[4]), int(relu), _p(mask), n_rois,
-                                                 M // n_rois, _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n,
-                                                 _stream())
+            fn = L.wsplumb_rowbn_backward_masked_pm if pos_major else L.wsplumb_rowbn_backward_masked
+            rc = fn(_p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]), _p(stats[3]), _p(stats[4]), int(relu),
+                    _p(mask), n_rois, M // n_rois, _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream())
     if rc:
         raise RuntimeError("wsplumb_rowbn_backward failed (%d)" % rc)
     return dx, dwb[0], dwb[1]
@@ -171,3 +185,242 @@ class Im2Col3x3Fn(torch.autograd.Function):
         if rc:
             raise RuntimeError("wsplumb_col2im3x3 failed (%d)" % rc)
         return dx, None, None, None, None, None
+
+
+# ---- 3x3 convolutions without their padding taps (csrc/plumbing/taps.hip) ----
+# Class table layout: keep in sync with the TAB_* / C_* constants of taps.hip.
+_TAB_CLS, _CLS_STRIDE, _MAX_CLS, _MAX_POS = 16, 24, 9, 64
+_TAB_SLOTPOS = _TAB_CLS + _CLS_STRIDE * _MAX_CLS
+_TAB_POSSLOT, _TAB_SLOTCLS = _TAB_SLOTPOS + _MAX_POS, _TAB_SLOTPOS + 2 * _MAX_POS
+_TAB_INTS = _TAB_SLOTCLS + _MAX_POS
+
+# one GEMM call per group of equal-shape classes (batched) or one per class (measurement switch)
+TAP_GEMM_GROUPED = True
+# Fewer RoIs than this keep the dense route: the class-packed route issues ~3x the launches of the dense one
+# (gather, weight gather, 3 GEMMs per pass instead of 1), which at a few hundred RoIs cost more than the skipped
+# FLOPs save (resnet18_sup_b2, R = 256: 15-25 % slower per step; profiles/README.md).
+TAPS_MIN_ROIS = 2048
+
+
+class TapPlan:
+    """Position classes of a 3x3 TF-'SAME' convolution of an h x w map at stride s.
+
+    Along each axis an output position's valid taps are those whose input lies inside the map; positions
+    with the same valid taps form an axis class, and a 2-D class is a (row class, column class) pair.  A
+    class is one GEMM with K = (its taps) * C.  Classes are ordered by (taps, positions) descending
+    (centre | edges | corners for a 4x4 output), and the output positions get SLOTS in that order:
+    position-major rows are slot * R + roi.  Classes of equal shape are adjacent and form one `group`.
+    """
+
+    def __init__(self, h, w, s):
+        from .backbones import _same_pad
+        self.h, self.w, self.s = h, w, s
+        self.pt, self.pl = _same_pad(h, 3, s)[0], _same_pad(w, 3, s)[0]
+        self.oh, self.ow = -(-h // s), -(-w // s)
+
+        def axis(n_in, n_out, pad):
+            cls = {}
+            for o in range(n_out):
+                taps = tuple(k for k in range(3) if 0 <= o * s + k - pad < n_in)
+                cls.setdefault(taps, []).append(o)
+            return list(cls.items())
+
+        classes = []
+        for ty, ys in axis(h, self.oh, self.pt):
+            for tx, xs in axis(w, self.ow, self.pl):
+                classes.append(([ky * 3 + kx for ky in ty for kx in tx], [(y, x) for y in ys for x in xs]))
+        classes.sort(key=lambda c: (-len(c[0]), -len(c[1])))        # stable: raster order within a shape
+        self.classes = classes
+        self.slots = [p for _, pos in classes for p in pos]
+        self.groups, k = [], 0                      # (first class, n classes, npos, ntaps)
+        while k < len(classes):
+            j = k
+            while j < len(classes) and (len(classes[j][0]), len(classes[j][1])) == \
+                    (len(classes[k][0]), len(classes[k][1])):
+                j += 1
+            self.groups.append((k, j - k, len(classes[k][1]), len(classes[k][0])))
+            k = j
+        self.cum, self.wcum, self.slot_base = [], [], []
+        u = wu = sb = 0
+        for taps, pos in classes:
+            self.cum.append(u)
+            self.wcum.append(wu)
+            self.slot_base.append(sb)
+            u, wu, sb = u + len(taps) * len(pos), wu + len(taps), sb + len(pos)
+        self.units, self.wunits = u, wu
+        self.ok = (len(classes) <= _MAX_CLS and self.oh * self.ow <= _MAX_POS and h * w <= _MAX_POS
+                   and self.units < 9 * self.oh * self.ow)          # nothing to skip: the dense route
+        self.table = self._table()
+        self.hnum = self.table.ctypes.data_as(ctypes.c_void_p)     # host copy: the entry points' shape checks
+        self._dev = {}
+
+    def _table(self):
+        import numpy as np
+        T = np.full(_TAB_INTS, -1, np.int32)
+        T[:10] = [len(self.classes), self.h, self.w, self.oh, self.ow, self.s, self.pt, self.pl, self.units,
+                  self.wunits]
+        for k, (taps, pos) in enumerate(self.classes[:_MAX_CLS]):
+            b = _TAB_CLS + _CLS_STRIDE * k
+            T[b:b + 5] = [len(pos), len(taps), self.slot_base[k], self.cum[k], self.wcum[k]]
+            T[b + 6:b + 6 + len(taps)] = taps
+            for i, t in enumerate(taps):
+                T[b + 15 + t] = i
+        for sl, (y, x) in enumerate(self.slots[:_MAX_POS]):
+            T[_TAB_SLOTPOS + sl] = y * self.ow + x
+            T[_TAB_POSSLOT + y * self.ow + x] = sl
+            T[_TAB_SLOTCLS + sl] = next(k for k in range(len(self.classes))
+                                        if self.slot_base[k] <= sl < self.slot_base[k] + len(self.classes[k][1]))
+        return T
+
+    def device_table(self, dev):
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = torch.from_numpy(self.table).to(dev)
+        return t
+
+    def subsample_index(self, w_in, s, dev):
+        """Flat input positions (y*s)*w_in + x*s of the slots: a 1x1 stride-s convolution in slot order."""
+        key = ("sub", w_in, s, dev)
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.tensor([y * s * w_in + x * s for y, x in self.slots],
+                                              dtype=torch.long, device=dev)
+        return t
+
+
+_PLANS = {}
+
+
+def tap_plan(h, w, s):
+    p = _PLANS.get((h, w, s))
+    if p is None:
+        p = _PLANS[(h, w, s)] = TapPlan(h, w, s)
+    return p
+
+
+def taps_usable(x):
+    """True when the head may run its 3x3 convolutions on the class-packed route (x: [R, h, w, C])."""
+    if os.environ.get("WSSDL_HEAD_DENSE_3X3"):            # A/B switch: the dense patch route
+        return False
+    return im2col_usable(x) and x.shape[0] >= TAPS_MIN_ROIS
+
+
+def _tap_call(name, *args):
+    rc = getattr(lib(), name)(*args, _stream())
+    if rc:
+        raise RuntimeError("%s failed (%d)" % (name, rc))
+
+
+def tap_gather(x, plan, in_pm, R):
+    """class-packed patches (plan.units * R * C floats) of x: roi-major [R, h, w, C] or position-major."""
+    C = x.shape[-1]
+    cols = torch.empty((plan.units * R * C,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _tap_call("wsplumb_tap_gather", _p(x), R, C, _p(plan.device_table(x.device)), plan.hnum, int(in_pm), _p(cols))
+    return cols
+
+
+def tap_col2im(dcols, plan, in_pm, R, C):
+    """adjoint of tap_gather: dx roi-major [R, h, w, C], or position-major [h*w*R, C] with in_pm."""
+    shape = (plan.h * plan.w * R, C) if in_pm else (R, plan.h, plan.w, C)
+    dx = torch.empty(shape, dtype=torch.float32, device=dcols.device)
+    with torch.cuda.device(dcols.device):
+        _tap_call("wsplumb_tap_col2im", _p(dcols), R, C, _p(plan.device_table(dcols.device)), plan.hnum, int(in_pm),
+                  _p(dx))
+    return dx
+
+
+def tap_weight_gather(weight, plan):
+    """[c_o, 9*C] -> class-packed (plan.wunits * c_o * C floats): class k is [c_o, ntaps_k * C]."""
+    CO, C = weight.shape[0], weight.shape[1] // 9
+    wp = torch.empty((plan.wunits * CO * C,), dtype=torch.float32, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _tap_call("wsplumb_tap_weight_gather", _p(weight), CO, C, _p(plan.device_table(weight.device)), plan.hnum,
+                  _p(wp))
+    return wp
+
+
+def tap_weight_scatter(dwp, plan, CO, C):
+    """adjoint of tap_weight_gather: [c_o, 9*C], each column the class contributions summed in class order."""
+    dw = torch.empty((CO, 9 * C), dtype=torch.float32, device=dwp.device)
+    with torch.cuda.device(dwp.device):
+        _tap_call("wsplumb_tap_weight_scatter", _p(dwp), CO, C, _p(plan.device_table(dwp.device)), plan.hnum, _p(dw))
+    return dw
+
+
+def _gemm_groups(plan, fn):
+    for k0, n, npos, ntaps in plan.groups:
+        if TAP_GEMM_GROUPED or n == 1:
+            fn(k0, n, npos, ntaps, slice(0, n))
+        else:
+            for j in range(n):
+                fn(k0, n, npos, ntaps, slice(j, j + 1))
+
+
+class TapConv3x3Fn(torch.autograd.Function):
+    """3x3 TF-'SAME' convolution over the valid taps only (TapPlan): x is roi-major [R, h, w, C] or, with
+    in_pm, position-major [h*w*R, C] in the plan's slot order; weight [c_o, 9*C] (kh, kw, c); returns the
+    position-major [oh*ow*R, c_o] output.  One GEMM per class group (torch's hipBLASLt); patches, weights
+    and their gradients move between the dense and the class-packed layouts in taps.hip."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, plan, in_pm, R):
+        C, CO = weight.shape[1] // 9, weight.shape[0]
+        x = x.contiguous()
+        assert x.shape[-1] == C and x.numel() == plan.h * plan.w * R * C and (not in_pm or plan.h == plan.oh)
+        cols = tap_gather(x, plan, in_pm, R)
+        wp = tap_weight_gather(weight.contiguous(), plan)
+        out = torch.empty((plan.oh * plan.ow * R, CO), dtype=torch.float32, device=x.device)
+
+        def gemm(k0, n, npos, ntaps, j):
+            a = cols[plan.cum[k0] * R * C:(plan.cum[k0] + n * npos * ntaps) * R * C].view(n, npos * R, ntaps * C)
+            b = wp[plan.wcum[k0] * CO * C:(plan.wcum[k0] + n * ntaps) * CO * C].view(n, CO, ntaps * C)
+            o = out[plan.slot_base[k0] * R:(plan.slot_base[k0] + n * npos) * R].view(n, npos * R, CO)
+            if j.stop - j.start == 1:
+                torch.mm(a[j.start], b[j.start].t(), out=o[j.start])
+            else:
+                torch.bmm(a, b.transpose(1, 2), out=o)
+
+        _gemm_groups(plan, gemm)
+        if bias is not None:
+            out.add_(bias)
+        ctx.save_for_backward(cols, wp)
+        ctx.geom = (plan, bool(in_pm), R, C, CO, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        cols, wp = ctx.saved_tensors
+        plan, in_pm, R, C, CO, has_bias = ctx.geom
+        dy = dy.contiguous()
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dcols = torch.empty_like(cols) if need_x else None
+        dwp = torch.empty_like(wp) if need_w else None
+
+        def gemm(k0, n, npos, ntaps, j):
+            g = dy[plan.slot_base[k0] * R:(plan.slot_base[k0] + n * npos) * R].view(n, npos * R, CO)
+            cs = slice(plan.cum[k0] * R * C, (plan.cum[k0] + n * npos * ntaps) * R * C)
+            ws = slice(plan.wcum[k0] * CO * C, (plan.wcum[k0] + n * ntaps) * CO * C)
+            one = j.stop - j.start == 1
+            if need_x:
+                b = wp[ws].view(n, CO, ntaps * C)
+                o = dcols[cs].view(n, npos * R, ntaps * C)
+                if one:
+                    torch.mm(g[j.start], b[j.start], out=o[j.start])
+                else:
+                    torch.bmm(g, b, out=o)
+            if need_w:
+                a = cols[cs].view(n, npos * R, ntaps * C)
+                o = dwp[ws].view(n, CO, ntaps * C)
+                if one:
+                    torch.mm(g[j.start].t(), a[j.start], out=o[j.start])
+                else:
+                    torch.bmm(g.transpose(1, 2), a, out=o)
+
+        _gemm_groups(plan, gemm)
+        dx = tap_col2im(dcols, plan, in_pm, R, C) if need_x else None
+        dw = tap_weight_scatter(dwp, plan, CO, C) if need_w else None
+        db = None
+        if has_bias and ctx.needs_input_grad[2]:
+            db = dy.sum(0)
+        return dx, dw, db, None, None, None

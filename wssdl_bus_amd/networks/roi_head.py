@@ -58,9 +58,9 @@ class _FusedRowBatchNormFn(torch.autograd.Function):
     with separate elementwise ops; the ReLU mask is recomputed from x in the backward."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, relu, roi_mask=None):
-        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask)
-        ctx.masked = roi_mask is not None
+    def forward(ctx, x, weight, bias, eps, relu, roi_mask=None, pos_major=False):
+        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask, pos_major)
+        ctx.masked, ctx.pos_major = roi_mask is not None, pos_major
         if ctx.masked:
             ctx.save_for_backward(x, weight, stats, roi_mask)
         else:
@@ -77,8 +77,8 @@ class _FusedRowBatchNormFn(torch.autograd.Function):
             x, weight, stats, roi_mask = ctx.saved_tensors
         else:
             (x, weight, stats), roi_mask = ctx.saved_tensors, None
-        dx, dw, db = _plumbing.rowbn_backward(x, dy.contiguous(), weight, stats, ctx.relu, roi_mask)
-        return dx, dw, db, None, None, None
+        dx, dw, db = _plumbing.rowbn_backward(x, dy.contiguous(), weight, stats, ctx.relu, roi_mask, ctx.pos_major)
+        return dx, dw, db, None, None, None, None
 
 
 # The head can see RoI rows that are not live: the padding rows of the fixed-shape blob
@@ -97,10 +97,10 @@ def set_roi_mask(mask):
     _ROI_MASK = mask
 
 
-def _masked_row_batch_norm(x, weight, bias, eps, relu, roi_mask):
+def _masked_row_batch_norm(x, weight, bias, eps, relu, roi_mask, pos_major=False):
     M = x.shape[0]
     per = M // roi_mask.shape[0]
-    m = roi_mask.repeat_interleave(per).unsqueeze(1)
+    m = (roi_mask.repeat(per) if pos_major else roi_mask.repeat_interleave(per)).unsqueeze(1)
     n = (roi_mask.sum() * per).clamp_min(1.0)
     mean = (x * m).sum(0) / n
     d = (x - mean) * m
@@ -113,7 +113,9 @@ def _masked_row_batch_norm(x, weight, bias, eps, relu, roi_mask):
 
 class RowBatchNorm(nn.Module):
     """BatchNorm over rows ([M, C] input) with the usual running statistics; `relu=True`
-    applies the ReLU that follows it in the network inside the same kernels."""
+    applies the ReLU that follows it in the network inside the same kernels.  Rows are roi-major
+    (row r belongs to RoI r // (M / R)) or, with `pos_major=True`, position-major (RoI r % R): only
+    the live-row mask cares."""
 
     def __init__(self, num_features, eps=1e-3, momentum=0.01):
         super().__init__()
@@ -123,7 +125,7 @@ class RowBatchNorm(nn.Module):
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features))
 
-    def forward(self, x, relu=False):
+    def forward(self, x, relu=False, pos_major=False):
         fused = _plumbing.usable(x)
         if not self.training:
             scale = self.weight * torch.rsqrt(self.running_var + self.eps)
@@ -134,10 +136,12 @@ class RowBatchNorm(nn.Module):
             return F.relu(y) if relu else y
         if _ROI_MASK is not None:
             if fused and x.shape[0] % _ROI_MASK.shape[0] == 0:
-                y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), _ROI_MASK)
+                y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), _ROI_MASK,
+                                                             bool(pos_major))
                 n = n[0]
             else:
-                y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, _ROI_MASK)
+                y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, _ROI_MASK,
+                                                         pos_major)
             with torch.no_grad():
                 self.running_mean.lerp_(mean, self.momentum)
                 self.running_var.lerp_(var * (n / (n - 1).clamp_min(1.0)), self.momentum)
@@ -187,12 +191,32 @@ class ConvNHWC(nn.Module):
             p = xp.unfold(1, k, s).unfold(2, k, s)            # [R, oh, ow, C, kh, kw]
             oh, ow = p.shape[1], p.shape[2]
             rows = p.permute(0, 1, 2, 4, 5, 3).reshape(-1, k * k * c)
-        y = F.linear(rows, self.weight, self.bias)
+        return self._act(F.linear(rows, self.weight, self.bias)).view(r, oh, ow, self.c_o)
+
+    def _act(self, y, pos_major=False):
         if self.bn is not None:
-            y = self.bn(y, relu=self.relu)
-        elif self.relu:
-            y = F.relu(y)
-        return y.view(r, oh, ow, self.c_o)
+            return self.bn(y, relu=self.relu, pos_major=pos_major)
+        return F.relu(y) if self.relu else y
+
+    # ---- position-major route of the head's 4x4 section (ResNetHeadNHWC.forward) ----
+    def forward_pm(self, x, plan, R):
+        """x: roi-major [R, h, w, C] or position-major [rows, C] rows in `plan`'s slot order; returns
+        position-major rows.  3x3: the class-packed GEMMs of `plan` (TapConv3x3Fn); 1x1 at stride s on a
+        roi-major input: the input positions of the slots, then a row GEMM; 1x1 on rows: a row GEMM."""
+        if self.k == 3:
+            y = _plumbing.TapConv3x3Fn.apply(x, self.weight, self.bias, plan, x.dim() == 2, R)
+        else:
+            if x.dim() == 4:
+                x = _pm_rows(x, plan, self.s)
+            y = F.linear(x, self.weight, self.bias)
+        return self._act(y, pos_major=True)
+
+
+def _pm_rows(x, plan, s):
+    """roi-major [R, h, w, C] -> position-major [slots * R, C]: the inputs x[:, y*s, x*s] of the slots."""
+    r, h, w, c = x.shape
+    idx = plan.subsample_index(w, s, x.device)
+    return x.view(r, h * w, c).transpose(0, 1).index_select(0, idx).reshape(-1, c)
 
 
 def _bn_rows(bn, x, relu=False):
@@ -222,6 +246,27 @@ class BottleneckNHWC(nn.Module):
         x = self.conv3(self.conv2(self.conv1(x)))
         return x + (self.short(ori) if self.short is not None else ori)
 
+    def forward_pm(self, x, plans, R):
+        """forward on the position-major route: x roi-major [R, 7, 7, C] (first block) or position-major rows;
+        plans: {stride: TapPlan}; returns position-major rows."""
+        pm = x.dim() == 2
+        ori = x
+        if self.preact != "no_preact":
+            y = _pre_act(self.pre_bn, x, pm)
+            if self.preact == "both_preact":
+                ori = y
+            x = y
+        s = self.conv2.s
+        plan = plans[s]
+        if not pm:
+            x = self.conv1(x)                                   # 1x1 on the roi-major 7x7 map
+        else:
+            x = self.conv1.forward_pm(x, plan, R)
+        x = self.conv3.forward_pm(self.conv2.forward_pm(x, plan, R), plan, R)
+        if self.short is not None:
+            return x + self.short.forward_pm(ori, plan, R)
+        return x + (ori if pm else _pm_rows(ori, plan, s))
+
 
 class BasicBlockNHWC(nn.Module):
     expansion = 1
@@ -244,6 +289,28 @@ class BasicBlockNHWC(nn.Module):
         x = self.conv2(self.conv1(x))
         return x + (self.short(ori) if self.short is not None else ori)
 
+    def forward_pm(self, x, plans, R):
+        """BottleneckNHWC.forward_pm for the basic block."""
+        pm = x.dim() == 2
+        ori = x
+        if self.preact != "no_preact":
+            y = _pre_act(self.pre_bn, x, pm)
+            if self.preact == "both_preact":
+                ori = y
+            x = y
+        s = self.conv1.s
+        plan = plans[s]
+        x = self.conv2.forward_pm(self.conv1.forward_pm(x, plan, R), plans[1], R)
+        if self.short is not None:
+            return x + self.short.forward_pm(ori, plan, R)
+        return x + (ori if pm else _pm_rows(ori, plan, s))
+
+
+def _pre_act(bn, x, pm):
+    if not pm:
+        return _bn_rows(bn, x, relu=True) if bn is not None else F.relu(x)
+    return bn(x, relu=True, pos_major=True) if bn is not None else F.relu(x)
+
 
 class ResNetHeadNHWC(nn.Module):
     """[R,7,7,C] NHWC -> [R, 512*expansion]."""
@@ -261,6 +328,33 @@ class ResNetHeadNHWC(nn.Module):
         self.out_features = 512 * e
 
     def forward(self, x):
+        plans = self._tap_plans(x)
+        if plans is not None:
+            return self._forward_pm(x, plans)
         x = self.group3(x)
         x = _bn_rows(self.norm, x, relu=True) if self.norm is not None else F.relu(x)
         return x.mean(dim=(1, 2))
+
+    @staticmethod
+    def _tap_plans(x):
+        """The class plans of the two 3x3 shapes (h x w at stride 2, then its output at stride 1), or None
+        for the dense route: CPU tensors, no plumbing library, WSSDL_HEAD_DENSE_3X3=1, fewer RoIs than
+        _plumbing.TAPS_MIN_ROIS, or a geometry with no padding taps to skip or different slot orders for the
+        two shapes."""
+        if not _plumbing.taps_usable(x):
+            return None
+        p2 = _plumbing.tap_plan(x.shape[1], x.shape[2], 2)
+        p1 = _plumbing.tap_plan(p2.oh, p2.ow, 1)
+        if not (p2.ok and p1.ok and p1.slots == p2.slots):
+            return None
+        return {2: p2, 1: p1}
+
+    def _forward_pm(self, x, plans):
+        """The 4x4 section in POSITION-MAJOR rows (row = slot * R + roi, slots ordered centre | edges |
+        corners by _plumbing.TapPlan): each 3x3 class GEMM writes its own contiguous slab; batch norm,
+        1x1 convolutions and residual adds do not care about row order, the final mean reduces over slots."""
+        R = x.shape[0]
+        for blk in self.group3:
+            x = blk.forward_pm(x, plans, R)
+        x = self.norm(x, relu=True, pos_major=True) if self.norm is not None else F.relu(x)
+        return x.view(-1, R, x.shape[1]).mean(dim=0)
