@@ -37,8 +37,62 @@ __device__ __forceinline__ unsigned mask_roi(long long r, int div) {
     return MASK == 2 ? (unsigned)r % (unsigned)div : (unsigned)r / (unsigned)div;
 }
 
-// Partial column sums of one row slab.  Thread t owns float4 column (t % L) + cc * L and the
-// rows r0 + t / L + k * RS; L = min(C/4, 256), RS = 256 / L.
+// ---- arithmetic shared by every kernel of this file (the join kernels below must round as these do) ----
+// The fused multiply-adds are written out: left to the compiler's contraction, the same expression came out
+// fused in one kernel and as separate multiplies and subtractions in another (even lane by lane within one
+// kernel), and a join must round exactly as the layers it replaces.
+// y = x*scale + shift
+__device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return __builtin_fmaf(x, sc, sh); }
+// dx = a*u - k0 - k1*x (coefficients of rowbn_bwd_finish_kernel)
+__device__ __forceinline__ float bn_dx(float ka, float u, float k0, float k1, float x) {
+    return __builtin_fmaf(-k1, x, __builtin_fmaf(ka, u, -k0));
+}
+// the f64 column sums of a thread: two rows per step, then a one-row tail
+__device__ __forceinline__ void acc_rows2(double &s, double &q, float v0, float w0, float v1, float w1) {
+    s += (double)v0 + (double)v1;
+    q += (double)v0 * (double)w0 + (double)v1 * (double)w1;
+}
+__device__ __forceinline__ void acc_row(double &s, double &q, float v, float w) {
+    s += (double)v;
+    q += (double)v * (double)w;
+}
+
+// Thread t of a slab kernel owns float4 column (t % L) + cc * L and the rows r0 + t / L + k * RS;
+// L = min(C/4, 256), RS = 256 / L.
+struct Slab {
+    int C4, L, RS, lc, lr;
+    long long r0, r1;
+    __device__ __forceinline__ Slab(long long M, int C, long long rows_per_block) {
+        C4 = C >> 2;
+        L = C4 < BLOCK ? C4 : BLOCK;
+        RS = BLOCK / L;
+        lc = threadIdx.x % L;
+        lr = threadIdx.x / L;
+        r0 = (long long)blockIdx.x * rows_per_block;
+        r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
+    }
+};
+
+// fixed-order reduction over the RS row phases of float4 column c4: out[0..C) = s, out[C..2C) = q
+__device__ __forceinline__ void slab_reduce(const Slab &b, int C, int c4, const double (&s)[4], const double (&q)[4],
+                                            double (*red)[8], double *__restrict__ out) {
+    const int t = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { red[t][j] = s[j]; red[t][4 + j] = q[j]; }
+    __syncthreads();
+    if (b.lr == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double ss = 0.0, qq = 0.0;
+            for (int k = 0; k < b.RS; ++k) { ss += red[k * b.L + b.lc][j]; qq += red[k * b.L + b.lc][4 + j]; }
+            out[c4 * 4 + j] = ss;
+            out[C + c4 * 4 + j] = qq;
+        }
+    }
+}
+
+// Partial column sums of one row slab (thread mapping: Slab).
 // MODE 0: s = sum x,  q = sum x*x
 // MODE 1: s = sum g,  q = sum g*x   with g = dy, masked by (x*scale + shift > 0) when RELU
 template <int MODE, bool RELU, int MASK>
@@ -47,13 +101,9 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
     const float *__restrict__ shift, long long M, int C, long long rows_per_block,
     double *__restrict__ partial, const float *__restrict__ mask, int per) {
     __shared__ double red[BLOCK][8];
-    const int C4 = C >> 2;
-    const int L = C4 < BLOCK ? C4 : BLOCK;
-    const int RS = BLOCK / L;
-    const int t = threadIdx.x;
-    const int lc = t % L, lr = t / L;
-    const long long r0 = (long long)blockIdx.x * rows_per_block;
-    const long long r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
+    const Slab b(M, C, rows_per_block);
+    const int C4 = b.C4, L = b.L, RS = b.RS, lc = b.lc, lr = b.lr;
+    const long long r0 = b.r0, r1 = b.r1;
     double *out = partial + (size_t)blockIdx.x * 2 * C;
     for (int cc = 0; cc * L < C4; ++cc) {
         const int c4 = cc * L + lc;
@@ -84,20 +134,18 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (MODE == 0) {
-                        s[j] += (double)a0[j] + (double)a1[j];
-                        q[j] += (double)a0[j] * (double)a0[j] + (double)a1[j] * (double)a1[j];
+                        acc_rows2(s[j], q[j], a0[j], a0[j], a1[j], a1[j]);
                     } else {
                         float u0 = g0[j], u1 = g1[j];
                         if (RELU) {
-                            if (!(a0[j] * sc[j] + sh[j] > 0.0f)) u0 = 0.0f;
-                            if (!(a1[j] * sc[j] + sh[j] > 0.0f)) u1 = 0.0f;
+                            if (!(bn_affine(a0[j], sc[j], sh[j]) > 0.0f)) u0 = 0.0f;
+                            if (!(bn_affine(a1[j], sc[j], sh[j]) > 0.0f)) u1 = 0.0f;
                         }
                         if (MASK) {                 // a dead row adds nothing (x = 0 would still pass the ReLU test)
                             if (!live0) u0 = 0.0f;
                             if (!live1) u1 = 0.0f;
                         }
-                        s[j] += (double)u0 + (double)u1;
-                        q[j] += (double)u0 * (double)a0[j] + (double)u1 * (double)a1[j];
+                        acc_rows2(s[j], q[j], u0, a0[j], u1, a1[j]);
                     }
                 }
             }
@@ -109,31 +157,16 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (MODE == 0) {
-                        s[j] += (double)a0[j];
-                        q[j] += (double)a0[j] * (double)a0[j];
+                        acc_row(s[j], q[j], a0[j], a0[j]);
                     } else {
                         float u0 = g0[j];
-                        if (RELU && !(a0[j] * sc[j] + sh[j] > 0.0f)) u0 = 0.0f;
-                        s[j] += (double)u0;
-                        q[j] += (double)u0 * (double)a0[j];
+                        if (RELU && !(bn_affine(a0[j], sc[j], sh[j]) > 0.0f)) u0 = 0.0f;
+                        acc_row(s[j], q[j], u0, a0[j]);
                     }
                 }
             }
         }
-        // fixed-order reduction over the RS row phases of a column
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { red[t][j] = s[j]; red[t][4 + j] = q[j]; }
-        __syncthreads();
-        if (lr == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                double ss = 0.0, qq = 0.0;
-                for (int k = 0; k < RS; ++k) { ss += red[k * L + lc][j]; qq += red[k * L + lc][4 + j]; }
-                out[c4 * 4 + j] = ss;
-                out[C + c4 * 4 + j] = qq;
-            }
-        }
+        slab_reduce(b, C, c4, s, q, red, out);
     }
 }
 
@@ -249,7 +282,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_fwd_kernel(
         float4v o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float v = a[j] * sc[j] + sh[j];
+            float v = bn_affine(a[j], sc[j], sh[j]);
             if (RELU) v = v > 0.0f ? v : 0.0f;
             o[j] = v;
         }
@@ -285,10 +318,196 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float u = g[j];
-            if (RELU && !(a[j] * sc[j] + sh[j] > 0.0f)) u = 0.0f;
-            o[j] = ka[j] * u - k0[j] - k1[j] * a[j];
+            if (RELU && !(bn_affine(a[j], sc[j], sh[j]) > 0.0f)) u = 0.0f;
+            o[j] = bn_dx(ka[j], u, k0[j], k1[j], a[j]);
         }
         reinterpret_cast<float4v *>(dx)[i] = o;
+    }
+}
+
+// ---- residual joins of the head's position-major section (networks/roi_head.py, _JoinFn) ----
+// A join is the end of a block: out = bn3(x3) + other, where other is the identity shortcut (a plain
+// tensor) or, with DUAL, the projection shortcut's own batch norm of xs; the next block's pre-activation
+// norm (or the head's final norm) then takes its statistics over out.  Both join kernels walk row slabs
+// exactly as rowbn_partial_kernel does (Slab, acc_rows2 / acc_row, slab_reduce), so the f64 partials
+// they leave are those that kernel would compute from the tensor they write.
+// MASK is 0 or 2 (the joins are position-major).
+
+template <int MASK>
+__device__ __forceinline__ bool row_live(const float *__restrict__ mask, long long r, int div) {
+    return MASK ? mask[mask_roi<MASK>(r, div)] != 0.0f : true;
+}
+
+__device__ __forceinline__ float4v load4(const float *__restrict__ p, long long r, int C, int c4, bool on) {
+    const float4v zero4 = {0, 0, 0, 0};
+    return on ? reinterpret_cast<const float4v *>(p + (size_t)r * C)[c4] : zero4;
+}
+
+// Forward join: writes out = act_mask(x3*sc3 + sh3) + (DUAL ? act_mask(other*sco + sho) : other), act_mask
+// being zero on dead rows, and the partials (sum, sum of squares over the live rows) of out.
+template <bool DUAL, int MASK>
+__global__ __launch_bounds__(BLOCK) void rowbn_join_fwd_kernel(
+    const float *__restrict__ x3, const float *__restrict__ sc3, const float *__restrict__ sh3,
+    const float *__restrict__ other, const float *__restrict__ sco, const float *__restrict__ sho, long long M,
+    int C, long long rows_per_block, float *__restrict__ out, double *__restrict__ partial,
+    const float *__restrict__ mask, int div) {
+    __shared__ double red[BLOCK][8];
+    const Slab b(M, C, rows_per_block);
+    double *pout = partial + (size_t)blockIdx.x * 2 * C;
+    for (int cc = 0; cc * b.L < b.C4; ++cc) {
+        const int c4 = cc * b.L + b.lc;
+        double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+        const float4v k3 = reinterpret_cast<const float4v *>(sc3)[c4], h3 = reinterpret_cast<const float4v *>(sh3)[c4];
+        float4v ko = {0, 0, 0, 0}, ho = {0, 0, 0, 0};
+        if (DUAL) {
+            ko = reinterpret_cast<const float4v *>(sco)[c4];
+            ho = reinterpret_cast<const float4v *>(sho)[c4];
+        }
+        // one element of out; a dead row is zero from the norm(s), plus the identity
+        auto join = [&](float a, float o, int j, bool live) {
+            const float t = live ? bn_affine(a, k3[j], h3[j]) : 0.0f;
+            const float u = DUAL ? (live ? bn_affine(o, ko[j], ho[j]) : 0.0f) : o;
+            return t + u;
+        };
+        if (b.lr < b.RS) {
+            const int RS = b.RS;
+            long long r = b.r0 + b.lr;
+#pragma unroll 1
+            for (; r + RS < b.r1; r += 2 * RS) {
+                const bool live0 = row_live<MASK>(mask, r, div), live1 = row_live<MASK>(mask, r + RS, div);
+                const float4v a0 = load4(x3, r, C, c4, live0), a1 = load4(x3, r + RS, C, c4, live1);
+                const float4v o0 = load4(other, r, C, c4, !DUAL || live0), o1 = load4(other, r + RS, C, c4, !DUAL || live1);
+                float4v y0, y1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    y0[j] = join(a0[j], o0[j], j, live0);
+                    y1[j] = join(a1[j], o1[j], j, live1);
+                    const float v0 = live0 ? y0[j] : 0.0f, v1 = live1 ? y1[j] : 0.0f;
+                    acc_rows2(s[j], q[j], v0, v0, v1, v1);
+                }
+                reinterpret_cast<float4v *>(out + (size_t)r * C)[c4] = y0;
+                reinterpret_cast<float4v *>(out + (size_t)(r + RS) * C)[c4] = y1;
+            }
+            for (; r < b.r1; r += RS) {
+                const bool live0 = row_live<MASK>(mask, r, div);
+                const float4v a0 = load4(x3, r, C, c4, live0), o0 = load4(other, r, C, c4, !DUAL || live0);
+                float4v y0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    y0[j] = join(a0[j], o0[j], j, live0);
+                    if (live0) acc_row(s[j], q[j], y0[j], y0[j]);
+                }
+                reinterpret_cast<float4v *>(out + (size_t)r * C)[c4] = y0;
+            }
+        }
+        slab_reduce(b, C, c4, s, q, red, pout);
+    }
+}
+
+// Backward join: writes g = (a*u - k0 - k1*xo) + d_res -- the dx of the norm that follows the join (its
+// coefficients in coef, u = dy masked by the recomputed ReLU of xo*scn + shn; zero on dead rows) plus, with
+// RES, the gradient arriving over the residual path -- and the partials bn3's backward takes over it:
+// partial3 = (sum g, sum g*x3) and, with DUAL, partials = (sum g, sum g*xs), live rows only.
+template <bool DUAL, bool RES, int MASK>
+__global__ __launch_bounds__(BLOCK) void rowbn_join_bwd_kernel(
+    const float *__restrict__ xo, const float *__restrict__ dy, const float *__restrict__ scn,
+    const float *__restrict__ shn, const float *__restrict__ coef, const float *__restrict__ dres,
+    const float *__restrict__ x3, const float *__restrict__ xs, long long M, int C, long long rows_per_block,
+    float *__restrict__ g, double *__restrict__ partial3, double *__restrict__ partials,
+    const float *__restrict__ mask, int div) {
+    __shared__ double red[BLOCK][8];
+    const Slab b(M, C, rows_per_block);
+    double *p3 = partial3 + (size_t)blockIdx.x * 2 * C;
+    double *ps = DUAL ? partials + (size_t)blockIdx.x * 2 * C : nullptr;
+    for (int cc = 0; cc * b.L < b.C4; ++cc) {
+        const int c4 = cc * b.L + b.lc;
+        double s[4] = {0, 0, 0, 0}, q3[4] = {0, 0, 0, 0}, qs[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+        const float4v sc = reinterpret_cast<const float4v *>(scn)[c4], sh = reinterpret_cast<const float4v *>(shn)[c4];
+        const float4v ka = reinterpret_cast<const float4v *>(coef)[c4];
+        const float4v k0 = reinterpret_cast<const float4v *>(coef + C)[c4];
+        const float4v k1 = reinterpret_cast<const float4v *>(coef + 2 * C)[c4];
+        auto grad = [&](float x, float d, float res, int j, bool live) {
+            float u = d;
+            if (!(bn_affine(x, sc[j], sh[j]) > 0.0f)) u = 0.0f;
+            const float dx = live ? bn_dx(ka[j], u, k0[j], k1[j], x) : 0.0f;
+            return RES ? dx + res : dx;
+        };
+        if (b.lr < b.RS) {
+            const int RS = b.RS;
+            long long r = b.r0 + b.lr;
+#pragma unroll 1
+            for (; r + RS < b.r1; r += 2 * RS) {
+                const bool live0 = row_live<MASK>(mask, r, div), live1 = row_live<MASK>(mask, r + RS, div);
+                const float4v x0 = load4(xo, r, C, c4, live0), x1 = load4(xo, r + RS, C, c4, live1);
+                const float4v d0 = load4(dy, r, C, c4, live0), d1 = load4(dy, r + RS, C, c4, live1);
+                const float4v e0 = load4(dres, r, C, c4, RES), e1 = load4(dres, r + RS, C, c4, RES);
+                const float4v a0 = load4(x3, r, C, c4, live0), a1 = load4(x3, r + RS, C, c4, live1);
+                const float4v b0 = load4(xs, r, C, c4, DUAL && live0), b1 = load4(xs, r + RS, C, c4, DUAL && live1);
+                float4v g0, g1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    g0[j] = grad(x0[j], d0[j], e0[j], j, live0);
+                    g1[j] = grad(x1[j], d1[j], e1[j], j, live1);
+                    const float v0 = live0 ? g0[j] : 0.0f, v1 = live1 ? g1[j] : 0.0f;
+                    acc_rows2(s[j], q3[j], v0, a0[j], v1, a1[j]);
+                    if (DUAL) acc_rows2(s2[j], qs[j], v0, b0[j], v1, b1[j]);
+                }
+                reinterpret_cast<float4v *>(g + (size_t)r * C)[c4] = g0;
+                reinterpret_cast<float4v *>(g + (size_t)(r + RS) * C)[c4] = g1;
+            }
+            for (; r < b.r1; r += RS) {
+                const bool live0 = row_live<MASK>(mask, r, div);
+                const float4v x0 = load4(xo, r, C, c4, live0), d0 = load4(dy, r, C, c4, live0);
+                const float4v e0 = load4(dres, r, C, c4, RES), a0 = load4(x3, r, C, c4, live0);
+                const float4v b0 = load4(xs, r, C, c4, DUAL && live0);
+                float4v g0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    g0[j] = grad(x0[j], d0[j], e0[j], j, live0);
+                    if (live0) {
+                        acc_row(s[j], q3[j], g0[j], a0[j]);
+                        if (DUAL) acc_row(s2[j], qs[j], g0[j], b0[j]);
+                    }
+                }
+                reinterpret_cast<float4v *>(g + (size_t)r * C)[c4] = g0;
+            }
+        }
+        slab_reduce(b, C, c4, s, q3, red, p3);
+        if (DUAL) slab_reduce(b, C, c4, s, qs, red, ps);
+    }
+}
+
+// Block 1's two backward applies in one pass over g: dx3 and dxs from their own coefficient sets (neither
+// norm has a ReLU).
+template <int MASK>
+__global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_dual_kernel(
+    const float *__restrict__ x3, const float *__restrict__ xs, const float *__restrict__ g,
+    const float *__restrict__ coef3, const float *__restrict__ coefs, long long total4, int C4,
+    float *__restrict__ dx3, float *__restrict__ dxs, const float *__restrict__ mask, int div) {
+    const int C = C4 * 4;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total4;
+         i += (long long)gridDim.x * BLOCK) {
+        const int c4 = (int)(i % C4);
+        if (MASK && mask[mask_roi<MASK>(i / C4, div)] == 0.0f) {
+            const float4v zero4 = {0, 0, 0, 0};
+            reinterpret_cast<float4v *>(dx3)[i] = zero4;
+            reinterpret_cast<float4v *>(dxs)[i] = zero4;
+            continue;
+        }
+        const float4v a = reinterpret_cast<const float4v *>(x3)[i];
+        const float4v e = reinterpret_cast<const float4v *>(xs)[i];
+        const float4v u = reinterpret_cast<const float4v *>(g)[i];
+        const float4v ka3 = reinterpret_cast<const float4v *>(coef3)[c4], kas = reinterpret_cast<const float4v *>(coefs)[c4];
+        const float4v k03 = reinterpret_cast<const float4v *>(coef3 + C)[c4], k0s = reinterpret_cast<const float4v *>(coefs + C)[c4];
+        const float4v k13 = reinterpret_cast<const float4v *>(coef3 + 2 * C)[c4], k1s = reinterpret_cast<const float4v *>(coefs + 2 * C)[c4];
+        float4v o3, os;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o3[j] = bn_dx(ka3[j], u[j], k03[j], k13[j], a[j]);
+            os[j] = bn_dx(kas[j], u[j], k0s[j], k1s[j], e[j]);
+        }
+        reinterpret_cast<float4v *>(dx3)[i] = o3;
+        reinterpret_cast<float4v *>(dxs)[i] = os;
     }
 }
 
@@ -467,4 +686,150 @@ PLUMB_API int wsplumb_rowbn_backward_masked_pm(const float *x, const float *dy, 
     if (!mask) return 1;
     return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, mask, n_rois, per,
                          workspace, workspace_bytes, stream, true);
+}
+
+// ---- residual joins (position-major rows; mask may be null: every row live) ----
+// Statistic blocks are [5, C] f32: mean, var, rstd, scale, shift (the layout of the Python binding).
+
+// bytes of scratch of one join call: two partial buffers
+PLUMB_API size_t wsplumb_rowbn_join_workspace_bytes(long long M, int C) {
+    return 2 * wsplumb_rowbn_workspace_bytes(M, C);
+}
+
+namespace {
+
+struct JoinGeom {
+    hipStream_t st;
+    int nb, mode, div;
+    long long rpb, total4;
+    double *p0, *p1;
+};
+
+// 0 when the arguments of a join entry point are usable
+inline int join_geom(long long M, int C, const float *mask, int n_rois, int per, void *workspace,
+                     size_t workspace_bytes, void *stream, JoinGeom &g) {
+    if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_join_workspace_bytes(M, C)) return 1;
+    if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
+    g.st = static_cast<hipStream_t>(stream);
+    g.nb = partial_blocks(M, C);
+    g.rpb = (M + g.nb - 1) / g.nb;
+    g.total4 = M * (C / 4);
+    g.mode = mask ? 2 : 0;
+    g.div = mask ? n_rois : 1;
+    g.p0 = static_cast<double *>(workspace);
+    g.p1 = g.p0 + (size_t)g.nb * 2 * C;
+    return 0;
+}
+
+// statistics of x (no apply): partial sums into g.p0, then the finish kernel
+inline void join_stats(const JoinGeom &g, const float *x, long long M, int C, const float *weight, const float *bias,
+                       float eps, float *stats, const float *mask, int n_rois, int per, float *count) {
+    if (g.mode)
+        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 2>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, nullptr, nullptr,
+                           nullptr, M, C, g.rpb, g.p0, mask, g.div);
+    else
+        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 0>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, nullptr, nullptr,
+                           nullptr, M, C, g.rpb, g.p0, nullptr, 1);
+    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
+                       g.st, g.p0, g.nb, C, M, weight, bias, eps, stats, stats + C, stats + 2 * C, stats + 3 * C,
+                       stats + 4 * C, mask, n_rois, per, count);
+}
+
+inline void join_bwd_finish(const JoinGeom &g, const double *partial, long long M, int C, const float *weight,
+                            const float *stats, float *dwb, float *coef, const float *mask, int n_rois, int per) {
+    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
+                       g.st, partial, g.nb, C, M, weight, stats, stats + 2 * C, dwb, dwb + C, coef, mask, n_rois, per);
+}
+
+}  // namespace
+
+// out = bn3(x3) + other, y = relu(bn_n(out)), all in training mode over the live rows:
+//   other is the identity shortcut when weight_s is null, else the input xs of the shortcut's own norm
+//   (out = bn3(x3) + bn_s(xs); stats_s is written only then);
+//   stats3 / stats_s / stats_n [5, C] and count [1] are what wsplumb_rowbn_forward_masked_pm writes for the
+//   three layers (count: once, they share the mask; untouched without a mask).
+// Dead rows: out = other (identity form) or 0, y = 0.  Bit-identical to the three (four) separate calls and
+// the add between them.
+PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, long long M, int C,
+                                         const float *weight3, const float *bias3, float eps3,
+                                         const float *weight_s, const float *bias_s, float eps_s,
+                                         const float *weight_n, const float *bias_n, float eps_n,
+                                         const float *mask, int n_rois, int per, float *out, float *y,
+                                         float *stats3, float *stats_s, float *stats_n, float *count,
+                                         void *workspace, size_t workspace_bytes, void *stream) {
+    JoinGeom g;
+    if (join_geom(M, C, mask, n_rois, per, workspace, workspace_bytes, stream, g)) return 1;
+    if (mask && !count) return 1;
+    const bool dual = weight_s != nullptr;
+    if (dual && (!bias_s || !stats_s)) return 1;
+    join_stats(g, x3, M, C, weight3, bias3, eps3, stats3, mask, n_rois, per, nullptr);
+    if (dual) join_stats(g, other, M, C, weight_s, bias_s, eps_s, stats_s, mask, n_rois, per, nullptr);
+    const float *sco = dual ? stats_s + 3 * C : nullptr, *sho = dual ? stats_s + 4 * C : nullptr;
+#define WSPLUMB_JOIN(DUAL, MASK) \
+    hipLaunchKernelGGL((rowbn_join_fwd_kernel<DUAL, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, x3, stats3 + 3 * C, \
+                       stats3 + 4 * C, other, sco, sho, M, C, g.rpb, out, g.p0, mask, g.div)
+    if (dual) { if (g.mode) WSPLUMB_JOIN(true, 2); else WSPLUMB_JOIN(true, 0); }
+    else { if (g.mode) WSPLUMB_JOIN(false, 2); else WSPLUMB_JOIN(false, 0); }
+#undef WSPLUMB_JOIN
+    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
+                       g.st, g.p0, g.nb, C, M, weight_n, bias_n, eps_n, stats_n, stats_n + C, stats_n + 2 * C,
+                       stats_n + 3 * C, stats_n + 4 * C, mask, n_rois, per, mask ? count : nullptr);
+    if (g.mode)
+        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, out,
+                           stats_n + 3 * C, stats_n + 4 * C, g.total4, C / 4, y, mask, g.div);
+    else
+        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 0>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, out,
+                           stats_n + 3 * C, stats_n + 4 * C, g.total4, C / 4, y, nullptr, 1);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+// gradients of wsplumb_rowbn_join_forward: dy is the gradient of y, dres that of out over the residual path
+// (null: none).  g = dx of bn_n + dres is the gradient of `other` in the identity form; dx3 (and dxs, when
+// xs / weight_s / stats_s are given) are bn3's (the shortcut norm's) input gradients.  dwb_* are [2, C]:
+// dweight, dbias.  coef is [9, C] scratch.
+PLUMB_API int wsplumb_rowbn_join_backward(const float *out, const float *dy, const float *dres, const float *x3,
+                                          const float *xs, long long M, int C, const float *weight_n,
+                                          const float *stats_n, const float *weight3, const float *stats3,
+                                          const float *weight_s, const float *stats_s, const float *mask,
+                                          int n_rois, int per, float *gout, float *dx3, float *dxs, float *dwb_n,
+                                          float *dwb3, float *dwb_s, float *coef, void *workspace,
+                                          size_t workspace_bytes, void *stream) {
+    JoinGeom g;
+    if (join_geom(M, C, mask, n_rois, per, workspace, workspace_bytes, stream, g)) return 1;
+    const bool dual = xs != nullptr;
+    if (dual && (!weight_s || !stats_s || !dxs || !dwb_s)) return 1;
+    float *coef_n = coef, *coef3 = coef + 3 * C, *coefs = coef + 6 * C;
+    const float *scn = stats_n + 3 * C, *shn = stats_n + 4 * C;
+    if (g.mode)
+        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 2>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn, shn, M, C,
+                           g.rpb, g.p0, mask, g.div);
+    else
+        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 0>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn, shn, M, C,
+                           g.rpb, g.p0, nullptr, 1);
+    join_bwd_finish(g, g.p0, M, C, weight_n, stats_n, dwb_n, coef_n, mask, n_rois, per);
+#define WSPLUMB_JOIN(DUAL, RES, MASK) \
+    hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, RES, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn, shn, \
+                       coef_n, dres, x3, xs, M, C, g.rpb, gout, g.p0, g.p1, mask, g.div)
+#define WSPLUMB_JOIN_M(DUAL, RES) do { if (g.mode) WSPLUMB_JOIN(DUAL, RES, 2); else WSPLUMB_JOIN(DUAL, RES, 0); } while (0)
+    if (dual) { if (dres) WSPLUMB_JOIN_M(true, true); else WSPLUMB_JOIN_M(true, false); }
+    else { if (dres) WSPLUMB_JOIN_M(false, true); else WSPLUMB_JOIN_M(false, false); }
+#undef WSPLUMB_JOIN_M
+#undef WSPLUMB_JOIN
+    join_bwd_finish(g, g.p0, M, C, weight3, stats3, dwb3, coef3, mask, n_rois, per);
+    if (dual) {
+        join_bwd_finish(g, g.p1, M, C, weight_s, stats_s, dwb_s, coefs, mask, n_rois, per);
+        if (g.mode)
+            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
+                               gout, coef3, coefs, g.total4, C / 4, dx3, dxs, mask, g.div);
+        else
+            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<0>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
+                               gout, coef3, coefs, g.total4, C / 4, dx3, dxs, nullptr, 1);
+    } else if (g.mode) {
+        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<false, 2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, gout,
+                           nullptr, nullptr, coef3, g.total4, C / 4, dx3, mask, g.div);
+    } else {
+        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<false, 0>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, gout,
+                           nullptr, nullptr, coef3, g.total4, C / 4, dx3, nullptr, 1);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : 3;
 }

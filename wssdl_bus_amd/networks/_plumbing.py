@@ -47,6 +47,13 @@ def lib():
         for name in ("wsplumb_rowbn_forward_masked_pm", "wsplumb_rowbn_backward_masked_pm"):
             base = getattr(L, name[:-3])
             getattr(L, name).restype, getattr(L, name).argtypes = base.restype, base.argtypes
+        L.wsplumb_rowbn_join_workspace_bytes.restype = _sz
+        L.wsplumb_rowbn_join_workspace_bytes.argtypes = [_ll, _i]
+        L.wsplumb_rowbn_join_forward.restype = _i
+        L.wsplumb_rowbn_join_forward.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _f, _vp, _i, _i,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        L.wsplumb_rowbn_join_backward.restype = _i
+        L.wsplumb_rowbn_join_backward.argtypes = [_vp] * 5 + [_ll, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 8 + [_sz, _vp]
         L.wsplumb_tap_table_ints.restype = _i
         L.wsplumb_tap_table_ints.argtypes = []
         for name in ("wsplumb_tap_gather", "wsplumb_tap_col2im"):
@@ -149,6 +156,72 @@ def rowbn_backward(x, dy, weight, stats, relu, mask=None, pos_major=False):
     if rc:
         raise RuntimeError("wsplumb_rowbn_backward failed (%d)" % rc)
     return dx, dwb[0], dwb[1]
+
+
+def join_usable(x):
+    """True when the residual-join kernels may take this position-major [M, C] tensor."""
+    if os.environ.get("WSSDL_HEAD_UNFUSED_JOIN"):          # A/B switch: separate norms and a torch add
+        return False
+    return usable(x)
+
+
+def _pn(t):
+    return _p(t) if t is not None else None
+
+
+def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None):
+    """out = bn3(x3) + (bns(other) if bns else other); y = relu(bnn(out)): training-mode row batch norms over
+    position-major rows, each bn a (weight, bias, eps) triple, mask as in rowbn_forward(pos_major=True).
+    Returns (out, y, stats3, stats_s, stats_n, count or None), stats_s unwritten without bns; bit-identical to the
+    separate calls."""
+    L = lib()
+    M, C = x3.shape
+    dev = x3.device
+    assert other.shape == x3.shape and other.is_contiguous() and other.dtype == torch.float32
+    out, y = torch.empty_like(x3), torch.empty_like(x3)
+    stats = torch.empty((3, 5, C), dtype=torch.float32, device=dev)
+    count, n_rois = None, 0
+    if mask is not None:
+        n_rois = mask.shape[0]
+        assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
+        count = torch.empty((1,), dtype=torch.float32, device=dev)
+    ws_, bs_, es_ = bns if bns is not None else (None, None, 0.0)
+    with torch.cuda.device(dev):
+        n = L.wsplumb_rowbn_join_workspace_bytes(M, C)
+        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+        rc = L.wsplumb_rowbn_join_forward(_p(x3), _p(other), M, C, _p(bn3[0]), _p(bn3[1]), float(bn3[2]), _pn(ws_),
+                                          _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]), _pn(mask), n_rois,
+                                          M // n_rois if n_rois else 1, _p(out), _p(y), _p(stats[0]),
+                                          _p(stats[1]) if bns is not None else None, _p(stats[2]), _pn(count), _p(ws), n,
+                                          _stream())
+    if rc:
+        raise RuntimeError("wsplumb_rowbn_join_forward failed (%d)" % rc)
+    return out, y, stats[0], stats[1], stats[2], count
+
+
+def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, stats_s, mask=None):
+    """Gradients of rowbn_join_forward: dy for y, dres (or None) for out; xs / ws_ / stats_s None in the identity
+    form.  Returns (g, dx3, dxs or None, dwb_n, dwb3, dwb_s or None), the dwb [2, C] = (dweight, dbias); g is the
+    gradient of `other` in the identity form."""
+    L = lib()
+    M, C = x3.shape
+    dev = x3.device
+    dual = xs is not None
+    g, dx3 = torch.empty_like(x3), torch.empty_like(x3)
+    dxs = torch.empty_like(x3) if dual else None
+    dwb = torch.empty((3, 2, C), dtype=torch.float32, device=dev)
+    coef = torch.empty((9, C), dtype=torch.float32, device=dev)
+    n_rois = mask.shape[0] if mask is not None else 0
+    with torch.cuda.device(dev):
+        n = L.wsplumb_rowbn_join_workspace_bytes(M, C)
+        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+        rc = L.wsplumb_rowbn_join_backward(_p(out), _p(dy), _pn(dres), _p(x3), _pn(xs), M, C, _p(wn), _p(stats_n), _p(w3),
+                                           _p(stats3), _pn(ws_), _pn(stats_s), _pn(mask), n_rois,
+                                           M // n_rois if n_rois else 1, _p(g), _p(dx3), _pn(dxs), _p(dwb[0]), _p(dwb[1]),
+                                           _p(dwb[2]) if dual else None, _p(coef), _p(ws), n, _stream())
+    if rc:
+        raise RuntimeError("wsplumb_rowbn_join_backward failed (%d)" % rc)
+    return g, dx3, dxs, dwb[0], dwb[1], dwb[2] if dual else None
 
 
 def im2col_usable(x):

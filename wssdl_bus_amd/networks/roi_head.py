@@ -81,6 +81,41 @@ class _FusedRowBatchNormFn(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+class _JoinFn(torch.autograd.Function):
+    """The end of a block on the position-major route in one Function: out = bn3(x3) + other, where other is the
+    identity shortcut or (with the shortcut norm's weight / bias) bn_s(xs), then y = relu(bn_n(out)) with the next
+    block's pre-activation norm or the head's final norm.  The join kernels of csrc/plumbing/rowbn.hip apply
+    bn3 (and bn_s), add and take bn_n's statistics in one pass over the tensors, and in the backward form
+    g = bn_n's dx + the residual gradient together with the sums bn3's (bn_s's) backward takes over it; results
+    are bit-identical to the separate layers and torch's adds.  Returns out, y, the three [5, C] statistic
+    blocks (stats_s is not written in the identity form) and the live-row count."""
+
+    @staticmethod
+    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask):
+        dual = ws is not None
+        out, y, st3, sts, stn, count = _plumbing.rowbn_join_forward(
+            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask)
+        ctx.dual, ctx.masked = dual, roi_mask is not None
+        ctx.save_for_backward(x3, other if dual else None, out, w3, ws, wn, st3, sts, stn, roi_mask)
+        if count is None:
+            count = stn[0, :1]                         # placeholder (unused without a mask)
+        ctx.mark_non_differentiable(st3, sts, stn, count)
+        ctx.set_materialize_grads(False)
+        return out, y, st3, sts, stn, count
+
+    @staticmethod
+    def backward(ctx, dres, dy, *_):
+        x3, xs, out, w3, ws, wn, st3, sts, stn, roi_mask = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(out)
+        g, dx3, dxs, dwbn, dwb3, dwbs = _plumbing.rowbn_join_backward(
+            out, dy.contiguous(), dres.contiguous() if dres is not None else None, x3, xs, wn, stn, w3, st3, ws, sts,
+            roi_mask)
+        if ctx.dual:
+            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None
+        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None
+
+
 # The head can see RoI rows that are not live: the padding rows of the fixed-shape blob
 # (cfg.PADDED_ROIS) and those of a supervised image that ran short of candidates under the device
 # sampler (cfg.SAMPLING_RNG = 'device': the layer keeps its fixed S*128 rows, batch index -1).
@@ -142,9 +177,7 @@ class RowBatchNorm(nn.Module):
             else:
                 y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, _ROI_MASK,
                                                          pos_major)
-            with torch.no_grad():
-                self.running_mean.lerp_(mean, self.momentum)
-                self.running_var.lerp_(var * (n / (n - 1).clamp_min(1.0)), self.momentum)
+            self._track(mean, var, n)
             return y
         if fused:
             y, mean, var, _ = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu))
@@ -152,11 +185,16 @@ class RowBatchNorm(nn.Module):
             y, mean, var = _RowBatchNormFn.apply(x, self.weight, self.bias, self.eps)
             if relu:
                 y = F.relu(y)
-        with torch.no_grad():
-            m = x.shape[0]
-            self.running_mean.lerp_(mean, self.momentum)
-            self.running_var.lerp_(var * (m / max(m - 1, 1)), self.momentum)
+        self._track(mean, var, x.shape[0])
         return y
+
+    def _track(self, mean, var, n):
+        """running statistics from one batch's mean / biased variance over n rows (n: an int, or the live-row
+        count as a 0-d tensor)."""
+        with torch.no_grad():
+            unbias = n / (n - 1).clamp_min(1.0) if torch.is_tensor(n) else n / max(n - 1, 1)
+            self.running_mean.lerp_(mean, self.momentum)
+            self.running_var.lerp_(var * unbias, self.momentum)
 
 
 class ConvNHWC(nn.Module):
@@ -199,17 +237,18 @@ class ConvNHWC(nn.Module):
         return F.relu(y) if self.relu else y
 
     # ---- position-major route of the head's 4x4 section (ResNetHeadNHWC.forward) ----
-    def forward_pm(self, x, plan, R):
+    def forward_pm(self, x, plan, R, act=True):
         """x: roi-major [R, h, w, C] or position-major [rows, C] rows in `plan`'s slot order; returns
         position-major rows.  3x3: the class-packed GEMMs of `plan` (TapConv3x3Fn); 1x1 at stride s on a
-        roi-major input: the input positions of the slots, then a row GEMM; 1x1 on rows: a row GEMM."""
+        roi-major input: the input positions of the slots, then a row GEMM; 1x1 on rows: a row GEMM.
+        act=False: the convolution's raw output (its norm is applied by the block's join, _join_pm)."""
         if self.k == 3:
             y = _plumbing.TapConv3x3Fn.apply(x, self.weight, self.bias, plan, x.dim() == 2, R)
         else:
             if x.dim() == 4:
                 x = _pm_rows(x, plan, self.s)
             y = F.linear(x, self.weight, self.bias)
-        return self._act(y, pos_major=True)
+        return self._act(y, pos_major=True) if act else y
 
 
 def _pm_rows(x, plan, s):
@@ -246,13 +285,14 @@ class BottleneckNHWC(nn.Module):
         x = self.conv3(self.conv2(self.conv1(x)))
         return x + (self.short(ori) if self.short is not None else ori)
 
-    def forward_pm(self, x, plans, R):
+    def forward_pm(self, x, plans, R, pre=None, nxt=None):
         """forward on the position-major route: x roi-major [R, 7, 7, C] (first block) or position-major rows;
-        plans: {stride: TapPlan}; returns position-major rows."""
+        plans: {stride: TapPlan}; pre: this block's pre-activation when the previous block's join computed it;
+        nxt: the norm (+ReLU) that follows this block.  Returns (position-major rows, nxt's output or None)."""
         pm = x.dim() == 2
         ori = x
         if self.preact != "no_preact":
-            y = _pre_act(self.pre_bn, x, pm)
+            y = pre if pre is not None else _pre_act(self.pre_bn, x, pm)
             if self.preact == "both_preact":
                 ori = y
             x = y
@@ -262,10 +302,8 @@ class BottleneckNHWC(nn.Module):
             x = self.conv1(x)                                   # 1x1 on the roi-major 7x7 map
         else:
             x = self.conv1.forward_pm(x, plan, R)
-        x = self.conv3.forward_pm(self.conv2.forward_pm(x, plan, R), plan, R)
-        if self.short is not None:
-            return x + self.short.forward_pm(ori, plan, R)
-        return x + (ori if pm else _pm_rows(ori, plan, s))
+        x = self.conv3.forward_pm(self.conv2.forward_pm(x, plan, R), plan, R, act=False)
+        return _join_pm(self.conv3, x, self.short, ori, plan, s, R, nxt)
 
 
 class BasicBlockNHWC(nn.Module):
@@ -289,21 +327,46 @@ class BasicBlockNHWC(nn.Module):
         x = self.conv2(self.conv1(x))
         return x + (self.short(ori) if self.short is not None else ori)
 
-    def forward_pm(self, x, plans, R):
+    def forward_pm(self, x, plans, R, pre=None, nxt=None):
         """BottleneckNHWC.forward_pm for the basic block."""
         pm = x.dim() == 2
         ori = x
         if self.preact != "no_preact":
-            y = _pre_act(self.pre_bn, x, pm)
+            y = pre if pre is not None else _pre_act(self.pre_bn, x, pm)
             if self.preact == "both_preact":
                 ori = y
             x = y
         s = self.conv1.s
         plan = plans[s]
-        x = self.conv2.forward_pm(self.conv1.forward_pm(x, plan, R), plans[1], R)
-        if self.short is not None:
-            return x + self.short.forward_pm(ori, plan, R)
-        return x + (ori if pm else _pm_rows(ori, plan, s))
+        x = self.conv2.forward_pm(self.conv1.forward_pm(x, plan, R), plans[1], R, act=False)
+        return _join_pm(self.conv2, x, self.short, ori, plan, s, R, nxt)
+
+
+def _join_pm(last, x3, short, ori, plan, s, R, nxt):
+    """The end of a block (stride s) on the position-major route: act(x3) + shortcut, x3 the raw output of the
+    block's last convolution `last`.  Returns (out, relu(nxt(out))) from the join kernels (_JoinFn) when `nxt` is given and
+    every norm involved is a training-mode RowBatchNorm on a tensor the kernels take; else (out, None) from the
+    separate layers (also with WSSDL_HEAD_UNFUSED_JOIN=1)."""
+    if short is not None:
+        xs = short.forward_pm(ori, plan, R, act=False)
+    else:
+        xs = ori if ori.dim() == 2 else _pm_rows(ori, plan, s)
+    bns = [last.bn, nxt] + ([short.bn] if short is not None else [])
+    mask = _ROI_MASK
+    if (nxt is None or any(b is None or not b.training for b in bns) or last.relu or not _plumbing.join_usable(x3)
+            or (mask is not None and x3.shape[0] % mask.shape[0] != 0)):
+        return last._act(x3, pos_major=True) + (short._act(xs, pos_major=True) if short is not None else xs), None
+    b3, bs = last.bn, short.bn if short is not None else None
+    out, y, st3, sts, stn, n = _JoinFn.apply(
+        x3, xs.contiguous(), b3.weight, b3.bias, bs.weight if bs is not None else None,
+        bs.bias if bs is not None else None, nxt.weight, nxt.bias, b3.eps, bs.eps if bs is not None else 0.0, nxt.eps,
+        mask)
+    n = n[0] if mask is not None else x3.shape[0]
+    b3._track(st3[0], st3[1], n)
+    if bs is not None:
+        bs._track(sts[0], sts[1], n)
+    nxt._track(stn[0], stn[1], n)
+    return out, y
 
 
 def _pre_act(bn, x, pm):
@@ -354,7 +417,12 @@ class ResNetHeadNHWC(nn.Module):
         corners by _plumbing.TapPlan): each 3x3 class GEMM writes its own contiguous slab; batch norm,
         1x1 convolutions and residual adds do not care about row order, the final mean reduces over slots."""
         R = x.shape[0]
-        for blk in self.group3:
-            x = blk.forward_pm(x, plans, R)
-        x = self.norm(x, relu=True, pos_major=True) if self.norm is not None else F.relu(x)
-        return x.view(-1, R, x.shape[1]).mean(dim=0)
+        blocks, pre = list(self.group3), None
+        for i, blk in enumerate(blocks):
+            # the norm (+ReLU) after this block: the next block's pre-activation, or the final norm
+            nxt = self.norm if i + 1 == len(blocks) else \
+                (blocks[i + 1].pre_bn if blocks[i + 1].preact != "no_preact" else None)
+            x, pre = blk.forward_pm(x, plans, R, pre, nxt)
+        if pre is None:
+            pre = self.norm(x, relu=True, pos_major=True) if self.norm is not None else F.relu(x)
+        return pre.view(-1, R, pre.shape[1]).mean(dim=0)
