@@ -121,6 +121,8 @@ def test_tuning_knobs_are_plain_ints(lib_path):
         assert _lib.get_tuning("roi_bwd_plan") == 11 and _lib.get_tuning("nms_one_pass") == 1
     assert _lib.get_tuning("roi_bwd_plan") == -1 and _lib.get_tuning("nms_one_pass") == 0
     assert L.wssdl_set_tuning(b"no_such_knob", 1) == _lib.ERR_INVALID_ARGUMENT
+    # (the barrier-free NMS sweep and its knob were removed: the name is an unknown key like any other)
+    assert L.wssdl_set_tuning(b"nms_sweep_async", 1) == _lib.ERR_INVALID_ARGUMENT
     assert L.wssdl_roi_pool_backward_plan_count() >= 26
     off = L.wssdl_roi_pool_backward_status_offset(8512, 8, 38, 63, 7, 7)
     assert off % 256 == 0 and 0 < off < L.wssdl_roi_pool_backward_workspace_bytes(8512, 8, 38, 63, 7, 7)

@@ -31,26 +31,31 @@ def test_a_violation_is_caught(monkeypatch):
     """the checker rejects a listing that touches v80-v95 outside the three allowed instruction shapes"""
     good = ["\tglobal_load_dwordx2 v[80:81], v[2:3], off"] * 8 + ["\tv_mov_b32_e32 v80, 0"] * 16 + \
            ["\tv_or3_b32 v4, v80, v82, v84"] * 8
-    def both(lines):       # each kernel in its two instances (the barrier form and the form without it)
-        return {"%s<%s>" % (k, b): list(lines) for k in isa_check.KERNELS for b in ("false", "true")}
-    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: both(good))
+    def listings(lines):       # one listing per kernel
+        return {k: list(lines) for k in isa_check.KERNELS}
+    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: listings(good))
     assert isa_check.check_library("unused")
-    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: both(good + good))       # the turn duplicated whole
+    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: listings(good + good))       # the turn duplicated whole
     assert isa_check.check_library("unused")
     bad = good + ["\tv_add_f32_e32 v85, v1, v2"]
-    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: both(bad))
+    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: listings(bad))
     with pytest.raises(isa_check.IsaCheckError, match="outside the helpers"):
         isa_check.check_library("unused")
     monkeypatch.setattr(isa_check, "kernel_listings",
-                        lambda lib, tmp: both(good + ["\tbuffer_load_dwordx4 v[78:81], v2, s[4:7], 0 offen"]))   # a tuple across the boundary
+                        lambda lib, tmp: listings(good + ["\tbuffer_load_dwordx4 v[78:81], v2, s[4:7], 0 offen"]))   # a tuple across the boundary
     with pytest.raises(isa_check.IsaCheckError, match="reaches into"):
         isa_check.check_library("unused")
-    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: both(good[1:]))          # a batch load went missing
+    monkeypatch.setattr(isa_check, "kernel_listings", lambda lib, tmp: listings(good[1:]))          # a batch load went missing
     with pytest.raises(isa_check.IsaCheckError, match="multiples"):
         isa_check.check_library("unused")
     monkeypatch.setattr(isa_check, "kernel_listings",
-                        lambda lib, tmp: {k: list(good) for k in isa_check.KERNELS})            # one instance each only
-    with pytest.raises(isa_check.IsaCheckError, match="two instances"):
+                        lambda lib, tmp: {isa_check.KERNELS[0]: list(good)})                     # a kernel is missing
+    with pytest.raises(isa_check.IsaCheckError, match="exactly one instance.*found 0"):
+        isa_check.check_library("unused")
+    second = isa_check.KERNELS[1] + "<true>"
+    monkeypatch.setattr(isa_check, "kernel_listings",
+                        lambda lib, tmp: dict(listings(good), **{second: list(good)}))             # a second instance of a kernel
+    with pytest.raises(isa_check.IsaCheckError, match="exactly one instance.*found 2.*" + second):
         isa_check.check_library("unused")
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CPU model (round 6): how many rounds a fixed-point ("decide every box whose higher-scored neighbours are all decided")
-form of the greedy NMS would need on the synthetic regimes of tools/nms_async_ab.py, and how sparse the neighbour lists
-are.  Greedy NMS has one fixed point: kept(i) <=> no kept j < i with IoU(i, j) >= t; iterating the rule from "unknown" in
+form of the greedy NMS would need on three synthetic regimes of the 12000 -> 2000 layer -- early stop (box deltas x 1.0,
+threshold 0.7) and full walks (x 0.5 at 0.5, x 0.3 at 0.3); the first and the last are the two of
+tools/nms_sweep_profile.py -- and how sparse the neighbour lists are.  Greedy NMS has one fixed point: kept(i) <=> no kept j < i with IoU(i, j) >= t; iterating the rule from "unknown" in
 parallel reaches it in (longest alternating chain) rounds.  python3 tools/probes/nms_rounds_model.py"""
 import os
 import sys

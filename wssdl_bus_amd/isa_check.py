@@ -83,22 +83,23 @@ def kernel_listings(lib_path, tmp):
             head = part.split("\n", 1)[0]
             for k in KERNELS:
                 if k in head:
-                    # (each kernel exists in two instances since round 6: the barrier form and the form without it)
                     m = re.search(r"<([^>]+)>", head)
                     out[m.group(1) if m else head] = part.split("\n")[1:]
     return out
 
 
 def check_library(lib_path):
-    """Raises IsaCheckError unless every instance of the sweep kernels keeps v80-v95 to the helpers' asm statements."""
+    """Raises IsaCheckError unless the library holds exactly one instance of each sweep kernel and each keeps v80-v95
+    to the helpers' asm statements."""
     tmp = tempfile.mkdtemp(prefix="wssdl_isa_")
     try:
         listings = kernel_listings(lib_path, tmp)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     for k in KERNELS:
-        if sum(1 for name in listings if k in name) < 2:
-            raise IsaCheckError("kernel %s: fewer than its two instances found in %s: have %s" % (k, lib_path, sorted(listings)))
+        found = sorted(name for name in listings if k in name)
+        if len(found) != 1:
+            raise IsaCheckError("kernel %s: expected exactly one instance in %s, found %d: %s" % (k, lib_path, len(found), found))
     for k, lines in listings.items():
         loads = zeroed = ors = 0
         for line in lines:
