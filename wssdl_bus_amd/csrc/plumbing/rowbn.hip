@@ -92,14 +92,40 @@ __device__ __forceinline__ void slab_reduce(const Slab &b, int C, int c4, const 
     }
 }
 
+// ---- block 1's entry gradient (networks/roi_head.py, _EntryNormFn) ----
+// Block 1's pre-activation output y (roi-major rows, `per` positions per RoI) feeds conv1 at every position and
+// the projection shortcut at the positions it samples.  Its gradient at row r = roi * per + p is
+//   dy[r] + (possel[p] >= 0 ? dys[possel[p] * R + roi] + 0 : 0)
+// with dy conv1's gradient, dys the shortcut's position-major gradient and possel[p] the shortcut's slot of
+// position p (-1: not sampled).  The ENTRY variants of the two backward kernels form it in registers.  The
+// "+ 0" is kept: the separate ops scatter dys into a zero tensor first, which turns a -0 into +0.
+struct EntryGrad {
+    const float *dys;       // [n_slots * R, C]
+    const int *possel;      // [per]
+    int per, R;
+};
+
+template <bool ENTRY>
+__device__ __forceinline__ float4v load_dy(const float *__restrict__ dy, const EntryGrad &e, long long r, int C, int c4) {
+    const float4v g = reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4];
+    if (!ENTRY) return g;
+    const unsigned roi = (unsigned)r / (unsigned)e.per, p = (unsigned)r - roi * (unsigned)e.per;
+    const int slot = e.possel[p];
+    const float4v zero4 = {0, 0, 0, 0};
+    float4v d = zero4;
+    if (slot >= 0) d = reinterpret_cast<const float4v *>(e.dys + ((size_t)slot * e.R + roi) * C)[c4] + zero4;
+    return g + d;
+}
+
 // Partial column sums of one row slab (thread mapping: Slab).
 // MODE 0: s = sum x,  q = sum x*x
 // MODE 1: s = sum g,  q = sum g*x   with g = dy, masked by (x*scale + shift > 0) when RELU
-template <int MODE, bool RELU, int MASK>
+// ENTRY: dy is block 1's entry gradient (EntryGrad; MODE 1, roi-major rows, M < 2^31)
+template <int MODE, bool RELU, int MASK, bool ENTRY = false>
 __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ scale,
     const float *__restrict__ shift, long long M, int C, long long rows_per_block,
-    double *__restrict__ partial, const float *__restrict__ mask, int per) {
+    double *__restrict__ partial, const float *__restrict__ mask, int per, EntryGrad eg = EntryGrad()) {
     __shared__ double red[BLOCK][8];
     const Slab b(M, C, rows_per_block);
     const int C4 = b.C4, L = b.L, RS = b.RS, lc = b.lc, lr = b.lr;
@@ -128,8 +154,8 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
                 const float4v a1 = live1 ? reinterpret_cast<const float4v *>(x + (size_t)(r + RS) * C)[c4] : zero4;
                 float4v g0, g1;
                 if (MODE == 1) {
-                    g0 = live0 ? reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4] : zero4;
-                    g1 = live1 ? reinterpret_cast<const float4v *>(dy + (size_t)(r + RS) * C)[c4] : zero4;
+                    g0 = live0 ? load_dy<ENTRY>(dy, eg, r, C, c4) : zero4;
+                    g1 = live1 ? load_dy<ENTRY>(dy, eg, r + RS, C, c4) : zero4;
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -153,7 +179,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
                 if (MASK && mask[mask_roi<MASK>(r, per)] == 0.0f) continue;
                 const float4v a0 = reinterpret_cast<const float4v *>(x + (size_t)r * C)[c4];
                 float4v g0;
-                if (MODE == 1) g0 = reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4];
+                if (MODE == 1) g0 = load_dy<ENTRY>(dy, eg, r, C, c4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (MODE == 0) {
@@ -290,11 +316,11 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_fwd_kernel(
     }
 }
 
-template <bool RELU, int MASK>
+template <bool RELU, int MASK, bool ENTRY = false>
 __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ scale,
     const float *__restrict__ shift, const float *__restrict__ coef, long long total4, int C4,
-    float *__restrict__ dx, const float *__restrict__ mask, int per) {
+    float *__restrict__ dx, const float *__restrict__ mask, int per, EntryGrad eg = EntryGrad()) {
     const int C = C4 * 4;
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total4;
          i += (long long)gridDim.x * BLOCK) {
@@ -305,7 +331,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
             continue;
         }
         const float4v a = reinterpret_cast<const float4v *>(x)[i];
-        const float4v g = reinterpret_cast<const float4v *>(dy)[i];
+        const float4v g = ENTRY ? load_dy<true>(dy, eg, i / C4, C, c4) : reinterpret_cast<const float4v *>(dy)[i];
         const float4v ka = reinterpret_cast<const float4v *>(coef)[c4];
         const float4v k0 = reinterpret_cast<const float4v *>(coef + C)[c4];
         const float4v k1 = reinterpret_cast<const float4v *>(coef + 2 * C)[c4];
@@ -686,6 +712,43 @@ PLUMB_API int wsplumb_rowbn_backward_masked_pm(const float *x, const float *dy, 
     if (!mask) return 1;
     return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, mask, n_rois, per,
                          workspace, workspace_bytes, stream, true);
+}
+
+// gradients of wsplumb_rowbn_forward[_masked] with ReLU for block 1's pre-activation norm, the output's gradient
+// given in its two parts (EntryGrad above): dy [n_rois * per, C] roi-major from conv1, dys [n_slots * n_rois, C]
+// position-major from the projection shortcut, possel [per] (device) the slot of each position or -1.
+// mask may be null.  Bit-identical to wsplumb_rowbn_backward[_masked] on dy + scatter(dys).
+PLUMB_API int wsplumb_rowbn_backward_entry(const float *x, const float *dy, const float *dys, const int *possel,
+                                           int n_slots, long long M, int C, const float *weight, const float *mean,
+                                           const float *rstd, const float *scale, const float *shift,
+                                           const float *mask, int n_rois, int per, float *dx, float *dweight,
+                                           float *dbias, float *coef, void *workspace, size_t workspace_bytes,
+                                           void *stream) {
+    if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
+    if (!dys || !possel || per < 1 || n_rois < 1 || n_slots < 1 || n_slots > per ||
+        (long long)n_rois * per != M || M > 0x7fffffffLL)
+        return 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = partial_blocks(M, C);
+    const long long rpb = (M + nb - 1) / nb;
+    double *partial = static_cast<double *>(workspace);
+    const EntryGrad eg = {dys, possel, per, n_rois};
+    if (mask)
+        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 1, true>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M,
+                           C, rpb, partial, mask, per, eg);
+    else
+        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 0, true>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M,
+                           C, rpb, partial, mask, 1, eg);
+    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st,
+                       partial, nb, C, M, weight, mean, rstd, dweight, dbias, coef, mask, n_rois, per);
+    const long long total4 = M * (C / 4);
+    if (mask)
+        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<true, 1, true>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy,
+                           scale, shift, coef, total4, C / 4, dx, mask, per, eg);
+    else
+        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<true, 0, true>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy,
+                           scale, shift, coef, total4, C / 4, dx, mask, 1, eg);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
 // ---- residual joins (position-major rows; mask may be null: every row live) ----

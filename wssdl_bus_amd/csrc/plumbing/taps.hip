@@ -46,81 +46,106 @@ __device__ __forceinline__ int find_class(const int *__restrict__ T, unsigned q)
     return k;
 }
 
-// one thread = one float4 of the packed patch matrix; consecutive threads walk c, then the tap,
-// then the RoI: coalesced writes, reads coalesced per tap.  32-bit index math (total4 < 2^31).
+// Thread mapping of the two patch kernels: a workgroup owns one (position, tap) unit of the table (gather) or
+// one input position (adjoint) and a chunk of RoIs, so the class, the tap, the source position and every
+// table entry are the same for all its threads and come from scalar loads, once.  Thread t then walks
+// float4 column(s) t % L (+ L ...) of RoIs roi0 + t / L (+ RS ...): L = C/4 and RS = 256 / L rows per pass when
+// C/4 divides 256, else L = 256 columns of one row.  Per element: a float4 load, a float4 store, an add.
+struct RoiWalk {
+    unsigned L, RS, lc, lr, roi0, roi1;
+    __device__ __forceinline__ RoiWalk(unsigned R, unsigned C4, unsigned chunk) {
+        L = (C4 <= 256u && 256u % C4 == 0u) ? C4 : 256u;
+        RS = 256u / L;
+        lc = threadIdx.x % L;
+        lr = threadIdx.x / L;
+        roi0 = blockIdx.x * chunk;
+        roi1 = roi0 + chunk < R ? roi0 + chunk : R;
+    }
+};
+
+constexpr unsigned GATHER_CHUNK = 32, COL2IM_CHUNK = 16;    // RoIs per workgroup
+
+// blockIdx.y = unit q of the packed patch matrix (class k, position p of the class, tap tl of the class),
+// blockIdx.x = RoI chunk.  32-bit index math (total4 < 2^31, checked by the entry point).
 __global__ __launch_bounds__(256) void tap_gather_kernel(const float *__restrict__ x, const int *__restrict__ T,
-                                                        int in_pm, unsigned R, unsigned C4, unsigned total4,
+                                                        int in_pm, unsigned R, unsigned C4,
                                                         float *__restrict__ cols) {
     const int H = T[TAB_H], W = T[TAB_W], OW = T[TAB_OW], S = T[TAB_S], PT = T[TAB_PT], PL = T[TAB_PL];
-    const unsigned unit4 = R * C4;                       // float4s of one (position, tap) unit
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total4; i += gridDim.x * 256u) {
-        const int k = find_class<C_CUM>(T, i / unit4);
-        const int *cl = cls_of(T, k);
-        const unsigned ntaps = cl[C_NTAPS];
-        const unsigned local = i - (unsigned)cl[C_CUM] * unit4;
-        const unsigned c4 = local % C4, t = local / C4;
-        const unsigned tl = t % ntaps, row = t / ntaps;
-        const unsigned roi = row % R, p = row / R;
-        const int pos = T[TAB_SLOTPOS + cl[C_SLOT] + p];
-        const int tap = cl[C_TAPS + tl];
-        const int y = (pos / OW) * S + tap / 3 - PT, xx = (pos % OW) * S + tap % 3 - PL;
-        float4v v = {0.f, 0.f, 0.f, 0.f};
-        if (y >= 0 && y < H && xx >= 0 && xx < W) {     // always true by construction of the classes
-            const size_t src = in_pm ? (size_t)T[TAB_POSSLOT + y * W + xx] * R + roi
-                                     : ((size_t)roi * H + y) * W + xx;
-            v = reinterpret_cast<const float4v *>(x)[src * C4 + c4];
+    const unsigned q = blockIdx.y;
+    const int *cl = cls_of(T, find_class<C_CUM>(T, q));
+    const unsigned ntaps = cl[C_NTAPS], local = q - (unsigned)cl[C_CUM];
+    const unsigned p = local / ntaps, tl = local - p * ntaps;
+    const int pos = T[TAB_SLOTPOS + cl[C_SLOT] + p];
+    const int tap = cl[C_TAPS + tl];
+    const int y = (pos / OW) * S + tap / 3 - PT, xx = (pos % OW) * S + tap % 3 - PL;
+    const bool inside = y >= 0 && y < H && xx >= 0 && xx < W;   // always true by construction of the classes
+    // source float4 of (roi, c4) = sbase + roi * sstride + c4, destination = dbase + roi * dstride + c4
+    const unsigned sbase = !inside ? 0u : in_pm ? (unsigned)T[TAB_POSSLOT + y * W + xx] * R * C4 : (unsigned)(y * W + xx) * C4;
+    const unsigned sstride = in_pm ? C4 : (unsigned)(H * W) * C4;
+    const unsigned dstride = ntaps * C4;
+    const unsigned dbase = (unsigned)cl[C_CUM] * R * C4 + p * R * dstride + tl * C4;
+    const float4v *__restrict__ src = reinterpret_cast<const float4v *>(x) + sbase;
+    float4v *__restrict__ dst = reinterpret_cast<float4v *>(cols) + dbase;
+    const RoiWalk w(R, C4, GATHER_CHUNK);
+    const float4v zero4 = {0.f, 0.f, 0.f, 0.f};
+    for (unsigned c4 = w.lc; c4 < C4; c4 += w.L) {
+        unsigned roi = w.roi0 + w.lr;
+        for (; roi + 3u * w.RS < w.roi1; roi += 4u * w.RS) {          // four rows in flight
+            float4v v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = inside ? src[(roi + k * w.RS) * sstride + c4] : zero4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[(roi + k * w.RS) * dstride + c4] = v[k];
         }
-        reinterpret_cast<float4v *>(cols)[i] = v;
+        for (; roi < w.roi1; roi += w.RS) dst[roi * dstride + c4] = inside ? src[roi * sstride + c4] : zero4;
     }
 }
 
-// adjoint: one thread = one float4 of dx; adds the (at most 9) packed entries that copied it in the
-// (ky, kx) order of col2im3x3_kernel (im2col.hip), so that it is bit-equal to the dense adjoint given the
-// same values in the valid columns
+// adjoint: blockIdx.y = input position (row-major y*W+x of the roi-major layout, or the slot with in_pm),
+// blockIdx.x = RoI chunk.  The (at most 9) packed units that copied the position are resolved once, in the
+// (ky, kx) order of col2im3x3_kernel (im2col.hip), and every element adds them in that order starting from
+// +0, so that it is bit-equal to the dense adjoint given the same values in the valid columns.
 __global__ __launch_bounds__(256) void tap_col2im_kernel(const float *__restrict__ dcols, const int *__restrict__ T,
-                                                        int in_pm, unsigned R, unsigned C4, unsigned total4,
+                                                        int in_pm, unsigned R, unsigned C4,
                                                         float *__restrict__ dx) {
     const int H = T[TAB_H], W = T[TAB_W], OH = T[TAB_OH], OW = T[TAB_OW], S = T[TAB_S], PT = T[TAB_PT],
               PL = T[TAB_PL];
-    const unsigned unit4 = R * C4;
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total4; i += gridDim.x * 256u) {
-        const unsigned c4 = i % C4, row = i / C4;
-        unsigned roi;
-        int y, xx;
-        if (in_pm) {
-            roi = row % R;
-            const int pos = T[TAB_SLOTPOS + row / R];
-            y = pos / W;
-            xx = pos % W;
-        } else {
-            xx = (int)(row % (unsigned)W);
-            const unsigned t = row / (unsigned)W;
-            y = (int)(t % (unsigned)H);
-            roi = t / (unsigned)H;
-        }
-        float4v acc = {0.f, 0.f, 0.f, 0.f};
+    const int pos = in_pm ? T[TAB_SLOTPOS + blockIdx.y] : (int)blockIdx.y;
+    const int y = pos / W, xx = pos % W;
+    unsigned base[9], stride[9], valid = 0;
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int ny = y + PT - ky;
-            if (ny < 0 || ny % S != 0) continue;
-            const int oy = ny / S;
-            if (oy >= OH) continue;
+    for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int nx = xx + PL - kx;
-                if (nx < 0 || nx % S != 0) continue;
-                const int ox = nx / S;
-                if (ox >= OW) continue;
-                const int slot = T[TAB_POSSLOT + oy * OW + ox];
-                const int *cl = cls_of(T, T[TAB_SLOTCLS + slot]);
-                const int tl = cl[C_TAPIDX + ky * 3 + kx];
-                if (tl < 0) continue;                  // never: an in-bounds input is a valid tap
-                const size_t u = (size_t)cl[C_CUM] * unit4 +
-                                 (((size_t)(slot - cl[C_SLOT]) * R + roi) * cl[C_NTAPS] + tl) * C4 + c4;
-                acc += reinterpret_cast<const float4v *>(dcols)[u];
-            }
+        for (int kx = 0; kx < 3; ++kx) {
+            const int j = ky * 3 + kx;
+            base[j] = stride[j] = 0;
+            const int ny = y + PT - ky, nx = xx + PL - kx;
+            if (ny < 0 || ny % S != 0 || nx < 0 || nx % S != 0) continue;
+            const int oy = ny / S, ox = nx / S;
+            if (oy >= OH || ox >= OW) continue;
+            const int slot = T[TAB_POSSLOT + oy * OW + ox];
+            const int *cl = cls_of(T, T[TAB_SLOTCLS + slot]);
+            const int tl = cl[C_TAPIDX + j];
+            if (tl < 0) continue;                      // never: an in-bounds input is a valid tap
+            stride[j] = (unsigned)cl[C_NTAPS] * C4;
+            base[j] = (unsigned)cl[C_CUM] * R * C4 + (unsigned)(slot - cl[C_SLOT]) * R * stride[j] + (unsigned)tl * C4;
+            valid |= 1u << j;
         }
-        reinterpret_cast<float4v *>(dx)[i] = acc;
+    }
+    const float4v *__restrict__ src = reinterpret_cast<const float4v *>(dcols);
+    // destination float4 of (roi, c4) = dbase + roi * dstride + c4
+    const unsigned dbase = in_pm ? blockIdx.y * R * C4 : (unsigned)pos * C4;
+    const unsigned dstride = in_pm ? C4 : (unsigned)(H * W) * C4;
+    float4v *__restrict__ dst = reinterpret_cast<float4v *>(dx) + dbase;
+    const RoiWalk w(R, C4, COL2IM_CHUNK);
+    for (unsigned c4 = w.lc; c4 < C4; c4 += w.L) {
+        for (unsigned roi = w.roi0 + w.lr; roi < w.roi1; roi += w.RS) {
+            float4v acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 9; ++j)
+                if (valid & (1u << j)) acc += src[base[j] + roi * stride[j] + c4];
+            dst[roi * dstride + c4] = acc;
+        }
     }
 }
 
@@ -168,6 +193,9 @@ inline int grid_for(unsigned total4) {
     return (int)(b < 262144u ? b : 262144u);
 }
 
+// workgroups along x of the patch kernels: RoI chunks (R < 2^31 by dims_ok)
+inline unsigned roi_chunks(long long R, unsigned chunk) { return (unsigned)((R + chunk - 1) / chunk); }
+
 // R, C and the products the kernels index with 32-bit math
 inline bool dims_ok(long long R, int C, long long total4) {
     return R >= 1 && C >= 4 && !(C & 3) && total4 >= 1 && total4 <= 0x7fffffffLL;
@@ -185,9 +213,9 @@ PLUMB_API int wsplumb_tap_gather(const float *x, long long R, int C, const int *
     const long long total4 = (long long)hnum[TAB_UNITS] * R * (C / 4);
     if (R < 1 || C < 4 || (C & 3)) return 1;
     if (!dims_ok(R, C, total4) || (long long)hnum[TAB_H] * hnum[TAB_W] * R * (C / 4) > 0x7fffffffLL) return 2;
-    hipLaunchKernelGGL(tap_gather_kernel, dim3(grid_for((unsigned)total4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, tab, in_pm, (unsigned)R, (unsigned)(C / 4),
-                       (unsigned)total4, cols);
+    if (hnum[TAB_UNITS] < 1 || hnum[TAB_UNITS] > 65535) return 1;
+    hipLaunchKernelGGL(tap_gather_kernel, dim3(roi_chunks(R, GATHER_CHUNK), hnum[TAB_UNITS]), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, tab, in_pm, (unsigned)R, (unsigned)(C / 4), cols);
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
@@ -197,9 +225,9 @@ PLUMB_API int wsplumb_tap_col2im(const float *dcols, long long R, int C, const i
     const long long total4 = (long long)hnum[TAB_H] * hnum[TAB_W] * R * (C / 4);
     if (R < 1 || C < 4 || (C & 3)) return 1;
     if (!dims_ok(R, C, total4) || (long long)hnum[TAB_UNITS] * R * (C / 4) > 0x7fffffffLL) return 2;
-    hipLaunchKernelGGL(tap_col2im_kernel, dim3(grid_for((unsigned)total4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), dcols, tab, in_pm, (unsigned)R, (unsigned)(C / 4),
-                       (unsigned)total4, dx);
+    if (hnum[TAB_H] * hnum[TAB_W] < 1 || hnum[TAB_H] * hnum[TAB_W] > MAX_POS) return 1;
+    hipLaunchKernelGGL(tap_col2im_kernel, dim3(roi_chunks(R, COL2IM_CHUNK), hnum[TAB_H] * hnum[TAB_W]), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), dcols, tab, in_pm, (unsigned)R, (unsigned)(C / 4), dx);
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 

@@ -47,6 +47,8 @@ def lib():
         for name in ("wsplumb_rowbn_forward_masked_pm", "wsplumb_rowbn_backward_masked_pm"):
             base = getattr(L, name[:-3])
             getattr(L, name).restype, getattr(L, name).argtypes = base.restype, base.argtypes
+        L.wsplumb_rowbn_backward_entry.restype = _i
+        L.wsplumb_rowbn_backward_entry.argtypes = [_vp] * 4 + [_i, _ll, _i] + [_vp] * 6 + [_i, _i] + [_vp] * 5 + [_sz, _vp]
         L.wsplumb_rowbn_join_workspace_bytes.restype = _sz
         L.wsplumb_rowbn_join_workspace_bytes.argtypes = [_ll, _i]
         L.wsplumb_rowbn_join_forward.restype = _i
@@ -155,6 +157,39 @@ def rowbn_backward(x, dy, weight, stats, relu, mask=None, pos_major=False):
                     _p(mask), n_rois, M // n_rois, _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream())
     if rc:
         raise RuntimeError("wsplumb_rowbn_backward failed (%d)" % rc)
+    return dx, dwb[0], dwb[1]
+
+
+def entry_usable(x):
+    """True when block 1's pre-activation norm may take its output's gradient in two parts (rowbn_backward_entry)
+    for this roi-major [M, C] tensor."""
+    if os.environ.get("WSSDL_HEAD_UNFUSED_ENTRY"):         # A/B switch: torch's scatter and add, then the plain backward
+        return False
+    return usable(x) and x.shape[0] < 2 ** 31
+
+
+def rowbn_backward_entry(x, dy, dys, possel, n_slots, weight, stats, mask=None):
+    """rowbn_backward(relu=True) of roi-major rows x [R * per, C] whose output gradient is dy [R * per, C] plus, at the
+    positions p with possel[p] = slot >= 0 (int32 [per] on the device), the position-major dys [n_slots * R, C]:
+    bit-identical to the plain backward on dy + scatter(dys), without forming that sum in memory."""
+    L = lib()
+    M, C = x.shape
+    dev = x.device
+    per = possel.shape[0]
+    n_rois = M // per
+    assert M == n_rois * per and dy.shape == x.shape and dys.shape == (n_slots * n_rois, C)
+    assert dy.is_contiguous() and dys.is_contiguous() and possel.dtype == torch.int32 and possel.is_contiguous()
+    assert mask is None or (mask.shape[0] == n_rois and mask.dtype == torch.float32 and mask.is_contiguous())
+    dx = torch.empty_like(x)
+    dwb = torch.empty((2, C), dtype=torch.float32, device=dev)
+    coef = torch.empty((3, C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, n = _workspace(L, M, C, dev)
+        rc = L.wsplumb_rowbn_backward_entry(_p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight), _p(stats[0]),
+                                            _p(stats[2]), _p(stats[3]), _p(stats[4]), _pn(mask), n_rois, per, _p(dx),
+                                            _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream())
+    if rc:
+        raise RuntimeError("wsplumb_rowbn_backward_entry failed (%d)" % rc)
     return dx, dwb[0], dwb[1]
 
 
@@ -358,6 +393,19 @@ class TapPlan:
         if t is None:
             t = self._dev[key] = torch.tensor([y * s * w_in + x * s for y, x in self.slots],
                                               dtype=torch.long, device=dev)
+        return t
+
+
+    def subsample_slots(self, h_in, w_in, s, dev):
+        """Inverse of subsample_index as an int32 [h_in * w_in] tensor: the slot that reads each input position,
+        -1 for the positions no slot reads."""
+        key = ("subinv", h_in, w_in, s, dev)
+        t = self._dev.get(key)
+        if t is None:
+            inv = [-1] * (h_in * w_in)
+            for sl, (y, x) in enumerate(self.slots):
+                inv[y * s * w_in + x * s] = sl
+            t = self._dev[key] = torch.tensor(inv, dtype=torch.int32, device=dev)
         return t
 
 

@@ -116,6 +116,37 @@ class _JoinFn(torch.autograd.Function):
         return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None
 
 
+class _EntryNormFn(torch.autograd.Function):
+    """Block 1's pre-activation norm + ReLU on the position-major route, with both consumers of its output y in
+    one Function: returns y (roi-major rows, for conv1) and the position-major rows of the positions the
+    projection shortcut samples (_pm_rows).  The backward takes the two gradients as they arrive and forms
+    their sum inside the norm's two backward passes (rowbn.hip, EntryGrad): no zero-fill, index_add, strided
+    add or contiguous copy of a [R, 49, C] tensor.  Bit-identical to the separate layers."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, roi_mask, plan, s, hw):
+        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, True, roi_mask, False)
+        h, w = hw
+        r = x.shape[0] // (h * w)
+        ys = _pm_rows(y.view(r, h, w, -1), plan, s)
+        ctx.save_for_backward(x, weight, stats, roi_mask)
+        ctx.geom = (plan, s, h, w)
+        if count is None:
+            count = stats[0, :1]                       # placeholder (unused without a mask)
+        mean, var = stats[0], stats[1]
+        ctx.mark_non_differentiable(mean, var, count)
+        return y, ys, mean, var, count
+
+    @staticmethod
+    def backward(ctx, dy, dys, *_):
+        x, weight, stats, roi_mask = ctx.saved_tensors
+        plan, s, h, w = ctx.geom
+        dx, dw, db = _plumbing.rowbn_backward_entry(x, dy.contiguous(), dys.contiguous(),
+                                                    plan.subsample_slots(h, w, s, x.device), len(plan.slots), weight,
+                                                    stats, roi_mask)
+        return dx, dw, db, None, None, None, None, None
+
+
 # The head can see RoI rows that are not live: the padding rows of the fixed-shape blob
 # (cfg.PADDED_ROIS) and those of a supervised image that ran short of candidates under the device
 # sampler (cfg.SAMPLING_RNG = 'device': the layer keeps its fixed S*128 rows, batch index -1).
@@ -291,19 +322,32 @@ class BottleneckNHWC(nn.Module):
         nxt: the norm (+ReLU) that follows this block.  Returns (position-major rows, nxt's output or None)."""
         pm = x.dim() == 2
         ori = x
-        if self.preact != "no_preact":
+        s = self.conv2.s
+        plan = plans[s]
+        if self._entry_fused(x, pre):
+            x, ori = _entry_pre_act(self.pre_bn, x, plan, s)   # ori: the shortcut's rows, already position-major
+        elif self.preact != "no_preact":
             y = pre if pre is not None else _pre_act(self.pre_bn, x, pm)
             if self.preact == "both_preact":
                 ori = y
             x = y
-        s = self.conv2.s
-        plan = plans[s]
         if not pm:
             x = self.conv1(x)                                   # 1x1 on the roi-major 7x7 map
         else:
             x = self.conv1.forward_pm(x, plan, R)
         x = self.conv3.forward_pm(self.conv2.forward_pm(x, plan, R), plan, R, act=False)
         return _join_pm(self.conv3, x, self.short, ori, plan, s, R, nxt)
+
+
+    def _entry_fused(self, x, pre):
+        """True when this is block 1 of the position-major route in the form _EntryNormFn covers: a roi-major
+        input, a training-mode pre-activation norm whose output feeds both conv1 and a projection shortcut."""
+        bn, mask = self.pre_bn, _ROI_MASK
+        if x.dim() != 4 or pre is not None or self.preact != "both_preact" or self.short is None or bn is None:
+            return False
+        rows = x.reshape(-1, x.shape[3])
+        return (bn.training and torch.is_grad_enabled() and _plumbing.entry_usable(rows)
+                and (mask is None or rows.shape[0] % mask.shape[0] == 0))
 
 
 class BasicBlockNHWC(nn.Module):
@@ -367,6 +411,14 @@ def _join_pm(last, x3, short, ori, plan, s, R, nxt):
         bs._track(sts[0], sts[1], n)
     nxt._track(stn[0], stn[1], n)
     return out, y
+
+
+def _entry_pre_act(bn, x, plan, s):
+    """Block 1's pre-activation through _EntryNormFn: (y roi-major [R, h, w, C], the shortcut's position-major rows)."""
+    r, h, w, c = x.shape
+    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, _ROI_MASK, plan, s, (h, w))
+    bn._track(mean, var, n[0] if _ROI_MASK is not None else r * h * w)
+    return y.view(r, h, w, c), ys
 
 
 def _pre_act(bn, x, pm):
