@@ -238,18 +238,41 @@ __device__ __forceinline__ double live_rows(const float *__restrict__ mask, int 
     return t < 1.0 ? 1.0 : t;
 }
 
-// forward finish: mean / biased var / scale / shift per column
+// The layer's running statistics (nn.BatchNorm's buffers), updated by the forward finish kernel from the batch
+// statistics it has just written; any pointer may be null (that buffer is left alone).
+//   running_mean += momentum * (mean - running_mean)
+//   running_var  += momentum * (var * n / max(n - 1, 1) - running_var)      n = the rows the statistics cover
+// evaluated in f64 from the f32 mean / var and rounded to f32 once; num_batches_tracked (int64 [1]) += 1.
+struct Running {
+    float *mean, *var;
+    float momentum;
+    long long *batches;
+};
+
+// r + mom * (stat * unbias - r), every f64 operation rounded on its own (no contraction: the host restates it)
+__device__ __forceinline__ float running_update(float r, float stat, double unbias, double mom) {
+#pragma clang fp contract(off)
+    const double t = (double)stat * unbias;
+    const double d = t - (double)r;
+    const double p = mom * d;
+    return (float)((double)r + p);
+}
+
+// forward finish: mean / biased var / scale / shift per column, and the running statistics
 __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel(
     const double *__restrict__ partial, int nblocks, int C, long long M,
     const float *__restrict__ weight, const float *__restrict__ bias, float eps,
     float *__restrict__ mean, float *__restrict__ var, float *__restrict__ rstd,
     float *__restrict__ scale, float *__restrict__ shift, const float *__restrict__ mask, int n_rois, int per,
-    float *__restrict__ count) {
+    float *__restrict__ count, Running run) {
     __shared__ double red[FIN_GROUPS][FIN_COLS][2];
     const int grp = threadIdx.x / FIN_COLS;
     const int c = blockIdx.x * FIN_COLS + threadIdx.x % FIN_COLS;
     const double Mn = live_rows(mask, n_rois, per, M, &red[0][0][0]);
-    if (count && blockIdx.x == 0 && threadIdx.x == 0) count[0] = (float)Mn;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (count) count[0] = (float)Mn;
+        if (run.batches) run.batches[0] = run.batches[0] + 1;
+    }
     double s, q;
     finish_reduce(partial, nblocks, C, c, grp, red, s, q);
     if (grp != 0 || c >= C) return;
@@ -263,6 +286,9 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel
     rstd[c] = rs;
     scale[c] = scl;
     shift[c] = bias[c] - (float)mu * scl;
+    const double mom = (double)run.momentum;
+    if (run.mean) run.mean[c] = running_update(run.mean[c], (float)mu, 1.0, mom);
+    if (run.var) run.var[c] = running_update(run.var[c], (float)v, Mn / (Mn - 1.0 > 1.0 ? Mn - 1.0 : 1.0), mom);
 }
 
 // backward finish: dweight, dbias and the three coefficients of dx = a*g - k0 - k1*x
@@ -571,7 +597,7 @@ PLUMB_API int wsplumb_rowbn_supported(long long M, int C) { return shape_ok(M, C
 static int forward_impl(const float *x, long long M, int C, const float *weight, const float *bias, float eps,
                         int relu, float *y, float *mean, float *var, float *rstd, float *scale, float *shift,
                         const float *mask, int n_rois, int per, float *count, void *workspace,
-                        size_t workspace_bytes, void *stream, bool pm = false) {
+                        size_t workspace_bytes, void *stream, Running run, bool pm = false) {
     if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
     if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -589,7 +615,7 @@ static int forward_impl(const float *x, long long M, int C, const float *weight,
         hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 0>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
                            nullptr, nullptr, M, C, rpb, partial, nullptr, 1);
     hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st, partial, nb, C,
-                       M, weight, bias, eps, mean, var, rstd, scale, shift, mask, n_rois, per, count);
+                       M, weight, bias, eps, mean, var, rstd, scale, shift, mask, n_rois, per, count, run);
     const long long total4 = M * (C / 4);
 #define WSPLUMB_APPLY(RELU, MASK) \
     hipLaunchKernelGGL((rowbn_apply_fwd_kernel<RELU, MASK>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, scale, \
@@ -603,12 +629,17 @@ static int forward_impl(const float *x, long long M, int C, const float *weight,
 
 // y = act(batch_norm(x)); writes mean, var (biased), rstd, scale = rstd*weight,
 // shift = bias - mean*scale (all [C]).  Returns 0 on success.
+// running_mean / running_var (f32 [C]) and num_batches_tracked (int64 [1]) are the layer's buffers, updated
+// in place with `momentum` (struct Running); each may be null.  The same four close every forward entry point.
 PLUMB_API int wsplumb_rowbn_forward(const float *x, long long M, int C, const float *weight,
                                     const float *bias, float eps, int relu, float *y, float *mean,
                                     float *var, float *rstd, float *scale, float *shift,
-                                    void *workspace, size_t workspace_bytes, void *stream) {
+                                    void *workspace, size_t workspace_bytes, void *stream,
+                                    float *running_mean, float *running_var, float momentum,
+                                    long long *num_batches_tracked) {
     return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, nullptr, 0, 1, nullptr,
-                        workspace, workspace_bytes, stream);
+                        workspace, workspace_bytes, stream,
+                        Running{running_mean, running_var, momentum, num_batches_tracked});
 }
 
 // the same over the live rows only: mask [n_rois] f32 (0 = dead), rows r*per .. r*per+per-1 belong to
@@ -618,10 +649,13 @@ PLUMB_API int wsplumb_rowbn_forward_masked(const float *x, long long M, int C, c
                                            const float *bias, float eps, int relu, const float *mask,
                                            int n_rois, int per, float *y, float *mean, float *var,
                                            float *rstd, float *scale, float *shift, float *count,
-                                           void *workspace, size_t workspace_bytes, void *stream) {
+                                           void *workspace, size_t workspace_bytes, void *stream,
+                                           float *running_mean, float *running_var, float momentum,
+                                           long long *num_batches_tracked) {
     if (!mask || !count) return 1;
     return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, mask, n_rois, per, count,
-                        workspace, workspace_bytes, stream);
+                        workspace, workspace_bytes, stream,
+                        Running{running_mean, running_var, momentum, num_batches_tracked});
 }
 
 // y = act(x*scale + shift) with given per-column scale / shift (inference statistics)
@@ -696,10 +730,13 @@ PLUMB_API int wsplumb_rowbn_forward_masked_pm(const float *x, long long M, int C
                                               const float *bias, float eps, int relu, const float *mask,
                                               int n_rois, int per, float *y, float *mean, float *var,
                                               float *rstd, float *scale, float *shift, float *count,
-                                              void *workspace, size_t workspace_bytes, void *stream) {
+                                              void *workspace, size_t workspace_bytes, void *stream,
+                                              float *running_mean, float *running_var, float momentum,
+                                              long long *num_batches_tracked) {
     if (!mask || !count) return 1;
     return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, mask, n_rois, per, count,
-                        workspace, workspace_bytes, stream, true);
+                        workspace, workspace_bytes, stream,
+                        Running{running_mean, running_var, momentum, num_batches_tracked}, true);
 }
 
 // gradients of wsplumb_rowbn_forward_masked_pm
@@ -786,7 +823,7 @@ inline int join_geom(long long M, int C, const float *mask, int n_rois, int per,
 
 // statistics of x (no apply): partial sums into g.p0, then the finish kernel
 inline void join_stats(const JoinGeom &g, const float *x, long long M, int C, const float *weight, const float *bias,
-                       float eps, float *stats, const float *mask, int n_rois, int per, float *count) {
+                       float eps, float *stats, const float *mask, int n_rois, int per, float *count, Running run) {
     if (g.mode)
         hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 2>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, nullptr, nullptr,
                            nullptr, M, C, g.rpb, g.p0, mask, g.div);
@@ -795,7 +832,7 @@ inline void join_stats(const JoinGeom &g, const float *x, long long M, int C, co
                            nullptr, M, C, g.rpb, g.p0, nullptr, 1);
     hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
                        g.st, g.p0, g.nb, C, M, weight, bias, eps, stats, stats + C, stats + 2 * C, stats + 3 * C,
-                       stats + 4 * C, mask, n_rois, per, count);
+                       stats + 4 * C, mask, n_rois, per, count, run);
 }
 
 inline void join_bwd_finish(const JoinGeom &g, const double *partial, long long M, int C, const float *weight,
@@ -810,7 +847,10 @@ inline void join_bwd_finish(const JoinGeom &g, const double *partial, long long 
 //   other is the identity shortcut when weight_s is null, else the input xs of the shortcut's own norm
 //   (out = bn3(x3) + bn_s(xs); stats_s is written only then);
 //   stats3 / stats_s / stats_n [5, C] and count [1] are what wsplumb_rowbn_forward_masked_pm writes for the
-//   three layers (count: once, they share the mask; untouched without a mask).
+//   three layers (count: once, they share the mask; untouched without a mask);
+//   running [6] / momentum [3] / batches [3] (host arrays, or null): the running_mean, running_var pointers, the
+//   momentum and the num_batches_tracked pointer of bn3, bn_s, bn_n in that order (struct Running), each
+//   updated once, by the finish kernel that writes the layer's statistics.
 // Dead rows: out = other (identity form) or 0, y = 0.  Bit-identical to the three (four) separate calls and
 // the add between them.
 PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, long long M, int C,
@@ -819,14 +859,22 @@ PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, lo
                                          const float *weight_n, const float *bias_n, float eps_n,
                                          const float *mask, int n_rois, int per, float *out, float *y,
                                          float *stats3, float *stats_s, float *stats_n, float *count,
-                                         void *workspace, size_t workspace_bytes, void *stream) {
+                                         void *workspace, size_t workspace_bytes, void *stream,
+                                         float *const *running, const float *momentum,
+                                         long long *const *batches) {
     JoinGeom g;
     if (join_geom(M, C, mask, n_rois, per, workspace, workspace_bytes, stream, g)) return 1;
     if (mask && !count) return 1;
     const bool dual = weight_s != nullptr;
     if (dual && (!bias_s || !stats_s)) return 1;
-    join_stats(g, x3, M, C, weight3, bias3, eps3, stats3, mask, n_rois, per, nullptr);
-    if (dual) join_stats(g, other, M, C, weight_s, bias_s, eps_s, stats_s, mask, n_rois, per, nullptr);
+    Running run[3] = {};
+    for (int k = 0; k < 3; ++k) {
+        if (running) { run[k].mean = running[2 * k]; run[k].var = running[2 * k + 1]; }
+        if (momentum) run[k].momentum = momentum[k];
+        if (batches) run[k].batches = batches[k];
+    }
+    join_stats(g, x3, M, C, weight3, bias3, eps3, stats3, mask, n_rois, per, nullptr, run[0]);
+    if (dual) join_stats(g, other, M, C, weight_s, bias_s, eps_s, stats_s, mask, n_rois, per, nullptr, run[1]);
     const float *sco = dual ? stats_s + 3 * C : nullptr, *sho = dual ? stats_s + 4 * C : nullptr;
 #define WSPLUMB_JOIN(DUAL, MASK) \
     hipLaunchKernelGGL((rowbn_join_fwd_kernel<DUAL, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, x3, stats3 + 3 * C, \
@@ -836,7 +884,7 @@ PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, lo
 #undef WSPLUMB_JOIN
     hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
                        g.st, g.p0, g.nb, C, M, weight_n, bias_n, eps_n, stats_n, stats_n + C, stats_n + 2 * C,
-                       stats_n + 3 * C, stats_n + 4 * C, mask, n_rois, per, mask ? count : nullptr);
+                       stats_n + 3 * C, stats_n + 4 * C, mask, n_rois, per, mask ? count : nullptr, run[2]);
     if (g.mode)
         hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, out,
                            stats_n + 3 * C, stats_n + 4 * C, g.total4, C / 4, y, mask, g.div);

@@ -14,6 +14,7 @@ _lib = None
 _warned = [False]
 
 _vp, _i, _ll, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t
+_RUN = [_vp, _vp, _f, _vp]          # running_mean, running_var, momentum, num_batches_tracked (struct Running)
 
 
 def lib():
@@ -32,7 +33,7 @@ def lib():
         L.wsplumb_rowbn_supported.argtypes = [_ll, _i]
         L.wsplumb_rowbn_forward.restype = _i
         L.wsplumb_rowbn_forward.argtypes = [_vp, _ll, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _sz, _vp]
+                                            _vp, _sz, _vp] + _RUN
         L.wsplumb_rowbn_apply.restype = _i
         L.wsplumb_rowbn_apply.argtypes = [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp]
         L.wsplumb_rowbn_backward.restype = _i
@@ -40,7 +41,7 @@ def lib():
                                              _vp, _vp, _sz, _vp]
         L.wsplumb_rowbn_forward_masked.restype = _i
         L.wsplumb_rowbn_forward_masked.argtypes = [_vp, _ll, _i, _vp, _vp, _f, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
-                                                   _vp, _vp, _vp, _vp, _sz, _vp]
+                                                   _vp, _vp, _vp, _vp, _sz, _vp] + _RUN
         L.wsplumb_rowbn_backward_masked.restype = _i
         L.wsplumb_rowbn_backward_masked.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
                                                     _vp, _vp, _vp, _vp, _vp, _sz, _vp]
@@ -53,7 +54,7 @@ def lib():
         L.wsplumb_rowbn_join_workspace_bytes.argtypes = [_ll, _i]
         L.wsplumb_rowbn_join_forward.restype = _i
         L.wsplumb_rowbn_join_forward.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _f, _vp, _i, _i,
-                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]
         L.wsplumb_rowbn_join_backward.restype = _i
         L.wsplumb_rowbn_join_backward.argtypes = [_vp] * 5 + [_ll, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 8 + [_sz, _vp]
         L.wsplumb_tap_table_ints.restype = _i
@@ -92,15 +93,40 @@ def usable(x):
     return L is not None and bool(L.wsplumb_rowbn_supported(x.shape[0], x.shape[1]))
 
 
+def fused_running_stats():
+    """True when the forward finish kernel updates the layers' running statistics (rowbn.hip, struct Running);
+    WSSDL_BN_TORCH_RUNNING_STATS=1 (A/B switch) leaves them to torch's lerp_ as before."""
+    return not os.environ.get("WSSDL_BN_TORCH_RUNNING_STATS")
+
+
+def running_of(bn):
+    """The `running` argument of rowbn_forward / rowbn_join_forward for a norm module: (running_mean, running_var,
+    momentum, num_batches_tracked or None), or None when torch updates the buffers (fused_running_stats)."""
+    if not fused_running_stats():
+        return None
+    mom = bn.momentum if bn.momentum is not None else 0.1
+    return bn.running_mean, bn.running_var, mom, getattr(bn, "num_batches_tracked", None)
+
+
+def _run_args(running):
+    if running is None:
+        return None, None, 0.0, None
+    rm, rv, mom, nbt = running
+    assert rm.dtype == torch.float32 and rv.dtype == torch.float32 and rm.is_contiguous() and rv.is_contiguous()
+    assert nbt is None or (nbt.dtype == torch.int64 and nbt.numel() == 1)
+    return _p(rm), _p(rv), float(mom), _pn(nbt)
+
+
 def _workspace(L, M, C, dev):
     n = L.wsplumb_rowbn_workspace_bytes(M, C)
     return torch.empty((n,), dtype=torch.uint8, device=dev), n
 
 
-def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False):
+def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False, *, running=None):
     """mask: [n_rois] f32 on x's device (0 = dead RoI), x = [n_rois * per, C] with row r belonging to RoI
     r // per, or r % n_rois when pos_major; returns (y, stats, count) where count is None without a mask,
-    else a [1] tensor holding the number of live rows."""
+    else a [1] tensor holding the number of live rows.  running: the layer's buffers to update in the same
+    kernels (running_of), or None."""
     L = lib()
     M, C = x.shape
     dev = x.device
@@ -112,7 +138,7 @@ def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False):
         if mask is None:
             rc = L.wsplumb_rowbn_forward(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _p(y),
                                          _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]),
-                                         _p(stats[4]), _p(ws), n, _stream())
+                                         _p(stats[4]), _p(ws), n, _stream(), *_run_args(running))
         else:
             n_rois = mask.shape[0]
             assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
@@ -120,7 +146,7 @@ def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False):
             fn = L.wsplumb_rowbn_forward_masked_pm if pos_major else L.wsplumb_rowbn_forward_masked
             rc = fn(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _p(mask), n_rois, M // n_rois, _p(y),
                     _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _p(count), _p(ws), n,
-                    _stream())
+                    _stream(), *_run_args(running))
     if rc:
         raise RuntimeError("wsplumb_rowbn_forward failed (%d)" % rc)
     return y, stats, count
@@ -204,11 +230,11 @@ def _pn(t):
     return _p(t) if t is not None else None
 
 
-def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None):
+def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
     """out = bn3(x3) + (bns(other) if bns else other); y = relu(bnn(out)): training-mode row batch norms over
     position-major rows, each bn a (weight, bias, eps) triple, mask as in rowbn_forward(pos_major=True).
     Returns (out, y, stats3, stats_s, stats_n, count or None), stats_s unwritten without bns; bit-identical to the
-    separate calls."""
+    separate calls.  running: None, or the running_of() of bn3, bns (None without it) and bnn."""
     L = lib()
     M, C = x3.shape
     dev = x3.device
@@ -221,6 +247,13 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None):
         assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
         count = torch.empty((1,), dtype=torch.float32, device=dev)
     ws_, bs_, es_ = bns if bns is not None else (None, None, 0.0)
+    run_ptrs = run_mom = run_nbt = None
+    if running is not None:
+        a = [_run_args(r) for r in running]
+        val = lambda q: q.value if q is not None else None
+        run_ptrs = (_vp * 6)(*[val(q) for r in a for q in r[:2]])
+        run_mom = (_f * 3)(*[r[2] for r in a])
+        run_nbt = (_vp * 3)(*[val(r[3]) for r in a])
     with torch.cuda.device(dev):
         n = L.wsplumb_rowbn_join_workspace_bytes(M, C)
         ws = torch.empty((n,), dtype=torch.uint8, device=dev)
@@ -228,7 +261,7 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None):
                                           _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]), _pn(mask), n_rois,
                                           M // n_rois if n_rois else 1, _p(out), _p(y), _p(stats[0]),
                                           _p(stats[1]) if bns is not None else None, _p(stats[2]), _pn(count), _p(ws), n,
-                                          _stream())
+                                          _stream(), run_ptrs, run_mom, run_nbt)
     if rc:
         raise RuntimeError("wsplumb_rowbn_join_forward failed (%d)" % rc)
     return out, y, stats[0], stats[1], stats[2], count

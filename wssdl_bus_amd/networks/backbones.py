@@ -7,6 +7,7 @@ Tensors are NCHW-shaped in channels_last memory format, so ``x.permute(0, 2, 3, 
 contiguous NHWC view the hot-path ops take, with no copy.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -28,16 +29,23 @@ class BatchNormAct2d(nn.BatchNorm2d):
                 n, h, w, c = rows.shape
                 r2 = rows.reshape(-1, c)
                 if _plumbing.usable(r2):
-                    y, mean, var, _ = _FusedRowBatchNormFn.apply(r2, self.weight, self.bias, self.eps, bool(relu))
-                    with torch.no_grad():
-                        m = r2.shape[0]
-                        mom = self.momentum if self.momentum is not None else 0.1
-                        self.running_mean.lerp_(mean, mom)
-                        self.running_var.lerp_(var * (m / max(m - 1, 1)), mom)
-                        self.num_batches_tracked += 1
+                    # the forward kernels update the running statistics themselves (run is not None)
+                    run = _plumbing.running_of(self)
+                    y, mean, var, _ = _FusedRowBatchNormFn.apply(r2, self.weight, self.bias, self.eps, bool(relu),
+                                                                 None, False, run)
+                    if run is None:
+                        self._track(mean, var, r2.shape[0])
                     return y.view(n, h, w, c).permute(0, 3, 1, 2)
         y = super().forward(x)
         return F.relu(y) if relu else y
+
+    def _track(self, mean, var, m):
+        """running statistics from one batch's mean / biased variance over m rows, with torch ops."""
+        with torch.no_grad():
+            mom = self.momentum if self.momentum is not None else 0.1
+            self.running_mean.lerp_(mean, mom)
+            self.running_var.lerp_(var * (m / max(m - 1, 1)), mom)
+            self.num_batches_tracked += 1
 
 
 def _same_pad(size, k, s):
@@ -60,15 +68,72 @@ class Conv(nn.Module):
             nn.init.zeros_(self.conv.bias)
         self.bn = BatchNormAct2d(c_o, eps=1e-3, momentum=0.01) if norm == "BN" else None
 
-    def forward(self, x):
+    def forward(self, x, act=True):
+        """act=False: the convolution's raw output (its norm is applied by the block's join, _join)."""
         if self.padding == "SAME" and self.k > 1:
             pt, pb = _same_pad(x.shape[2], self.k, self.s)
             pl, pr = _same_pad(x.shape[3], self.k, self.s)
             x = F.pad(x, (pl, pr, pt, pb))
         x = self.conv(x)
+        return self._act(x) if act else x
+
+    def _act(self, x):
         if self.bn is not None:
             return self.bn(x, relu=self.relu)
         return F.relu(x) if self.relu else x
+
+
+def _rows(x):
+    """The [N*H*W, C] row matrix of an NCHW-shaped channels_last tensor (a view), or None."""
+    if x.dim() != 4:
+        return None
+    r = x.permute(0, 2, 3, 1)
+    return r.reshape(-1, r.shape[3]) if r.is_contiguous() else None
+
+
+def _join(last, x, short, ori, nxt):
+    """The end of a trunk block: last(x) + shortcut, `last` the block's final Conv (norm, no ReLU), the shortcut
+    `ori` itself or short(ori); then, when `nxt` is given, relu(nxt(out)) with the norm that follows the block.
+    Returns (out, relu(nxt(out))) from the residual-join kernels of csrc/plumbing/rowbn.hip (roi_head._JoinFn on
+    the [N*H*W, C] row views, no mask) when every norm involved is a training-mode BatchNormAct2d with running
+    statistics on a CUDA f32 channels_last tensor the kernels take and autograd is recording; else (out, None)
+    from the separate layers (also with WSSDL_TRUNK_UNFUSED_JOIN=1)."""
+    x3 = last(x, act=False)
+    xs = short(ori, act=False) if short is not None else ori
+    bns = [last.bn, nxt] + ([short.bn] if short is not None else [])
+    if (nxt is not None and not last.relu and torch.is_grad_enabled()
+            and not os.environ.get("WSSDL_TRUNK_UNFUSED_JOIN")
+            and all(isinstance(b, BatchNormAct2d) and b.training and b.track_running_stats for b in bns)
+            and xs.shape == x3.shape):
+        r3, rs = _rows(x3), _rows(xs)
+        from . import _plumbing
+        if r3 is not None and rs is not None and _plumbing.usable(r3) and _plumbing.usable(rs):
+            from .roi_head import _JoinFn
+            b3, bs = last.bn, short.bn if short is not None else None
+            run = None
+            if _plumbing.fused_running_stats():
+                run = (_plumbing.running_of(b3), _plumbing.running_of(bs) if bs is not None else None,
+                       _plumbing.running_of(nxt))
+            out, y, st3, sts, stn, _ = _JoinFn.apply(
+                r3, rs, b3.weight, b3.bias, bs.weight if bs is not None else None,
+                bs.bias if bs is not None else None, nxt.weight, nxt.bias, b3.eps, bs.eps if bs is not None else 0.0,
+                nxt.eps, None, run)
+            if run is None:
+                m = r3.shape[0]
+                b3._track(st3[0], st3[1], m)
+                if bs is not None:
+                    bs._track(sts[0], sts[1], m)
+                nxt._track(stn[0], stn[1], m)
+            n, c, h, w = x3.shape
+            return out.view(n, h, w, c).permute(0, 3, 1, 2), y.view(n, h, w, c).permute(0, 3, 1, 2)
+    return last._act(x3) + (short._act(xs) if short is not None else xs), None
+
+
+def _pre_act(blk, x, pre):
+    """A block's pre-activation: given by the previous block's join (pre), or computed here."""
+    if pre is not None:
+        return pre
+    return blk.pre_bn(x, relu=True) if blk.pre_bn is not None else F.relu(x)
 
 
 class Bottleneck(nn.Module):
@@ -85,15 +150,16 @@ class Bottleneck(nn.Module):
         self.conv3 = Conv(c_o, c_o * 4, 1, 1, norm, relu=False)
         self.short = Conv(c_i, c_o * 4, 1, s, norm, relu=False) if c_i != c_o * 4 else None
 
-    def forward(self, x):
+    def forward(self, x, pre=None, nxt=None):
+        """pre: this block's pre-activation when the previous block's join computed it; nxt: the norm (+ReLU)
+        that follows this block.  Returns (the block's output, nxt's output or None): _join."""
         ori = x
         if self.preact != "no_preact":
-            y = self.pre_bn(x, relu=True) if self.pre_bn is not None else F.relu(x)
+            y = _pre_act(self, x, pre)
             if self.preact == "both_preact":
                 ori = y
             x = y
-        x = self.conv3(self.conv2(self.conv1(x)))
-        return x + (self.short(ori) if self.short is not None else ori)
+        return _join(self.conv3, self.conv2(self.conv1(x)), self.short, ori, nxt)
 
 
 class BasicBlock(nn.Module):
@@ -109,15 +175,15 @@ class BasicBlock(nn.Module):
         self.conv2 = Conv(c_o, c_o, 3, 1, norm, relu=False)
         self.short = Conv(c_i, c_o, 1, s, norm, relu=False) if c_i != c_o else None
 
-    def forward(self, x):
+    def forward(self, x, pre=None, nxt=None):
+        """Bottleneck.forward for the basic block."""
         ori = x
         if self.preact != "no_preact":
-            y = self.pre_bn(x, relu=True) if self.pre_bn is not None else F.relu(x)
+            y = _pre_act(self, x, pre)
             if self.preact == "both_preact":
                 ori = y
             x = y
-        x = self.conv2(self.conv1(x))
-        return x + (self.short(ori) if self.short is not None else ori)
+        return _join(self.conv2, self.conv1(x), self.short, ori, nxt)
 
 
 def layer_group(block, c_i, c_o, count, s, norm, first=False):
@@ -126,6 +192,21 @@ def layer_group(block, c_i, c_o, count, s, norm, first=False):
     for _ in range(1, count):
         blocks.append(block(c_o * block.expansion, c_o, 1, "default", norm))
     return nn.Sequential(*blocks)
+
+
+def _walk(blocks, x, final, join=True):
+    """The blocks in order, each told (with `join`) the norm that follows it -- the next block's pre-activation
+    norm, or `final` after the last -- so that its join can apply it; returns final's output (with its ReLU)."""
+    pre = None
+    for i, blk in enumerate(blocks):
+        nxt = None
+        if join:
+            nxt = final if i + 1 == len(blocks) else \
+                (getattr(blocks[i + 1], "pre_bn", None) if blocks[i + 1].preact != "no_preact" else None)
+        x, pre = blk(x, pre, nxt)
+    if pre is None:
+        pre = final(x, relu=True) if final is not None else F.relu(x)
+    return pre
 
 
 RESNET_DEFS = {18: ([2, 2, 2, 2], BasicBlock), 34: ([3, 4, 6, 3], BasicBlock),
@@ -149,8 +230,7 @@ class ResNetTrunk(nn.Module):
     def forward(self, x):
         x = self.conv0(x)
         x = F.max_pool2d(x, 3, 2)                         # 'VALID'
-        x = self.group2(self.group1(self.group0(x)))
-        return self.norm(x, relu=True) if self.norm is not None else F.relu(x)
+        return _walk(list(self.group0) + list(self.group1) + list(self.group2), x, self.norm)
 
 
 class ResNetHead(nn.Module):
@@ -165,9 +245,7 @@ class ResNetHead(nn.Module):
         self.out_features = 512 * e
 
     def forward(self, x):
-        x = self.group3(x)
-        x = self.norm(x, relu=True) if self.norm is not None else F.relu(x)
-        return x.mean(dim=(2, 3))
+        return _walk(list(self.group3), x, self.norm, join=False).mean(dim=(2, 3))
 
 
 class VGGTrunk(nn.Module):

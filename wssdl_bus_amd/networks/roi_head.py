@@ -55,11 +55,12 @@ class _RowBatchNormFn(torch.autograd.Function):
 class _FusedRowBatchNormFn(torch.autograd.Function):
     """The same layer (optionally with its ReLU) on the fused HIP kernels of
     csrc/plumbing/rowbn.hip: 3 passes over the tensor forward, 5 backward, instead of 5 + 14
-    with separate elementwise ops; the ReLU mask is recomputed from x in the backward."""
+    with separate elementwise ops; the ReLU mask is recomputed from x in the backward.  `running`
+    (_plumbing.running_of: the layer's buffers, not autograd inputs) are updated by the forward kernels."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, relu, roi_mask=None, pos_major=False):
-        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask, pos_major)
+    def forward(ctx, x, weight, bias, eps, relu, roi_mask=None, pos_major=False, running=None):
+        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask, pos_major, running=running)
         ctx.masked, ctx.pos_major = roi_mask is not None, pos_major
         if ctx.masked:
             ctx.save_for_backward(x, weight, stats, roi_mask)
@@ -69,6 +70,7 @@ class _FusedRowBatchNormFn(torch.autograd.Function):
         ctx.relu = relu
         mean, var = stats[0], stats[1]
         ctx.mark_non_differentiable(mean, var, count)
+        ctx.set_materialize_grads(False)               # no zero-filled gradients for mean / var / count
         return y, mean, var, count
 
     @staticmethod
@@ -77,8 +79,10 @@ class _FusedRowBatchNormFn(torch.autograd.Function):
             x, weight, stats, roi_mask = ctx.saved_tensors
         else:
             (x, weight, stats), roi_mask = ctx.saved_tensors, None
+        if dy is None:
+            dy = torch.zeros_like(x)
         dx, dw, db = _plumbing.rowbn_backward(x, dy.contiguous(), weight, stats, ctx.relu, roi_mask, ctx.pos_major)
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
 class _JoinFn(torch.autograd.Function):
@@ -91,10 +95,10 @@ class _JoinFn(torch.autograd.Function):
     blocks (stats_s is not written in the identity form) and the live-row count."""
 
     @staticmethod
-    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask):
+    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask, running=None):
         dual = ws is not None
         out, y, st3, sts, stn, count = _plumbing.rowbn_join_forward(
-            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask)
+            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask, running=running)
         ctx.dual, ctx.masked = dual, roi_mask is not None
         ctx.save_for_backward(x3, other if dual else None, out, w3, ws, wn, st3, sts, stn, roi_mask)
         if count is None:
@@ -112,8 +116,8 @@ class _JoinFn(torch.autograd.Function):
             out, dy.contiguous(), dres.contiguous() if dres is not None else None, x3, xs, wn, stn, w3, st3, ws, sts,
             roi_mask)
         if ctx.dual:
-            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None
-        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None
+            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None, None
+        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None, None
 
 
 class _EntryNormFn(torch.autograd.Function):
@@ -124,8 +128,8 @@ class _EntryNormFn(torch.autograd.Function):
     add or contiguous copy of a [R, 49, C] tensor.  Bit-identical to the separate layers."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, roi_mask, plan, s, hw):
-        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, True, roi_mask, False)
+    def forward(ctx, x, weight, bias, eps, roi_mask, plan, s, hw, running=None):
+        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, True, roi_mask, False, running=running)
         h, w = hw
         r = x.shape[0] // (h * w)
         ys = _pm_rows(y.view(r, h, w, -1), plan, s)
@@ -135,16 +139,21 @@ class _EntryNormFn(torch.autograd.Function):
             count = stats[0, :1]                       # placeholder (unused without a mask)
         mean, var = stats[0], stats[1]
         ctx.mark_non_differentiable(mean, var, count)
+        ctx.set_materialize_grads(False)               # no zero-filled gradients for mean / var / count
         return y, ys, mean, var, count
 
     @staticmethod
     def backward(ctx, dy, dys, *_):
         x, weight, stats, roi_mask = ctx.saved_tensors
         plan, s, h, w = ctx.geom
+        if dy is None:
+            dy = torch.zeros_like(x)
+        if dys is None:
+            dys = x.new_zeros((len(plan.slots) * (x.shape[0] // (h * w)), x.shape[1]))
         dx, dw, db = _plumbing.rowbn_backward_entry(x, dy.contiguous(), dys.contiguous(),
                                                     plan.subsample_slots(h, w, s, x.device), len(plan.slots), weight,
                                                     stats, roi_mask)
-        return dx, dw, db, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None
 
 
 # The head can see RoI rows that are not live: the padding rows of the fixed-shape blob
@@ -200,10 +209,14 @@ class RowBatchNorm(nn.Module):
                 return _plumbing.rowbn_apply(x, scale.contiguous(), shift.contiguous(), relu)
             y = torch.addcmul(shift, x, scale)
             return F.relu(y) if relu else y
+        # on the fused route the forward kernels update the running statistics themselves (run is not None)
+        run = _plumbing.running_of(self) if fused else None
         if _ROI_MASK is not None:
             if fused and x.shape[0] % _ROI_MASK.shape[0] == 0:
                 y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), _ROI_MASK,
-                                                             bool(pos_major))
+                                                             bool(pos_major), run)
+                if run is not None:
+                    return y
                 n = n[0]
             else:
                 y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, _ROI_MASK,
@@ -211,7 +224,10 @@ class RowBatchNorm(nn.Module):
             self._track(mean, var, n)
             return y
         if fused:
-            y, mean, var, _ = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu))
+            y, mean, var, _ = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), None, False,
+                                                         run)
+            if run is not None:
+                return y
         else:
             y, mean, var = _RowBatchNormFn.apply(x, self.weight, self.bias, self.eps)
             if relu:
@@ -401,10 +417,15 @@ def _join_pm(last, x3, short, ori, plan, s, R, nxt):
             or (mask is not None and x3.shape[0] % mask.shape[0] != 0)):
         return last._act(x3, pos_major=True) + (short._act(xs, pos_major=True) if short is not None else xs), None
     b3, bs = last.bn, short.bn if short is not None else None
+    run = None
+    if _plumbing.fused_running_stats():
+        run = (_plumbing.running_of(b3), _plumbing.running_of(bs) if bs is not None else None, _plumbing.running_of(nxt))
     out, y, st3, sts, stn, n = _JoinFn.apply(
         x3, xs.contiguous(), b3.weight, b3.bias, bs.weight if bs is not None else None,
         bs.bias if bs is not None else None, nxt.weight, nxt.bias, b3.eps, bs.eps if bs is not None else 0.0, nxt.eps,
-        mask)
+        mask, run)
+    if run is not None:                                 # the join's finish kernels updated the running statistics
+        return out, y
     n = n[0] if mask is not None else x3.shape[0]
     b3._track(st3[0], st3[1], n)
     if bs is not None:
@@ -416,8 +437,11 @@ def _join_pm(last, x3, short, ori, plan, s, R, nxt):
 def _entry_pre_act(bn, x, plan, s):
     """Block 1's pre-activation through _EntryNormFn: (y roi-major [R, h, w, C], the shortcut's position-major rows)."""
     r, h, w, c = x.shape
-    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, _ROI_MASK, plan, s, (h, w))
-    bn._track(mean, var, n[0] if _ROI_MASK is not None else r * h * w)
+    run = _plumbing.running_of(bn)
+    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, _ROI_MASK, plan, s, (h, w),
+                                             run)
+    if run is None:
+        bn._track(mean, var, n[0] if _ROI_MASK is not None else r * h * w)
     return y.view(r, h, w, c), ys
 
 
