@@ -610,6 +610,63 @@ WSSDL_API int wssdl_post_detections_batched(const float *rois, const float *scor
                      int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
                      wssdl_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation ---
+ * Detection evaluation, datasets/voc_eval_bus.py + the 44 calls of datasets/bus.py:_do_python_eval in one pass:
+ * for every class j = 1 .. n_classes-1 the PASCAL VOC precision / recall curve and AP (11-point and area), and for
+ * every one of T score thresholds the CorLoc count nok and the FROC count num_all_fps.  One overlap pass (f64, the
+ * operation order of voc_eval_bus.py:221-236, first maximum like np.argmax), one sort, one first-hit-per-box pass
+ * and one prefix sum.  No allocation, no read-back, no host synchronisation: capturable like the other entry points.
+ *
+ * flags
+ *   WSSDL_EVAL_QUANTISE  evaluate what the reference wrote to its result file (bus.py:257-261): the score as
+ *          '{:.3f}' -- conf = rint(double(s) * 1000.0) / 1000.0 -- and every coordinate as '{:.1f}' of the f32 value
+ *          x + 1 -- rint(double(x +f32 1.0f) * 10.0) / 10.0; both reproduce the parsed doubles exactly (the products
+ *          are exact in f64, rint rounds half to even like the correctly rounded formatting, the division is the
+ *          decimal parse).  The ground truth then holds the annotation's 1-based pixel values as they stand.
+ *          Without the flag the f32 values are used as they are, no + 1 on either side.
+ *   WSSDL_EVAL_BATCHED   the detections are the (dets, counts) pair wssdl_post_detections_batched wrote:
+ *          dets [N, n_classes-1, P, 5] f32, counts [N, n_classes-1] i32 (a count < 0 reads as 0); batch image i is
+ *          image first_image + i.  Input index of a slot = ((i * (n_classes-1) + j-1) * P + p); D is ignored and the
+ *          outputs sized by D below are sized by N * (n_classes-1) * P.
+ *          Without the flag: det_boxes [D,4] f32, det_scores [D] f32, det_image [D] i32, det_class [D] i32 in
+ *          1 .. n_classes-1.  A detection whose image is outside 0 .. n_images-1 or whose class is outside
+ *          1 .. n_classes-1 is ignored.  The pointers of the layout that is not used may be NULL.
+ * Ground truth: gt_boxes [G,4] f64, gt_class [G] i32, gt_difficult [G] u8, gt_image_offsets [n_images+1] i32 (the
+ * boxes of image i are rows gt_image_offsets[i] .. gt_image_offsets[i+1]-1).
+ *
+ * Order: per class, descending confidence; detections of equal confidence keep their INPUT order (image index,
+ * then rank within the image) -- the stable sort of the result file's lines.  The reference's
+ * np.argsort(-confidence) is an unstable introsort: its order among equal scores, and every curve value that depends
+ * on it, is an accident of NumPy; with pairwise distinct (quantised) scores the two agree bit for bit.
+ *
+ * Outputs (device):
+ *   order [D] i32          input indices, class 1's detections first (best first), then class 2's, ...; -1 past the end
+ *   class_offsets [n_classes] i32   class j's segment of order / tp / fp / rec / prec is [class_offsets[j-1], class_offsets[j])
+ *   tp, fp [D] i32         cumulative counts along the class's segment (integer-exact)
+ *   rec, prec [D] f64      tp / double(npos), tp / max(tp + fp, DBL_EPSILON)
+ *   ap07, ap_area [n_classes-1] f64   voc_ap with use_07_metric True (bit-equal: p / 11. accumulated in the
+ *                          reference's order by one thread) and False; -1 for a class without detections (the
+ *                          reference's sentinel for an empty result file; its tp / fp / nok / num_all_fps are 0)
+ *   npos, ni [n_classes-1] i32   non-difficult boxes of the class; images with a box of the class (0 is reported as
+ *                          0: the caller decides what CorLoc means then, the reference divides by zero)
+ *   nok, num_all_fps [n_classes-1, T] i32   for thresholds [T] f64 (device), `conf >= t`
+ *   arr_ok [n_classes-1, n_images] u8, num_fp_per_img [n_classes-1, n_images] i32   at thresholds[base_threshold]
+ * D == 0 and G == 0 are valid.  WSSDL_ERR_INVALID_ARGUMENT: negative sizes, T < 1, n_classes < 2 or > 65, more than
+ * 2^24 detections (slots), base_threshold outside 0 .. T-1, a missing pointer, a workspace smaller than
+ * wssdl_eval_detections_workspace_bytes(D or N * (n_classes-1) * P, G, n_images, n_classes) (pure host; 0 for
+ * sizes the op rejects). */
+#define WSSDL_EVAL_QUANTISE 1
+#define WSSDL_EVAL_BATCHED 2
+WSSDL_API size_t wssdl_eval_detections_workspace_bytes(int64_t D, int G, int n_images, int n_classes);
+WSSDL_API int wssdl_eval_detections(int flags, const float *det_boxes, const float *det_scores, const int32_t *det_image,
+                     const int32_t *det_class, int D, const float *dets, const int32_t *counts, int N, int P,
+                     int first_image, const double *gt_boxes, const int32_t *gt_class, const uint8_t *gt_difficult,
+                     const int32_t *gt_image_offsets, int G, int n_images, int n_classes, double ovthresh,
+                     const double *thresholds, int T, int base_threshold, int32_t *order, int32_t *class_offsets,
+                     int32_t *tp, int32_t *fp, double *rec, double *prec, double *ap07, double *ap_area, int32_t *npos,
+                     int32_t *ni, int32_t *nok, int32_t *num_all_fps, uint8_t *arr_ok, int32_t *num_fp_per_img,
+                     void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,38 @@
+"""Batched validation: detect N images per forward and score the detections where they are (the validation pass of
+reference code/lib/fast_rcnn/train_bus.py:485-534 / :850-899 and test_net's evaluate_detections, without result
+files): get_test_blobs -> im_detect_batch -> post_detections_batched_device -> DetectionAccumulator -> one
+evaluation op.  No detection is read back; the summary is."""
+from ..datasets.voc_eval_bus import DetectionAccumulator, evaluate_detections
+from .detect_batch import get_test_blobs, im_detect_batch, post_detections_batched_device
+
+
+def accumulate_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_image=300):
+    """The detections of `planes` at `batch_size` images per forward, kept on the GPU: a DetectionAccumulator."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    acc = None
+    for b0 in range(0, len(planes), batch_size):
+        data, info = get_test_blobs(planes[b0:b0 + batch_size], net_name)
+        scores, boxes, rois = im_detect_batch(net, data, info)
+        K = int(scores.shape[1])
+        if acc is None:
+            acc = DetectionAccumulator(K)
+        dets, counts = post_detections_batched_device(scores, boxes, rois, data.shape[0], K, thresh, max_per_image)
+        acc.add(dets, counts, b0)
+    return acc
+
+
+def evaluate_images(net, planes, gt_roidb, net_name, batch_size=8, classes=None, thresh=0.05, max_per_image=300,
+                    ovthresh=0.5, score_thresh=0.5, use_07_metric=True):
+    """evaluate_detections (datasets/voc_eval_bus.py) of the network's detections on `planes` against gt_roidb
+    (one entry per plane).  classes: the class names, '__background__' first (default: numbered)."""
+    if len(planes) != len(gt_roidb):
+        raise ValueError("one gt_roidb entry per image")
+    acc = accumulate_images(net, planes, net_name, batch_size, thresh, max_per_image)
+    if acc is None:
+        raise ValueError("evaluate_images needs at least one image")
+    if classes is None:
+        classes = ['__background__'] + ['class_%d' % j for j in range(1, acc.num_classes)]
+    if len(classes) != acc.num_classes:
+        raise ValueError("the network scores %d classes, `classes` names %d" % (acc.num_classes, len(classes)))
+    return evaluate_detections(acc, gt_roidb, classes, ovthresh, score_thresh, use_07_metric)
