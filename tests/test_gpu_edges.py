@@ -536,6 +536,76 @@ def test_fused_row_batchnorm_matches_torch_ops(torch_cuda):
     assert not _plumbing.usable(torch.zeros((10, 96), device="cuda"))
 
 
+def test_rowbn_exports_reject_bad_arguments_before_any_launch(torch_cuda):
+    """The merged exports of csrc/plumbing/rowbn.hip through ctypes at M = 8, C = 16: every bad call returns non-zero
+    and leaves its sentinel-filled outputs as they were (every buffer has its full size, so nothing could be written
+    out of bounds even by a call that wrongly went ahead)."""
+    import torch
+    from wssdl_bus_amd.networks import _plumbing as P
+    L = P.lib()
+    M, C, SENT = 8, 16, -77.0
+    x, dy = torch.randn((M, C), device="cuda"), torch.randn((M, C), device="cuda")
+    w, b = torch.ones((C,), device="cuda"), torch.zeros((C,), device="cuda")
+    mask = torch.ones((M,), device="cuda")                 # room for any n_rois <= M
+    n = L.wsplumb_rowbn_workspace_bytes(M, C)
+    assert n > 0
+    ws = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    sent = lambda *shape: torch.full(shape, SENT, device="cuda")
+    stats = torch.randn((5, C), device="cuda")
+    p, run = P._p, (None, None, 0.0, None)
+    stream = P._stream()
+
+    def forward(mask_, n_rois, per, pm, with_count=True, nbytes=n):
+        outs = [sent(M, C), sent(5, C), sent(1)]
+        y, st, count = outs
+        rc = L.wsplumb_rowbn_forward(p(x), M, C, p(w), p(b), 1e-3, 1, P._pn(mask_), n_rois, per, pm, p(y), p(st[0]), p(st[1]),
+                                     p(st[2]), p(st[3]), p(st[4]), p(count) if with_count else None, p(ws), nbytes, stream,
+                                     *run)
+        return rc, outs
+
+    def backward(mask_, n_rois, per, pm, nbytes=n):
+        outs = [sent(M, C), sent(2, C), sent(3, C)]
+        dx, dwb, coef = outs
+        rc = L.wsplumb_rowbn_backward(p(x), p(dy), M, C, p(w), p(stats[0]), p(stats[2]), p(stats[3]), p(stats[4]), 1,
+                                      P._pn(mask_), n_rois, per, pm, p(dx), p(dwb[0]), p(dwb[1]), p(coef), p(ws), nbytes,
+                                      stream)
+        return rc, outs
+
+    def entry(n_slots, per, nbytes=n):
+        n_rois = M // per
+        dys = torch.randn((max(n_slots, 1) * n_rois, C), device="cuda")
+        possel = torch.full((per,), -1, dtype=torch.int32, device="cuda")
+        outs = [sent(M, C), sent(2, C), sent(3, C)]
+        dx, dwb, coef = outs
+        rc = L.wsplumb_rowbn_backward_entry(p(x), p(dy), p(dys), p(possel), n_slots, M, C, p(w), p(stats[0]), p(stats[2]),
+                                            p(stats[3]), p(stats[4]), None, n_rois, per, p(dx), p(dwb[0]), p(dwb[1]),
+                                            p(coef), p(ws), nbytes, stream)
+        return rc, outs
+
+    cases = {
+        "forward: pos_major without a mask": forward(None, 4, 2, 1),
+        "backward: pos_major without a mask": backward(None, 4, 2, 1),
+        "forward: n_rois * per != M": forward(mask, 3, 2, 0),
+        "forward: n_rois * per != M, pos_major": forward(mask, 3, 2, 1),
+        "backward: n_rois * per != M": backward(mask, 3, 2, 0),
+        "backward: n_rois * per != M, pos_major": backward(mask, 3, 2, 1),
+        "forward: mask without count": forward(mask, 4, 2, 0, with_count=False),
+        "forward: workspace one byte short": forward(None, 0, 1, 0, nbytes=n - 1),
+        "backward: workspace one byte short": backward(None, 0, 1, 0, nbytes=n - 1),
+        "entry: workspace one byte short": entry(1, 2, nbytes=n - 1),
+        "entry: n_slots > per": entry(3, 2),
+    }
+    torch.cuda.synchronize()
+    for name, (rc, outs) in cases.items():
+        assert rc != 0, name
+        assert all(bool((t == SENT).all()) for t in outs), name
+    # the same calls with good arguments go through (the rejections above are not a dead library)
+    for name, (rc, outs) in {"forward": forward(mask, 4, 2, 1), "backward": backward(mask, 4, 2, 0),
+                             "entry": entry(2, 2)}.items():
+        torch.cuda.synchronize()
+        assert rc == 0 and not bool((outs[0] == SENT).any()), name
+
+
 def test_fused_batchnorm2d_channels_last_matches_stock(torch_cuda):
     import torch
     from wssdl_bus_amd.networks.backbones import BatchNormAct2d

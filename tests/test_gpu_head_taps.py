@@ -162,8 +162,8 @@ def _close(torch, a, b, rel=1e-4):
 
 
 def test_position_major_masked_batch_norm(torch_cuda):
-    """wsplumb_rowbn_*_masked_pm on position-major rows = the roi-major masked entry points on the same
-    rows reordered (same statistics, same outputs and gradients)."""
+    """wsplumb_rowbn_forward / _backward with a mask and pos_major on position-major rows = the same exports
+    without pos_major on the same rows reordered (same statistics, same outputs and gradients)."""
     torch = torch_cuda
     from wssdl_bus_amd.networks import _plumbing
     g = torch.Generator(device="cuda").manual_seed(5)

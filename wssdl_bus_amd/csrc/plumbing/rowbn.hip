@@ -10,16 +10,17 @@
 // Column sums are accumulated in f64 per thread, reduced in a fixed order (partials per
 // workgroup, then one thread per column): results do not depend on scheduling.
 //
-// LIVE-ROW MASK (the *_masked entry points).  The rows come in groups of `per` (the h*w positions of
+// LIVE-ROW MASK (the `mask` argument of the entry points).  The rows come in groups of `per` (the h*w positions of
 // one RoI); `mask[roi]` = 0 marks a dead RoI -- a padding row of the fixed-shape RoI blob, or of a
 // supervised image that ran short of candidates.  Dead rows are skipped by the column sums (not even
 // loaded), the statistics are taken over the live rows (n = per * sum(mask), computed on the device:
 // no host read-back), and the layer writes zeros for dead rows in both directions, so the live rows
 // come out exactly as if the blob had been compacted first.
-// The *_masked_pm entry points take the same mask on POSITION-MAJOR rows (row r belongs to RoI
-// r % n_rois: the head's 4x4 section, networks/roi_head.py); statistics and outputs are the same.
+// With `pos_major` the same mask applies to POSITION-MAJOR rows (row r belongs to RoI r % n_rois: the
+// head's 4x4 section, networks/roi_head.py); statistics and outputs are the same.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define PLUMB_API extern "C" __attribute__((visibility("default")))
 
@@ -47,16 +48,70 @@ __device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return
 __device__ __forceinline__ float bn_dx(float ka, float u, float k0, float k1, float x) {
     return __builtin_fmaf(-k1, x, __builtin_fmaf(ka, u, -k0));
 }
-// the f64 column sums of a thread: two rows per step, then a one-row tail
+// The f64 column sums of a thread: two rows per step, then a one-row tail.  Written out as well, in the form the
+// compiler's contraction gave every slab kernel before (4 multiplies + 8 fused multiply-adds per float4 column):
+//   two rows: q += fma(v0, w0, v1 * w1)        one row: q = fma(v, w, q)
+// (The product of two f32 values is exact in f64, so either form rounds as the separate operations would; what is
+// pinned is that every instantiation issues the same operations.)
+__device__ __forceinline__ void dot_rows2(double &q, float v0, float w0, float v1, float w1) {
+#pragma clang fp contract(off)
+    const double p1 = (double)v1 * (double)w1;
+    q += __builtin_fma((double)v0, (double)w0, p1);
+}
+__device__ __forceinline__ void dot_row(double &q, float v, float w) { q = __builtin_fma((double)v, (double)w, q); }
 __device__ __forceinline__ void acc_rows2(double &s, double &q, float v0, float w0, float v1, float w1) {
     s += (double)v0 + (double)v1;
-    q += (double)v0 * (double)w0 + (double)v1 * (double)w1;
+    dot_rows2(q, v0, w0, v1, w1);
 }
 __device__ __forceinline__ void acc_row(double &s, double &q, float v, float w) {
     s += (double)v;
-    q += (double)v * (double)w;
+    dot_row(q, v, w);
 }
 
+// ---- how a slab kernel reads and writes a row: float4 column c4 of row r ----
+template <int MASK>
+__device__ __forceinline__ bool row_live(const float *__restrict__ mask, long long r, int div) {
+    return MASK ? mask[mask_roi<MASK>(r, div)] != 0.0f : true;
+}
+
+// zeros, and no load, unless `on`
+__device__ __forceinline__ float4v load4(const float *__restrict__ p, long long r, int C, int c4, bool on) {
+    const float4v zero4 = {0, 0, 0, 0};
+    return on ? reinterpret_cast<const float4v *>(p + (size_t)r * C)[c4] : zero4;
+}
+
+__device__ __forceinline__ void store4(float *__restrict__ p, long long r, int C, int c4, float4v v) {
+    reinterpret_cast<float4v *>(p + (size_t)r * C)[c4] = v;
+}
+
+// ---- block 1's entry gradient (networks/roi_head.py, _EntryNormFn) ----
+// Block 1's pre-activation output y (roi-major rows, `per` positions per RoI) feeds conv1 at every position and
+// the projection shortcut at the positions it samples.  Its gradient at row r = roi * per + p is
+//   dy[r] + (possel[p] >= 0 ? dys[possel[p] * R + roi] + 0 : 0)
+// with dy conv1's gradient, dys the shortcut's position-major gradient and possel[p] the shortcut's slot of
+// position p (-1: not sampled).  The ENTRY variants of the two backward kernels form it in registers.  The
+// "+ 0" is kept: the separate ops scatter dys into a zero tensor first, which turns a -0 into +0.
+struct EntryGrad {
+    const float *dys;       // [n_slots * R, C]
+    const int *possel;      // [per]
+    int per, R;
+};
+
+template <bool ENTRY>
+__device__ __forceinline__ float4v load_dy(const float *__restrict__ dy, const EntryGrad &e, long long r, int C, int c4,
+                                           bool on = true) {
+    const float4v zero4 = {0, 0, 0, 0};
+    if (!on) return zero4;
+    const float4v g = reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4];
+    if (!ENTRY) return g;
+    const unsigned roi = (unsigned)r / (unsigned)e.per, p = (unsigned)r - roi * (unsigned)e.per;
+    const int slot = e.possel[p];
+    float4v d = zero4;
+    if (slot >= 0) d = reinterpret_cast<const float4v *>(e.dys + ((size_t)slot * e.R + roi) * C)[c4] + zero4;
+    return g + d;
+}
+
+// ---- row slabs ----
 // Thread t of a slab kernel owns float4 column (t % L) + cc * L and the rows r0 + t / L + k * RS;
 // L = min(C/4, 256), RS = 256 / L.
 struct Slab {
@@ -92,35 +147,105 @@ __device__ __forceinline__ void slab_reduce(const Slab &b, int C, int c4, const 
     }
 }
 
-// ---- block 1's entry gradient (networks/roi_head.py, _EntryNormFn) ----
-// Block 1's pre-activation output y (roi-major rows, `per` positions per RoI) feeds conv1 at every position and
-// the projection shortcut at the positions it samples.  Its gradient at row r = roi * per + p is
-//   dy[r] + (possel[p] >= 0 ? dys[possel[p] * R + roi] + 0 : 0)
-// with dy conv1's gradient, dys the shortcut's position-major gradient and possel[p] the shortcut's slot of
-// position p (-1: not sampled).  The ENTRY variants of the two backward kernels form it in registers.  The
-// "+ 0" is kept: the separate ops scatter dys into a zero tensor first, which turns a -0 into +0.
-struct EntryGrad {
-    const float *dys;       // [n_slots * R, C]
-    const int *possel;      // [per]
-    int per, R;
+// What one row adds to the sums of its float4 column: s += v, q += v * w and, for a functor with TWO_Q, q2 += v * w2.
+struct Term {
+    float4v v, w, w2;
 };
 
-template <bool ENTRY>
-__device__ __forceinline__ float4v load_dy(const float *__restrict__ dy, const EntryGrad &e, long long r, int C, int c4) {
-    const float4v g = reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4];
-    if (!ENTRY) return g;
-    const unsigned roi = (unsigned)r / (unsigned)e.per, p = (unsigned)r - roi * (unsigned)e.per;
-    const int slot = e.possel[p];
-    const float4v zero4 = {0, 0, 0, 0};
-    float4v d = zero4;
-    if (slot >= 0) d = reinterpret_cast<const float4v *>(e.dys + ((size_t)slot * e.R + roi) * C)[c4] + zero4;
-    return g + d;
+// THE walk of a row slab, shared by rowbn_partial_kernel and rowbn_join_bwd_kernel (rowbn_join_fwd_kernel keeps a
+// hand-written copy of it, see there: a change to the walk has to be made in both): column chunk by column chunk,
+// two rows in flight per step and a one-row tail, the f64 sums of the live rows in the one association of acc_rows2 /
+// acc_row, then the fixed-order reduction into this block's partials (out; out2 takes (s, q2) with TWO_Q).  A kernel
+// supplies its columns as a functor F:
+//   f.setup(c4)                      per column chunk: its per-column constants
+//   f.load(r, c4, live) -> F::Row    the row's loads, nothing else (a dead row loads nothing from a masked operand)
+//   f.finish(row, r, c4, live)       the element arithmetic and any store; returns the row's Term
+//   F::VISITS_DEAD                   false: the kernel writes nothing per row, dead rows are skipped unloaded (a pair
+//                                    when both are dead); true: every row is finished, a dead row must still be stored
+//   F::TWO_Q                         a second product sum over the same v (the dual backward join)
+// Both rows of a pair are loaded before either is finished.  A dead row adds nothing: in a pair its term counts as
+// v = w = 0 (so the pair's operations stay those of two rows), the tail leaves it out.  The kernels that go through
+// here leave exactly the partials rowbn_partial_kernel would compute from the same v and w because they share this
+// walk; the forward join's copy is held to it by the bit-for-bit join tests (tests/test_gpu_head_join.py).
+template <int MASK, class F>
+__device__ __forceinline__ void slab_walk(const Slab &b, int C, const float *__restrict__ mask, int div, F &f,
+                                          double (*red)[8], double *__restrict__ out,
+                                          double *__restrict__ out2 = nullptr) {
+    const int RS = b.RS;
+    for (int cc = 0; cc * b.L < b.C4; ++cc) {
+        const int c4 = cc * b.L + b.lc;
+        double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, q2[4] = {0, 0, 0, 0};
+        f.setup(c4);
+        if (b.lr < RS) {
+            long long r = b.r0 + b.lr;
+#pragma unroll 1
+            for (; r + RS < b.r1; r += 2 * RS) {
+                const bool live0 = row_live<MASK>(mask, r, div), live1 = row_live<MASK>(mask, r + RS, div);
+                if (!F::VISITS_DEAD && !live0 && !live1) continue;
+                const typename F::Row a0 = f.load(r, c4, live0), a1 = f.load(r + RS, c4, live1);
+                const Term t0 = f.finish(a0, r, c4, live0), t1 = f.finish(a1, r + RS, c4, live1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float v0 = live0 ? t0.v[j] : 0.0f, v1 = live1 ? t1.v[j] : 0.0f;
+                    acc_rows2(s[j], q[j], v0, live0 ? t0.w[j] : 0.0f, v1, live1 ? t1.w[j] : 0.0f);
+                    if (F::TWO_Q) dot_rows2(q2[j], v0, live0 ? t0.w2[j] : 0.0f, v1, live1 ? t1.w2[j] : 0.0f);
+                }
+            }
+            for (; r < b.r1; r += RS) {
+                const bool live = row_live<MASK>(mask, r, div);
+                if (!F::VISITS_DEAD && !live) continue;
+                const Term t = f.finish(f.load(r, c4, live), r, c4, live);
+                if (live) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        acc_row(s[j], q[j], t.v[j], t.w[j]);
+                        if (F::TWO_Q) dot_row(q2[j], t.v[j], t.w2[j]);
+                    }
+                }
+            }
+        }
+        slab_reduce(b, C, c4, s, q, red, out);
+        if (F::TWO_Q) slab_reduce(b, C, c4, s, q2, red, out2);
+    }
 }
 
-// Partial column sums of one row slab (thread mapping: Slab).
+// Partial column sums of one row slab.
 // MODE 0: s = sum x,  q = sum x*x
 // MODE 1: s = sum g,  q = sum g*x   with g = dy, masked by (x*scale + shift > 0) when RELU
 // ENTRY: dy is block 1's entry gradient (EntryGrad; MODE 1, roi-major rows, M < 2^31)
+template <int MODE, bool RELU, bool ENTRY>
+struct PartialCols {
+    static constexpr bool VISITS_DEAD = false, TWO_Q = false;
+    const float *x, *dy, *scale, *shift;
+    int C;
+    EntryGrad eg;
+    float4v sc, sh;
+    struct Row {
+        float4v a, g;
+    };
+    __device__ __forceinline__ void setup(int c4) {
+        if (MODE == 1 && RELU) {
+            sc = reinterpret_cast<const float4v *>(scale)[c4];
+            sh = reinterpret_cast<const float4v *>(shift)[c4];
+        }
+    }
+    __device__ __forceinline__ Row load(long long r, int c4, bool live) const {
+        Row w = {load4(x, r, C, c4, live), {0, 0, 0, 0}};
+        if (MODE == 1) w.g = load_dy<ENTRY>(dy, eg, r, C, c4, live);
+        return w;
+    }
+    __device__ __forceinline__ Term finish(const Row &w, long long, int, bool) const {
+        Term t = {w.a, w.a, {0, 0, 0, 0}};
+        if (MODE == 1) {
+            t.v = w.g;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (RELU && !(bn_affine(w.a[j], sc[j], sh[j]) > 0.0f)) t.v[j] = 0.0f;
+        }
+        return t;
+    }
+};
+
 template <int MODE, bool RELU, int MASK, bool ENTRY = false>
 __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ scale,
@@ -128,72 +253,8 @@ __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
     double *__restrict__ partial, const float *__restrict__ mask, int per, EntryGrad eg = EntryGrad()) {
     __shared__ double red[BLOCK][8];
     const Slab b(M, C, rows_per_block);
-    const int C4 = b.C4, L = b.L, RS = b.RS, lc = b.lc, lr = b.lr;
-    const long long r0 = b.r0, r1 = b.r1;
-    double *out = partial + (size_t)blockIdx.x * 2 * C;
-    for (int cc = 0; cc * L < C4; ++cc) {
-        const int c4 = cc * L + lc;
-        double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-        float4v sc = {0, 0, 0, 0}, sh = {0, 0, 0, 0};
-        if (MODE == 1 && RELU) {
-            sc = reinterpret_cast<const float4v *>(scale)[c4];
-            sh = reinterpret_cast<const float4v *>(shift)[c4];
-        }
-        if (lr < RS) {
-            long long r = r0 + lr;
-            // two rows in flight per step
-            for (; r + RS < r1; r += 2 * RS) {
-                bool live0 = true, live1 = true;
-                if (MASK) {
-                    live0 = mask[mask_roi<MASK>(r, per)] != 0.0f;
-                    live1 = mask[mask_roi<MASK>(r + RS, per)] != 0.0f;
-                    if (!live0 && !live1) continue;
-                }
-                const float4v zero4 = {0, 0, 0, 0};
-                const float4v a0 = live0 ? reinterpret_cast<const float4v *>(x + (size_t)r * C)[c4] : zero4;
-                const float4v a1 = live1 ? reinterpret_cast<const float4v *>(x + (size_t)(r + RS) * C)[c4] : zero4;
-                float4v g0, g1;
-                if (MODE == 1) {
-                    g0 = live0 ? load_dy<ENTRY>(dy, eg, r, C, c4) : zero4;
-                    g1 = live1 ? load_dy<ENTRY>(dy, eg, r + RS, C, c4) : zero4;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (MODE == 0) {
-                        acc_rows2(s[j], q[j], a0[j], a0[j], a1[j], a1[j]);
-                    } else {
-                        float u0 = g0[j], u1 = g1[j];
-                        if (RELU) {
-                            if (!(bn_affine(a0[j], sc[j], sh[j]) > 0.0f)) u0 = 0.0f;
-                            if (!(bn_affine(a1[j], sc[j], sh[j]) > 0.0f)) u1 = 0.0f;
-                        }
-                        if (MASK) {                 // a dead row adds nothing (x = 0 would still pass the ReLU test)
-                            if (!live0) u0 = 0.0f;
-                            if (!live1) u1 = 0.0f;
-                        }
-                        acc_rows2(s[j], q[j], u0, a0[j], u1, a1[j]);
-                    }
-                }
-            }
-            for (; r < r1; r += RS) {
-                if (MASK && mask[mask_roi<MASK>(r, per)] == 0.0f) continue;
-                const float4v a0 = reinterpret_cast<const float4v *>(x + (size_t)r * C)[c4];
-                float4v g0;
-                if (MODE == 1) g0 = load_dy<ENTRY>(dy, eg, r, C, c4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (MODE == 0) {
-                        acc_row(s[j], q[j], a0[j], a0[j]);
-                    } else {
-                        float u0 = g0[j];
-                        if (RELU && !(bn_affine(a0[j], sc[j], sh[j]) > 0.0f)) u0 = 0.0f;
-                        acc_row(s[j], q[j], u0, a0[j]);
-                    }
-                }
-            }
-        }
-        slab_reduce(b, C, c4, s, q, red, out);
-    }
+    PartialCols<MODE, RELU, ENTRY> f = {x, dy, scale, shift, C, eg};
+    slab_walk<MASK>(b, C, mask, per, f, red, partial + (size_t)blockIdx.x * 2 * C);
 }
 
 // Sum of the per-workgroup partials of 16 columns, in a fixed order: 64 row groups of 16 lanes
@@ -380,23 +441,27 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
 // ---- residual joins of the head's position-major section (networks/roi_head.py, _JoinFn) ----
 // A join is the end of a block: out = bn3(x3) + other, where other is the identity shortcut (a plain
 // tensor) or, with DUAL, the projection shortcut's own batch norm of xs; the next block's pre-activation
-// norm (or the head's final norm) then takes its statistics over out.  Both join kernels walk row slabs
-// exactly as rowbn_partial_kernel does (Slab, acc_rows2 / acc_row, slab_reduce), so the f64 partials
-// they leave are those that kernel would compute from the tensor they write.
+// norm (or the head's final norm) then takes its statistics over out.  Both join kernels walk row slabs as
+// rowbn_partial_kernel does (the backward join through slab_walk itself), so the f64 partials they leave are
+// those that kernel would compute from the tensor they write.  Unlike it they store every row, dead ones too.
 // MASK is 0 or 2 (the joins are position-major).
-
-template <int MASK>
-__device__ __forceinline__ bool row_live(const float *__restrict__ mask, long long r, int div) {
-    return MASK ? mask[mask_roi<MASK>(r, div)] != 0.0f : true;
-}
-
-__device__ __forceinline__ float4v load4(const float *__restrict__ p, long long r, int C, int c4, bool on) {
-    const float4v zero4 = {0, 0, 0, 0};
-    return on ? reinterpret_cast<const float4v *>(p + (size_t)r * C)[c4] : zero4;
-}
 
 // Forward join: writes out = act_mask(x3*sc3 + sh3) + (DUAL ? act_mask(other*sco + sho) : other), act_mask
 // being zero on dead rows, and the partials (sum, sum of squares over the live rows) of out.
+// This kernel keeps a walk of its own, a copy of slab_walk's built from the same pieces (Slab, row_live, load4, store4,
+// slab_reduce), and sums through acc_rows2_loose / acc_row_loose, the accumulation as it was before it was pinned:
+// through the walker, and equally with the pinned sums in this loop, the <true, 2> instantiation waits for each of
+// its conditional loads on its own (21 % slower).  The sums are the same bits either way (exact products).
+// Change this loop and slab_walk together.
+__device__ __forceinline__ void acc_rows2_loose(double &s, double &q, float v0, float w0, float v1, float w1) {
+    s += (double)v0 + (double)v1;
+    q += (double)v0 * (double)w0 + (double)v1 * (double)w1;
+}
+__device__ __forceinline__ void acc_row_loose(double &s, double &q, float v, float w) {
+    s += (double)v;
+    q += (double)v * (double)w;
+}
+
 template <bool DUAL, int MASK>
 __global__ __launch_bounds__(BLOCK) void rowbn_join_fwd_kernel(
     const float *__restrict__ x3, const float *__restrict__ sc3, const float *__restrict__ sh3,
@@ -435,10 +500,10 @@ __global__ __launch_bounds__(BLOCK) void rowbn_join_fwd_kernel(
                     y0[j] = join(a0[j], o0[j], j, live0);
                     y1[j] = join(a1[j], o1[j], j, live1);
                     const float v0 = live0 ? y0[j] : 0.0f, v1 = live1 ? y1[j] : 0.0f;
-                    acc_rows2(s[j], q[j], v0, v0, v1, v1);
+                    acc_rows2_loose(s[j], q[j], v0, v0, v1, v1);
                 }
-                reinterpret_cast<float4v *>(out + (size_t)r * C)[c4] = y0;
-                reinterpret_cast<float4v *>(out + (size_t)(r + RS) * C)[c4] = y1;
+                store4(out, r, C, c4, y0);
+                store4(out, r + RS, C, c4, y1);
             }
             for (; r < b.r1; r += RS) {
                 const bool live0 = row_live<MASK>(mask, r, div);
@@ -447,9 +512,9 @@ __global__ __launch_bounds__(BLOCK) void rowbn_join_fwd_kernel(
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     y0[j] = join(a0[j], o0[j], j, live0);
-                    if (live0) acc_row(s[j], q[j], y0[j], y0[j]);
+                    if (live0) acc_row_loose(s[j], q[j], y0[j], y0[j]);
                 }
-                reinterpret_cast<float4v *>(out + (size_t)r * C)[c4] = y0;
+                store4(out, r, C, c4, y0);
             }
         }
         slab_reduce(b, C, c4, s, q, red, pout);
@@ -460,6 +525,41 @@ __global__ __launch_bounds__(BLOCK) void rowbn_join_fwd_kernel(
 // coefficients in coef, u = dy masked by the recomputed ReLU of xo*scn + shn; zero on dead rows) plus, with
 // RES, the gradient arriving over the residual path -- and the partials bn3's backward takes over it:
 // partial3 = (sum g, sum g*x3) and, with DUAL, partials = (sum g, sum g*xs), live rows only.
+template <bool DUAL, bool RES>
+struct JoinBwdCols {
+    static constexpr bool VISITS_DEAD = true, TWO_Q = DUAL;
+    const float *xo, *dy, *scn, *shn, *coef, *dres, *x3, *xs;
+    float *g;
+    int C;
+    float4v sc, sh, ka, k0, k1;
+    struct Row {
+        float4v x, d, e, a, b;
+    };
+    __device__ __forceinline__ void setup(int c4) {
+        sc = reinterpret_cast<const float4v *>(scn)[c4];
+        sh = reinterpret_cast<const float4v *>(shn)[c4];
+        ka = reinterpret_cast<const float4v *>(coef)[c4];
+        k0 = reinterpret_cast<const float4v *>(coef + C)[c4];
+        k1 = reinterpret_cast<const float4v *>(coef + 2 * C)[c4];
+    }
+    __device__ __forceinline__ Row load(long long r, int c4, bool live) const {
+        return {load4(xo, r, C, c4, live), load4(dy, r, C, c4, live), load4(dres, r, C, c4, RES),
+                load4(x3, r, C, c4, live), load4(xs, r, C, c4, DUAL && live)};
+    }
+    __device__ __forceinline__ Term finish(const Row &w, long long r, int c4, bool live) const {
+        float4v o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float u = w.d[j];
+            if (!(bn_affine(w.x[j], sc[j], sh[j]) > 0.0f)) u = 0.0f;
+            const float dx = live ? bn_dx(ka[j], u, k0[j], k1[j], w.x[j]) : 0.0f;
+            o[j] = RES ? dx + w.e[j] : dx;
+        }
+        store4(g, r, C, c4, o);
+        return {o, w.a, w.b};
+    }
+};
+
 template <bool DUAL, bool RES, int MASK>
 __global__ __launch_bounds__(BLOCK) void rowbn_join_bwd_kernel(
     const float *__restrict__ xo, const float *__restrict__ dy, const float *__restrict__ scn,
@@ -469,64 +569,9 @@ __global__ __launch_bounds__(BLOCK) void rowbn_join_bwd_kernel(
     const float *__restrict__ mask, int div) {
     __shared__ double red[BLOCK][8];
     const Slab b(M, C, rows_per_block);
-    double *p3 = partial3 + (size_t)blockIdx.x * 2 * C;
-    double *ps = DUAL ? partials + (size_t)blockIdx.x * 2 * C : nullptr;
-    for (int cc = 0; cc * b.L < b.C4; ++cc) {
-        const int c4 = cc * b.L + b.lc;
-        double s[4] = {0, 0, 0, 0}, q3[4] = {0, 0, 0, 0}, qs[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-        const float4v sc = reinterpret_cast<const float4v *>(scn)[c4], sh = reinterpret_cast<const float4v *>(shn)[c4];
-        const float4v ka = reinterpret_cast<const float4v *>(coef)[c4];
-        const float4v k0 = reinterpret_cast<const float4v *>(coef + C)[c4];
-        const float4v k1 = reinterpret_cast<const float4v *>(coef + 2 * C)[c4];
-        auto grad = [&](float x, float d, float res, int j, bool live) {
-            float u = d;
-            if (!(bn_affine(x, sc[j], sh[j]) > 0.0f)) u = 0.0f;
-            const float dx = live ? bn_dx(ka[j], u, k0[j], k1[j], x) : 0.0f;
-            return RES ? dx + res : dx;
-        };
-        if (b.lr < b.RS) {
-            const int RS = b.RS;
-            long long r = b.r0 + b.lr;
-#pragma unroll 1
-            for (; r + RS < b.r1; r += 2 * RS) {
-                const bool live0 = row_live<MASK>(mask, r, div), live1 = row_live<MASK>(mask, r + RS, div);
-                const float4v x0 = load4(xo, r, C, c4, live0), x1 = load4(xo, r + RS, C, c4, live1);
-                const float4v d0 = load4(dy, r, C, c4, live0), d1 = load4(dy, r + RS, C, c4, live1);
-                const float4v e0 = load4(dres, r, C, c4, RES), e1 = load4(dres, r + RS, C, c4, RES);
-                const float4v a0 = load4(x3, r, C, c4, live0), a1 = load4(x3, r + RS, C, c4, live1);
-                const float4v b0 = load4(xs, r, C, c4, DUAL && live0), b1 = load4(xs, r + RS, C, c4, DUAL && live1);
-                float4v g0, g1;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    g0[j] = grad(x0[j], d0[j], e0[j], j, live0);
-                    g1[j] = grad(x1[j], d1[j], e1[j], j, live1);
-                    const float v0 = live0 ? g0[j] : 0.0f, v1 = live1 ? g1[j] : 0.0f;
-                    acc_rows2(s[j], q3[j], v0, a0[j], v1, a1[j]);
-                    if (DUAL) acc_rows2(s2[j], qs[j], v0, b0[j], v1, b1[j]);
-                }
-                reinterpret_cast<float4v *>(g + (size_t)r * C)[c4] = g0;
-                reinterpret_cast<float4v *>(g + (size_t)(r + RS) * C)[c4] = g1;
-            }
-            for (; r < b.r1; r += RS) {
-                const bool live0 = row_live<MASK>(mask, r, div);
-                const float4v x0 = load4(xo, r, C, c4, live0), d0 = load4(dy, r, C, c4, live0);
-                const float4v e0 = load4(dres, r, C, c4, RES), a0 = load4(x3, r, C, c4, live0);
-                const float4v b0 = load4(xs, r, C, c4, DUAL && live0);
-                float4v g0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    g0[j] = grad(x0[j], d0[j], e0[j], j, live0);
-                    if (live0) {
-                        acc_row(s[j], q3[j], g0[j], a0[j]);
-                        if (DUAL) acc_row(s2[j], qs[j], g0[j], b0[j]);
-                    }
-                }
-                reinterpret_cast<float4v *>(g + (size_t)r * C)[c4] = g0;
-            }
-        }
-        slab_reduce(b, C, c4, s, q3, red, p3);
-        if (DUAL) slab_reduce(b, C, c4, s, qs, red, ps);
-    }
+    JoinBwdCols<DUAL, RES> f = {xo, dy, scn, shn, coef, dres, x3, xs, g, C};
+    slab_walk<MASK>(b, C, mask, div, f, red, partial3 + (size_t)blockIdx.x * 2 * C,
+                    DUAL ? partials + (size_t)blockIdx.x * 2 * C : nullptr);
 }
 
 // Block 1's two backward applies in one pass over g: dx3 and dxs from their own coefficient sets (neither
@@ -594,203 +639,6 @@ PLUMB_API size_t wsplumb_rowbn_workspace_bytes(long long M, int C) {
 // 1 when the kernels support the shape (C % 4 == 0 and C/4 divides or is a multiple of 256)
 PLUMB_API int wsplumb_rowbn_supported(long long M, int C) { return shape_ok(M, C) ? 1 : 0; }
 
-static int forward_impl(const float *x, long long M, int C, const float *weight, const float *bias, float eps,
-                        int relu, float *y, float *mean, float *var, float *rstd, float *scale, float *shift,
-                        const float *mask, int n_rois, int per, float *count, void *workspace,
-                        size_t workspace_bytes, void *stream, Running run, bool pm = false) {
-    if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
-    if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nb = partial_blocks(M, C);
-    const long long rpb = (M + nb - 1) / nb;
-    double *partial = static_cast<double *>(workspace);
-    const int div = pm ? n_rois : per;          // row -> RoI divisor of the mask modes (mask_roi)
-    if (mask && pm)
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 2>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
-                           nullptr, nullptr, M, C, rpb, partial, mask, div);
-    else if (mask)
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 1>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
-                           nullptr, nullptr, M, C, rpb, partial, mask, per);
-    else
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 0>), dim3(nb), dim3(BLOCK), 0, st, x, nullptr,
-                           nullptr, nullptr, M, C, rpb, partial, nullptr, 1);
-    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st, partial, nb, C,
-                       M, weight, bias, eps, mean, var, rstd, scale, shift, mask, n_rois, per, count, run);
-    const long long total4 = M * (C / 4);
-#define WSPLUMB_APPLY(RELU, MASK) \
-    hipLaunchKernelGGL((rowbn_apply_fwd_kernel<RELU, MASK>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, scale, \
-                       shift, total4, C / 4, y, mask, div)
-    const int mode = mask ? (pm ? 2 : 1) : 0;
-    if (relu) { if (mode == 2) WSPLUMB_APPLY(true, 2); else if (mode) WSPLUMB_APPLY(true, 1); else WSPLUMB_APPLY(true, 0); }
-    else { if (mode == 2) WSPLUMB_APPLY(false, 2); else if (mode) WSPLUMB_APPLY(false, 1); else WSPLUMB_APPLY(false, 0); }
-#undef WSPLUMB_APPLY
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-}
-
-// y = act(batch_norm(x)); writes mean, var (biased), rstd, scale = rstd*weight,
-// shift = bias - mean*scale (all [C]).  Returns 0 on success.
-// running_mean / running_var (f32 [C]) and num_batches_tracked (int64 [1]) are the layer's buffers, updated
-// in place with `momentum` (struct Running); each may be null.  The same four close every forward entry point.
-PLUMB_API int wsplumb_rowbn_forward(const float *x, long long M, int C, const float *weight,
-                                    const float *bias, float eps, int relu, float *y, float *mean,
-                                    float *var, float *rstd, float *scale, float *shift,
-                                    void *workspace, size_t workspace_bytes, void *stream,
-                                    float *running_mean, float *running_var, float momentum,
-                                    long long *num_batches_tracked) {
-    return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, nullptr, 0, 1, nullptr,
-                        workspace, workspace_bytes, stream,
-                        Running{running_mean, running_var, momentum, num_batches_tracked});
-}
-
-// the same over the live rows only: mask [n_rois] f32 (0 = dead), rows r*per .. r*per+per-1 belong to
-// RoI r (M = n_rois * per); dead rows of y are written as zeros; count[0] receives the number of live
-// rows (>= 1) as a float, for the caller's running-variance correction
-PLUMB_API int wsplumb_rowbn_forward_masked(const float *x, long long M, int C, const float *weight,
-                                           const float *bias, float eps, int relu, const float *mask,
-                                           int n_rois, int per, float *y, float *mean, float *var,
-                                           float *rstd, float *scale, float *shift, float *count,
-                                           void *workspace, size_t workspace_bytes, void *stream,
-                                           float *running_mean, float *running_var, float momentum,
-                                           long long *num_batches_tracked) {
-    if (!mask || !count) return 1;
-    return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, mask, n_rois, per, count,
-                        workspace, workspace_bytes, stream,
-                        Running{running_mean, running_var, momentum, num_batches_tracked});
-}
-
-// y = act(x*scale + shift) with given per-column scale / shift (inference statistics)
-PLUMB_API int wsplumb_rowbn_apply(const float *x, long long M, int C, const float *scale,
-                                  const float *shift, int relu, float *y, void *stream) {
-    if (M < 1 || C < 4 || (C & 3)) return 1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long long total4 = M * (C / 4);
-    if (relu)
-        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 0>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x,
-                           scale, shift, total4, C / 4, y, nullptr, 1);
-    else
-        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<false, 0>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x,
-                           scale, shift, total4, C / 4, y, nullptr, 1);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-}
-
-static int backward_impl(const float *x, const float *dy, long long M, int C, const float *weight,
-                         const float *mean, const float *rstd, const float *scale, const float *shift, int relu,
-                         float *dx, float *dweight, float *dbias, float *coef, const float *mask, int n_rois,
-                         int per, void *workspace, size_t workspace_bytes, void *stream, bool pm = false) {
-    if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
-    if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nb = partial_blocks(M, C);
-    const long long rpb = (M + nb - 1) / nb;
-    double *partial = static_cast<double *>(workspace);
-    const int div = pm ? n_rois : per;
-    const int mode = mask ? (pm ? 2 : 1) : 0;
-#define WSPLUMB_PARTIAL(RELU, MASK) \
-    hipLaunchKernelGGL((rowbn_partial_kernel<1, RELU, MASK>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M, C, \
-                       rpb, partial, mask, div)
-    if (relu) { if (mode == 2) WSPLUMB_PARTIAL(true, 2); else if (mode) WSPLUMB_PARTIAL(true, 1); else WSPLUMB_PARTIAL(true, 0); }
-    else { if (mode == 2) WSPLUMB_PARTIAL(false, 2); else if (mode) WSPLUMB_PARTIAL(false, 1); else WSPLUMB_PARTIAL(false, 0); }
-#undef WSPLUMB_PARTIAL
-    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st, partial, nb, C,
-                       M, weight, mean, rstd, dweight, dbias, coef, mask, n_rois, per);
-    const long long total4 = M * (C / 4);
-#define WSPLUMB_APPLY(RELU, MASK) \
-    hipLaunchKernelGGL((rowbn_apply_bwd_kernel<RELU, MASK>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy, scale, \
-                       shift, coef, total4, C / 4, dx, mask, div)
-    if (relu) { if (mode == 2) WSPLUMB_APPLY(true, 2); else if (mode) WSPLUMB_APPLY(true, 1); else WSPLUMB_APPLY(true, 0); }
-    else { if (mode == 2) WSPLUMB_APPLY(false, 2); else if (mode) WSPLUMB_APPLY(false, 1); else WSPLUMB_APPLY(false, 0); }
-#undef WSPLUMB_APPLY
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-}
-
-// gradients of wsplumb_rowbn_forward: dx [M,C], dweight [C], dbias [C]; coef is [3*C] scratch
-PLUMB_API int wsplumb_rowbn_backward(const float *x, const float *dy, long long M, int C,
-                                     const float *weight, const float *mean, const float *rstd,
-                                     const float *scale, const float *shift, int relu, float *dx,
-                                     float *dweight, float *dbias, float *coef, void *workspace,
-                                     size_t workspace_bytes, void *stream) {
-    return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, nullptr, 0, 1,
-                         workspace, workspace_bytes, stream);
-}
-
-// gradients of wsplumb_rowbn_forward_masked (dead rows: dy ignored, dx = 0)
-PLUMB_API int wsplumb_rowbn_backward_masked(const float *x, const float *dy, long long M, int C,
-                                            const float *weight, const float *mean, const float *rstd,
-                                            const float *scale, const float *shift, int relu,
-                                            const float *mask, int n_rois, int per, float *dx,
-                                            float *dweight, float *dbias, float *coef, void *workspace,
-                                            size_t workspace_bytes, void *stream) {
-    if (!mask) return 1;
-    return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, mask, n_rois, per,
-                         workspace, workspace_bytes, stream);
-}
-
-// the masked forward on position-major rows: row r belongs to RoI r % n_rois (M = n_rois * per)
-PLUMB_API int wsplumb_rowbn_forward_masked_pm(const float *x, long long M, int C, const float *weight,
-                                              const float *bias, float eps, int relu, const float *mask,
-                                              int n_rois, int per, float *y, float *mean, float *var,
-                                              float *rstd, float *scale, float *shift, float *count,
-                                              void *workspace, size_t workspace_bytes, void *stream,
-                                              float *running_mean, float *running_var, float momentum,
-                                              long long *num_batches_tracked) {
-    if (!mask || !count) return 1;
-    return forward_impl(x, M, C, weight, bias, eps, relu, y, mean, var, rstd, scale, shift, mask, n_rois, per, count,
-                        workspace, workspace_bytes, stream,
-                        Running{running_mean, running_var, momentum, num_batches_tracked}, true);
-}
-
-// gradients of wsplumb_rowbn_forward_masked_pm
-PLUMB_API int wsplumb_rowbn_backward_masked_pm(const float *x, const float *dy, long long M, int C,
-                                               const float *weight, const float *mean, const float *rstd,
-                                               const float *scale, const float *shift, int relu,
-                                               const float *mask, int n_rois, int per, float *dx,
-                                               float *dweight, float *dbias, float *coef, void *workspace,
-                                               size_t workspace_bytes, void *stream) {
-    if (!mask) return 1;
-    return backward_impl(x, dy, M, C, weight, mean, rstd, scale, shift, relu, dx, dweight, dbias, coef, mask, n_rois, per,
-                         workspace, workspace_bytes, stream, true);
-}
-
-// gradients of wsplumb_rowbn_forward[_masked] with ReLU for block 1's pre-activation norm, the output's gradient
-// given in its two parts (EntryGrad above): dy [n_rois * per, C] roi-major from conv1, dys [n_slots * n_rois, C]
-// position-major from the projection shortcut, possel [per] (device) the slot of each position or -1.
-// mask may be null.  Bit-identical to wsplumb_rowbn_backward[_masked] on dy + scatter(dys).
-PLUMB_API int wsplumb_rowbn_backward_entry(const float *x, const float *dy, const float *dys, const int *possel,
-                                           int n_slots, long long M, int C, const float *weight, const float *mean,
-                                           const float *rstd, const float *scale, const float *shift,
-                                           const float *mask, int n_rois, int per, float *dx, float *dweight,
-                                           float *dbias, float *coef, void *workspace, size_t workspace_bytes,
-                                           void *stream) {
-    if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_workspace_bytes(M, C)) return 1;
-    if (!dys || !possel || per < 1 || n_rois < 1 || n_slots < 1 || n_slots > per ||
-        (long long)n_rois * per != M || M > 0x7fffffffLL)
-        return 1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nb = partial_blocks(M, C);
-    const long long rpb = (M + nb - 1) / nb;
-    double *partial = static_cast<double *>(workspace);
-    const EntryGrad eg = {dys, possel, per, n_rois};
-    if (mask)
-        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 1, true>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M,
-                           C, rpb, partial, mask, per, eg);
-    else
-        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 0, true>), dim3(nb), dim3(BLOCK), 0, st, x, dy, scale, shift, M,
-                           C, rpb, partial, mask, 1, eg);
-    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0, st,
-                       partial, nb, C, M, weight, mean, rstd, dweight, dbias, coef, mask, n_rois, per);
-    const long long total4 = M * (C / 4);
-    if (mask)
-        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<true, 1, true>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy,
-                           scale, shift, coef, total4, C / 4, dx, mask, per, eg);
-    else
-        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<true, 0, true>), dim3(apply_grid(total4)), dim3(BLOCK), 0, st, x, dy,
-                           scale, shift, coef, total4, C / 4, dx, mask, 1, eg);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-}
-
-// ---- residual joins (position-major rows; mask may be null: every row live) ----
-// Statistic blocks are [5, C] f32: mean, var, rstd, scale, shift (the layout of the Python binding).
-
 // bytes of scratch of one join call: two partial buffers
 PLUMB_API size_t wsplumb_rowbn_join_workspace_bytes(long long M, int C) {
     return 2 * wsplumb_rowbn_workspace_bytes(M, C);
@@ -798,55 +646,207 @@ PLUMB_API size_t wsplumb_rowbn_join_workspace_bytes(long long M, int C) {
 
 namespace {
 
-struct JoinGeom {
+// Everything a launch needs to know about one call's rows: filled, and the call's arguments checked, by make_geom.
+struct Geom {
     hipStream_t st;
-    int nb, mode, div;
-    long long rpb, total4;
-    double *p0, *p1;
+    long long M, rpb, total4;
+    int C, nb;
+    const float *mask;      // null: every row live
+    int mode, div;          // mask mode and row -> RoI divisor of the kernels (mask_roi); 0, 1 without a mask
+    int n_rois, per;
+    double *p0, *p1;        // partial buffers in the workspace (p1 with n_partials = 2)
 };
 
-// 0 when the arguments of a join entry point are usable
-inline int join_geom(long long M, int C, const float *mask, int n_rois, int per, void *workspace,
-                     size_t workspace_bytes, void *stream, JoinGeom &g) {
-    if (!shape_ok(M, C) || workspace_bytes < wsplumb_rowbn_join_workspace_bytes(M, C)) return 1;
-    if (mask && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
+// THE argument check of every entry point; returns 0 and fills g when the call may launch.
+//   n_partials   partial buffers the workspace must hold (0: an elementwise call, any C % 4 == 0)
+//   grouped      the rows must come as n_rois groups of `per` even without a mask (the entry gradient)
+//   args_ok      the entry point's own requirements on its optional pointers, evaluated by the caller
+inline int make_geom(Geom &g, long long M, int C, const float *mask, int n_rois, int per, bool pos_major, bool grouped,
+                     bool args_ok, void *workspace, size_t workspace_bytes, int n_partials, void *stream) {
+    if (!args_ok || M < 1 || C < 4 || (C & 3)) return 1;
+    if (n_partials && (!shape_ok(M, C) || workspace_bytes < n_partials * wsplumb_rowbn_workspace_bytes(M, C))) return 1;
+    if (pos_major && !mask) return 1;
+    if ((mask || grouped) && (per < 1 || n_rois < 1 || (long long)n_rois * per != M || M > 0x7fffffffLL)) return 1;
     g.st = static_cast<hipStream_t>(stream);
-    g.nb = partial_blocks(M, C);
-    g.rpb = (M + g.nb - 1) / g.nb;
+    g.M = M;
+    g.C = C;
+    g.nb = n_partials ? partial_blocks(M, C) : 0;
+    g.rpb = n_partials ? (M + g.nb - 1) / g.nb : 0;
     g.total4 = M * (C / 4);
-    g.mode = mask ? 2 : 0;
-    g.div = mask ? n_rois : 1;
+    g.mask = mask;
+    g.mode = mask ? (pos_major ? 2 : 1) : 0;
+    g.div = mask ? (pos_major ? n_rois : per) : 1;
+    g.n_rois = n_rois;
+    g.per = per;
     g.p0 = static_cast<double *>(workspace);
     g.p1 = g.p0 + (size_t)g.nb * 2 * C;
     return 0;
 }
 
-// statistics of x (no apply): partial sums into g.p0, then the finish kernel
-inline void join_stats(const JoinGeom &g, const float *x, long long M, int C, const float *weight, const float *bias,
-                       float eps, float *stats, const float *mask, int n_rois, int per, float *count, Running run) {
-    if (g.mode)
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 2>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, nullptr, nullptr,
-                           nullptr, M, C, g.rpb, g.p0, mask, g.div);
-    else
-        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, 0>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, nullptr, nullptr,
-                           nullptr, M, C, g.rpb, g.p0, nullptr, 1);
-    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
-                       g.st, g.p0, g.nb, C, M, weight, bias, eps, stats, stats + C, stats + 2 * C, stats + 3 * C,
-                       stats + 4 * C, mask, n_rois, per, count, run);
+// THE place where a runtime flag becomes a template argument: f(std::integral_constant<.., V>) for the V equal to v.
+template <auto... Vs, class T, class F>
+inline void pick(T v, F &&f) {
+    (void)((v == Vs && (f(std::integral_constant<decltype(Vs), Vs>{}), true)) || ...);
 }
 
-inline void join_bwd_finish(const JoinGeom &g, const double *partial, long long M, int C, const float *weight,
-                            const float *stats, float *dwb, float *coef, const float *mask, int n_rois, int per) {
-    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
-                       g.st, partial, g.nb, C, M, weight, stats, stats + 2 * C, dwb, dwb + C, coef, mask, n_rois, per);
+// column sums of x (MODE 0 of rowbn_partial_kernel)
+inline void launch_sums(const Geom &g, const float *x, double *partial) {
+    pick<0, 1, 2>(g.mode, [&](auto MASK) {
+        hipLaunchKernelGGL((rowbn_partial_kernel<0, false, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, nullptr, nullptr,
+                           nullptr, g.M, g.C, g.rpb, partial, g.mask, g.div);
+    });
+}
+
+// column sums of g and g*x (MODE 1), dy given in two parts with eg
+inline void launch_grad_sums(const Geom &g, const float *x, const float *dy, const float *scale, const float *shift,
+                             bool relu, const EntryGrad *eg, double *partial) {
+    if (eg)
+        pick<0, 1>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_partial_kernel<1, true, MASK, true>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, dy, scale,
+                               shift, g.M, g.C, g.rpb, partial, g.mask, g.div, *eg);
+        });
+    else
+        pick<false, true>(relu, [&](auto RELU) {
+            pick<0, 1, 2>(g.mode, [&](auto MASK) {
+                hipLaunchKernelGGL((rowbn_partial_kernel<1, RELU, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, dy, scale,
+                                   shift, g.M, g.C, g.rpb, partial, g.mask, g.div);
+            });
+        });
+}
+
+inline void launch_fwd_finish(const Geom &g, const double *partial, const float *weight, const float *bias, float eps,
+                              float *mean, float *var, float *rstd, float *scale, float *shift, float *count,
+                              Running run) {
+    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((g.C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
+                       g.st, partial, g.nb, g.C, g.M, weight, bias, eps, mean, var, rstd, scale, shift, g.mask, g.n_rois,
+                       g.per, g.mask ? count : nullptr, run);
+}
+
+// the same into a [5, C] statistic block: mean, var, rstd, scale, shift (the layout of the Python binding)
+inline void launch_fwd_finish(const Geom &g, const double *partial, const float *weight, const float *bias, float eps,
+                              float *stats, float *count, Running run) {
+    const int C = g.C;
+    launch_fwd_finish(g, partial, weight, bias, eps, stats, stats + C, stats + 2 * C, stats + 3 * C, stats + 4 * C, count,
+                      run);
+}
+
+inline void launch_bwd_finish(const Geom &g, const double *partial, const float *weight, const float *mean,
+                              const float *rstd, float *dweight, float *dbias, float *coef) {
+    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((g.C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
+                       g.st, partial, g.nb, g.C, g.M, weight, mean, rstd, dweight, dbias, coef, g.mask, g.n_rois, g.per);
+}
+
+inline void launch_apply_fwd(const Geom &g, const float *x, const float *scale, const float *shift, bool relu, float *y) {
+    pick<false, true>(relu, [&](auto RELU) {
+        pick<0, 1, 2>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_apply_fwd_kernel<RELU, MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x,
+                               scale, shift, g.total4, g.C / 4, y, g.mask, g.div);
+        });
+    });
+}
+
+inline void launch_apply_bwd(const Geom &g, const float *x, const float *dy, const float *scale, const float *shift,
+                             const float *coef, bool relu, const EntryGrad *eg, float *dx) {
+    if (eg)
+        pick<0, 1>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_apply_bwd_kernel<true, MASK, true>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st,
+                               x, dy, scale, shift, coef, g.total4, g.C / 4, dx, g.mask, g.div, *eg);
+        });
+    else
+        pick<false, true>(relu, [&](auto RELU) {
+            pick<0, 1, 2>(g.mode, [&](auto MASK) {
+                hipLaunchKernelGGL((rowbn_apply_bwd_kernel<RELU, MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st,
+                                   x, dy, scale, shift, coef, g.total4, g.C / 4, dx, g.mask, g.div);
+            });
+        });
+}
+
+inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
+
+// the backward of one layer; eg: dy comes in the two parts of block 1's entry gradient (relu, roi-major rows)
+int backward_impl(const Geom &g, const float *x, const float *dy, const EntryGrad *eg, const float *weight,
+                  const float *mean, const float *rstd, const float *scale, const float *shift, bool relu, float *dx,
+                  float *dweight, float *dbias, float *coef) {
+    launch_grad_sums(g, x, dy, scale, shift, relu, eg, g.p0);
+    launch_bwd_finish(g, g.p0, weight, mean, rstd, dweight, dbias, coef);
+    launch_apply_bwd(g, x, dy, scale, shift, coef, relu, eg, dx);
+    return launched();
 }
 
 }  // namespace
 
+// y = act(batch_norm(x)); writes mean, var (biased), rstd, scale = rstd*weight, shift = bias - mean*scale (all [C]).
+// Returns 0 on success, 1 for arguments it rejects (before any launch).
+// mask (null: every row live): [n_rois] f32, 0 = dead; M = n_rois * per and row r belongs to RoI r / per or, with
+// pos_major, r % n_rois (pos_major needs a mask).  Statistics are taken over the live rows, dead rows of y are
+// written as zeros, and count[0] (required with a mask, untouched without) receives the number of live rows (>= 1)
+// as a float.
+// running_mean / running_var (f32 [C]) and num_batches_tracked (int64 [1]) are the layer's buffers, updated in place
+// with `momentum` (struct Running); each may be null.
+PLUMB_API int wsplumb_rowbn_forward(const float *x, long long M, int C, const float *weight, const float *bias,
+                                    float eps, int relu, const float *mask, int n_rois, int per, int pos_major,
+                                    float *y, float *mean, float *var, float *rstd, float *scale, float *shift,
+                                    float *count, void *workspace, size_t workspace_bytes, void *stream,
+                                    float *running_mean, float *running_var, float momentum,
+                                    long long *num_batches_tracked) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, !mask || count, workspace, workspace_bytes, 1,
+                  stream))
+        return 1;
+    launch_sums(g, x, g.p0);
+    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
+                      Running{running_mean, running_var, momentum, num_batches_tracked});
+    launch_apply_fwd(g, x, scale, shift, relu != 0, y);
+    return launched();
+}
+
+// y = act(x*scale + shift) with given per-column scale / shift (inference statistics)
+PLUMB_API int wsplumb_rowbn_apply(const float *x, long long M, int C, const float *scale,
+                                  const float *shift, int relu, float *y, void *stream) {
+    Geom g;
+    if (make_geom(g, M, C, nullptr, 0, 1, false, false, true, nullptr, 0, 0, stream)) return 1;
+    launch_apply_fwd(g, x, scale, shift, relu != 0, y);
+    return launched();
+}
+
+// gradients of wsplumb_rowbn_forward (same mask arguments; dead rows: dy ignored, dx = 0): dx [M,C], dweight [C],
+// dbias [C]; coef is [3*C] scratch
+PLUMB_API int wsplumb_rowbn_backward(const float *x, const float *dy, long long M, int C, const float *weight,
+                                     const float *mean, const float *rstd, const float *scale, const float *shift,
+                                     int relu, const float *mask, int n_rois, int per, int pos_major, float *dx,
+                                     float *dweight, float *dbias, float *coef, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, true, workspace, workspace_bytes, 1, stream))
+        return 1;
+    return backward_impl(g, x, dy, nullptr, weight, mean, rstd, scale, shift, relu != 0, dx, dweight, dbias, coef);
+}
+
+// gradients of wsplumb_rowbn_forward with ReLU for block 1's pre-activation norm (roi-major rows), the output's
+// gradient given in its two parts (EntryGrad above): dy [n_rois * per, C] roi-major from conv1, dys
+// [n_slots * n_rois, C] position-major from the projection shortcut, possel [per] (device) the slot of each position
+// or -1.  mask may be null.  Bit-identical to wsplumb_rowbn_backward on dy + scatter(dys).
+PLUMB_API int wsplumb_rowbn_backward_entry(const float *x, const float *dy, const float *dys, const int *possel,
+                                           int n_slots, long long M, int C, const float *weight, const float *mean,
+                                           const float *rstd, const float *scale, const float *shift,
+                                           const float *mask, int n_rois, int per, float *dx, float *dweight,
+                                           float *dbias, float *coef, void *workspace, size_t workspace_bytes,
+                                           void *stream) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, false, true, dys && possel && n_slots >= 1 && n_slots <= per, workspace,
+                  workspace_bytes, 1, stream))
+        return 1;
+    const EntryGrad eg = {dys, possel, per, n_rois};
+    return backward_impl(g, x, dy, &eg, weight, mean, rstd, scale, shift, true, dx, dweight, dbias, coef);
+}
+
+// ---- residual joins (position-major rows; mask may be null: every row live) ----
+// Statistic blocks are [5, C] f32: mean, var, rstd, scale, shift (the layout of the Python binding).
+
 // out = bn3(x3) + other, y = relu(bn_n(out)), all in training mode over the live rows:
 //   other is the identity shortcut when weight_s is null, else the input xs of the shortcut's own norm
 //   (out = bn3(x3) + bn_s(xs); stats_s is written only then);
-//   stats3 / stats_s / stats_n [5, C] and count [1] are what wsplumb_rowbn_forward_masked_pm writes for the
+//   stats3 / stats_s / stats_n [5, C] and count [1] are what wsplumb_rowbn_forward (pos_major) writes for the
 //   three layers (count: once, they share the mask; untouched without a mask);
 //   running [6] / momentum [3] / batches [3] (host arrays, or null): the running_mean, running_var pointers, the
 //   momentum and the num_batches_tracked pointer of bn3, bn_s, bn_n in that order (struct Running), each
@@ -862,36 +862,33 @@ PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, lo
                                          void *workspace, size_t workspace_bytes, void *stream,
                                          float *const *running, const float *momentum,
                                          long long *const *batches) {
-    JoinGeom g;
-    if (join_geom(M, C, mask, n_rois, per, workspace, workspace_bytes, stream, g)) return 1;
-    if (mask && !count) return 1;
     const bool dual = weight_s != nullptr;
-    if (dual && (!bias_s || !stats_s)) return 1;
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, mask != nullptr, false, (!mask || count) && (!dual || (bias_s && stats_s)),
+                  workspace, workspace_bytes, 2, stream))
+        return 1;
     Running run[3] = {};
     for (int k = 0; k < 3; ++k) {
         if (running) { run[k].mean = running[2 * k]; run[k].var = running[2 * k + 1]; }
         if (momentum) run[k].momentum = momentum[k];
         if (batches) run[k].batches = batches[k];
     }
-    join_stats(g, x3, M, C, weight3, bias3, eps3, stats3, mask, n_rois, per, nullptr, run[0]);
-    if (dual) join_stats(g, other, M, C, weight_s, bias_s, eps_s, stats_s, mask, n_rois, per, nullptr, run[1]);
+    launch_sums(g, x3, g.p0);
+    launch_fwd_finish(g, g.p0, weight3, bias3, eps3, stats3, nullptr, run[0]);
+    if (dual) {
+        launch_sums(g, other, g.p0);
+        launch_fwd_finish(g, g.p0, weight_s, bias_s, eps_s, stats_s, nullptr, run[1]);
+    }
     const float *sco = dual ? stats_s + 3 * C : nullptr, *sho = dual ? stats_s + 4 * C : nullptr;
-#define WSPLUMB_JOIN(DUAL, MASK) \
-    hipLaunchKernelGGL((rowbn_join_fwd_kernel<DUAL, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, x3, stats3 + 3 * C, \
-                       stats3 + 4 * C, other, sco, sho, M, C, g.rpb, out, g.p0, mask, g.div)
-    if (dual) { if (g.mode) WSPLUMB_JOIN(true, 2); else WSPLUMB_JOIN(true, 0); }
-    else { if (g.mode) WSPLUMB_JOIN(false, 2); else WSPLUMB_JOIN(false, 0); }
-#undef WSPLUMB_JOIN
-    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
-                       g.st, g.p0, g.nb, C, M, weight_n, bias_n, eps_n, stats_n, stats_n + C, stats_n + 2 * C,
-                       stats_n + 3 * C, stats_n + 4 * C, mask, n_rois, per, mask ? count : nullptr, run[2]);
-    if (g.mode)
-        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, out,
-                           stats_n + 3 * C, stats_n + 4 * C, g.total4, C / 4, y, mask, g.div);
-    else
-        hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, 0>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, out,
-                           stats_n + 3 * C, stats_n + 4 * C, g.total4, C / 4, y, nullptr, 1);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
+    pick<false, true>(dual, [&](auto DUAL) {
+        pick<0, 2>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_join_fwd_kernel<DUAL, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, x3, stats3 + 3 * C,
+                               stats3 + 4 * C, other, sco, sho, M, C, g.rpb, out, g.p0, mask, g.div);
+        });
+    });
+    launch_fwd_finish(g, g.p0, weight_n, bias_n, eps_n, stats_n, count, run[2]);
+    launch_apply_fwd(g, out, stats_n + 3 * C, stats_n + 4 * C, true, y);
+    return launched();
 }
 
 // gradients of wsplumb_rowbn_join_forward: dy is the gradient of y, dres that of out over the residual path
@@ -905,42 +902,32 @@ PLUMB_API int wsplumb_rowbn_join_backward(const float *out, const float *dy, con
                                           int n_rois, int per, float *gout, float *dx3, float *dxs, float *dwb_n,
                                           float *dwb3, float *dwb_s, float *coef, void *workspace,
                                           size_t workspace_bytes, void *stream) {
-    JoinGeom g;
-    if (join_geom(M, C, mask, n_rois, per, workspace, workspace_bytes, stream, g)) return 1;
     const bool dual = xs != nullptr;
-    if (dual && (!weight_s || !stats_s || !dxs || !dwb_s)) return 1;
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, mask != nullptr, false, !dual || (weight_s && stats_s && dxs && dwb_s),
+                  workspace, workspace_bytes, 2, stream))
+        return 1;
     float *coef_n = coef, *coef3 = coef + 3 * C, *coefs = coef + 6 * C;
     const float *scn = stats_n + 3 * C, *shn = stats_n + 4 * C;
-    if (g.mode)
-        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 2>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn, shn, M, C,
-                           g.rpb, g.p0, mask, g.div);
-    else
-        hipLaunchKernelGGL((rowbn_partial_kernel<1, true, 0>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn, shn, M, C,
-                           g.rpb, g.p0, nullptr, 1);
-    join_bwd_finish(g, g.p0, M, C, weight_n, stats_n, dwb_n, coef_n, mask, n_rois, per);
-#define WSPLUMB_JOIN(DUAL, RES, MASK) \
-    hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, RES, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn, shn, \
-                       coef_n, dres, x3, xs, M, C, g.rpb, gout, g.p0, g.p1, mask, g.div)
-#define WSPLUMB_JOIN_M(DUAL, RES) do { if (g.mode) WSPLUMB_JOIN(DUAL, RES, 2); else WSPLUMB_JOIN(DUAL, RES, 0); } while (0)
-    if (dual) { if (dres) WSPLUMB_JOIN_M(true, true); else WSPLUMB_JOIN_M(true, false); }
-    else { if (dres) WSPLUMB_JOIN_M(false, true); else WSPLUMB_JOIN_M(false, false); }
-#undef WSPLUMB_JOIN_M
-#undef WSPLUMB_JOIN
-    join_bwd_finish(g, g.p0, M, C, weight3, stats3, dwb3, coef3, mask, n_rois, per);
+    launch_grad_sums(g, out, dy, scn, shn, true, nullptr, g.p0);
+    launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n);
+    pick<false, true>(dual, [&](auto DUAL) {
+        pick<false, true>(dres != nullptr, [&](auto RES) {
+            pick<0, 2>(g.mode, [&](auto MASK) {
+                hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, RES, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn,
+                                   shn, coef_n, dres, x3, xs, M, C, g.rpb, gout, g.p0, g.p1, mask, g.div);
+            });
+        });
+    });
+    launch_bwd_finish(g, g.p0, weight3, stats3, stats3 + 2 * C, dwb3, dwb3 + C, coef3);
     if (dual) {
-        join_bwd_finish(g, g.p1, M, C, weight_s, stats_s, dwb_s, coefs, mask, n_rois, per);
-        if (g.mode)
-            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
+        launch_bwd_finish(g, g.p1, weight_s, stats_s, stats_s + 2 * C, dwb_s, dwb_s + C, coefs);
+        pick<0, 2>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
                                gout, coef3, coefs, g.total4, C / 4, dx3, dxs, mask, g.div);
-        else
-            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<0>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
-                               gout, coef3, coefs, g.total4, C / 4, dx3, dxs, nullptr, 1);
-    } else if (g.mode) {
-        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<false, 2>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, gout,
-                           nullptr, nullptr, coef3, g.total4, C / 4, dx3, mask, g.div);
+        });
     } else {
-        hipLaunchKernelGGL((rowbn_apply_bwd_kernel<false, 0>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, gout,
-                           nullptr, nullptr, coef3, g.total4, C / 4, dx3, nullptr, 1);
+        launch_apply_bwd(g, x3, gout, nullptr, nullptr, coef3, false, nullptr, dx3);
     }
-    return hipGetLastError() == hipSuccess ? 0 : 3;
+    return launched();
 }

@@ -32,22 +32,13 @@ def lib():
         L.wsplumb_rowbn_supported.restype = _i
         L.wsplumb_rowbn_supported.argtypes = [_ll, _i]
         L.wsplumb_rowbn_forward.restype = _i
-        L.wsplumb_rowbn_forward.argtypes = [_vp, _ll, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _sz, _vp] + _RUN
+        L.wsplumb_rowbn_forward.argtypes = ([_vp, _ll, _i, _vp, _vp, _f, _i, _vp, _i, _i, _i] + [_vp] * 8 + [_sz, _vp]
+                                            + _RUN)
         L.wsplumb_rowbn_apply.restype = _i
         L.wsplumb_rowbn_apply.argtypes = [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp]
         L.wsplumb_rowbn_backward.restype = _i
-        L.wsplumb_rowbn_backward.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
-                                             _vp, _vp, _sz, _vp]
-        L.wsplumb_rowbn_forward_masked.restype = _i
-        L.wsplumb_rowbn_forward_masked.argtypes = [_vp, _ll, _i, _vp, _vp, _f, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
-                                                   _vp, _vp, _vp, _vp, _sz, _vp] + _RUN
-        L.wsplumb_rowbn_backward_masked.restype = _i
-        L.wsplumb_rowbn_backward_masked.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
-                                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]
-        for name in ("wsplumb_rowbn_forward_masked_pm", "wsplumb_rowbn_backward_masked_pm"):
-            base = getattr(L, name[:-3])
-            getattr(L, name).restype, getattr(L, name).argtypes = base.restype, base.argtypes
+        L.wsplumb_rowbn_backward.argtypes = ([_vp, _vp, _ll, _i] + [_vp] * 5 + [_i, _vp, _i, _i, _i] + [_vp] * 5
+                                             + [_sz, _vp])
         L.wsplumb_rowbn_backward_entry.restype = _i
         L.wsplumb_rowbn_backward_entry.argtypes = [_vp] * 4 + [_i, _ll, _i] + [_vp] * 6 + [_i, _i] + [_vp] * 5 + [_sz, _vp]
         L.wsplumb_rowbn_join_workspace_bytes.restype = _sz
@@ -77,6 +68,15 @@ def lib():
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _pn(t):
+    return _p(t) if t is not None else None
+
+
+def _check(rc, name):
+    if rc:
+        raise RuntimeError("%s failed (%d)" % (name, rc))
 
 
 def _stream():
@@ -132,23 +132,17 @@ def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False, *, run
     dev = x.device
     y = torch.empty_like(x)
     stats = torch.empty((5, C), dtype=torch.float32, device=dev)   # mean, var, rstd, scale, shift
-    count = None
+    count, n_rois = None, 0
+    if mask is not None:
+        n_rois = mask.shape[0]
+        assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
+        count = torch.empty((1,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         ws, n = _workspace(L, M, C, dev)
-        if mask is None:
-            rc = L.wsplumb_rowbn_forward(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _p(y),
-                                         _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]),
-                                         _p(stats[4]), _p(ws), n, _stream(), *_run_args(running))
-        else:
-            n_rois = mask.shape[0]
-            assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
-            count = torch.empty((1,), dtype=torch.float32, device=dev)
-            fn = L.wsplumb_rowbn_forward_masked_pm if pos_major else L.wsplumb_rowbn_forward_masked
-            rc = fn(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _p(mask), n_rois, M // n_rois, _p(y),
-                    _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _p(count), _p(ws), n,
-                    _stream(), *_run_args(running))
-    if rc:
-        raise RuntimeError("wsplumb_rowbn_forward failed (%d)" % rc)
+        _check(L.wsplumb_rowbn_forward(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _pn(mask), n_rois,
+                                       M // n_rois if n_rois else 1, int(bool(pos_major) and n_rois > 0), _p(y),
+                                       _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _pn(count),
+                                       _p(ws), n, _stream(), *_run_args(running)), "wsplumb_rowbn_forward")
     return y, stats, count
 
 
@@ -158,31 +152,28 @@ def rowbn_apply(x, scale, shift, relu):
     y = torch.empty_like(x)
     with torch.cuda.device(x.device):
         rc = L.wsplumb_rowbn_apply(_p(x), M, C, _p(scale), _p(shift), int(relu), _p(y), _stream())
-    if rc:
-        raise RuntimeError("wsplumb_rowbn_apply failed (%d)" % rc)
+    _check(rc, "wsplumb_rowbn_apply")
     return y
+
+
+def _backward_outputs(L, x):
+    """dx, dwb [2, C] = (dweight, dbias), the coefficient scratch and the workspace (tensor, bytes) of a backward call"""
+    M, C = x.shape
+    dwb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    coef = torch.empty((3, C), dtype=torch.float32, device=x.device)
+    return torch.empty_like(x), dwb, coef, _workspace(L, M, C, x.device)
 
 
 def rowbn_backward(x, dy, weight, stats, relu, mask=None, pos_major=False):
     L = lib()
     M, C = x.shape
-    dev = x.device
-    dx = torch.empty_like(x)
-    dwb = torch.empty((2, C), dtype=torch.float32, device=dev)
-    coef = torch.empty((3, C), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, n = _workspace(L, M, C, dev)
-        if mask is None:
-            rc = L.wsplumb_rowbn_backward(_p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]),
-                                          _p(stats[3]), _p(stats[4]), int(relu), _p(dx), _p(dwb[0]),
-                                          _p(dwb[1]), _p(coef), _p(ws), n, _stream())
-        else:
-            n_rois = mask.shape[0]
-            fn = L.wsplumb_rowbn_backward_masked_pm if pos_major else L.wsplumb_rowbn_backward_masked
-            rc = fn(_p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]), _p(stats[3]), _p(stats[4]), int(relu),
-                    _p(mask), n_rois, M // n_rois, _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream())
-    if rc:
-        raise RuntimeError("wsplumb_rowbn_backward failed (%d)" % rc)
+    n_rois = mask.shape[0] if mask is not None else 0
+    with torch.cuda.device(x.device):
+        dx, dwb, coef, (ws, n) = _backward_outputs(L, x)
+        _check(L.wsplumb_rowbn_backward(_p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]), _p(stats[3]),
+                                        _p(stats[4]), int(relu), _pn(mask), n_rois, M // n_rois if n_rois else 1,
+                                        int(bool(pos_major) and n_rois > 0), _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef),
+                                        _p(ws), n, _stream()), "wsplumb_rowbn_backward")
     return dx, dwb[0], dwb[1]
 
 
@@ -206,16 +197,12 @@ def rowbn_backward_entry(x, dy, dys, possel, n_slots, weight, stats, mask=None):
     assert M == n_rois * per and dy.shape == x.shape and dys.shape == (n_slots * n_rois, C)
     assert dy.is_contiguous() and dys.is_contiguous() and possel.dtype == torch.int32 and possel.is_contiguous()
     assert mask is None or (mask.shape[0] == n_rois and mask.dtype == torch.float32 and mask.is_contiguous())
-    dx = torch.empty_like(x)
-    dwb = torch.empty((2, C), dtype=torch.float32, device=dev)
-    coef = torch.empty((3, C), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        ws, n = _workspace(L, M, C, dev)
-        rc = L.wsplumb_rowbn_backward_entry(_p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight), _p(stats[0]),
-                                            _p(stats[2]), _p(stats[3]), _p(stats[4]), _pn(mask), n_rois, per, _p(dx),
-                                            _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream())
-    if rc:
-        raise RuntimeError("wsplumb_rowbn_backward_entry failed (%d)" % rc)
+        dx, dwb, coef, (ws, n) = _backward_outputs(L, x)
+        _check(L.wsplumb_rowbn_backward_entry(_p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight), _p(stats[0]),
+                                              _p(stats[2]), _p(stats[3]), _p(stats[4]), _pn(mask), n_rois, per, _p(dx),
+                                              _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream()),
+               "wsplumb_rowbn_backward_entry")
     return dx, dwb[0], dwb[1]
 
 
@@ -224,10 +211,6 @@ def join_usable(x):
     if os.environ.get("WSSDL_HEAD_UNFUSED_JOIN"):          # A/B switch: separate norms and a torch add
         return False
     return usable(x)
-
-
-def _pn(t):
-    return _p(t) if t is not None else None
 
 
 def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
@@ -262,8 +245,7 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
                                           M // n_rois if n_rois else 1, _p(out), _p(y), _p(stats[0]),
                                           _p(stats[1]) if bns is not None else None, _p(stats[2]), _pn(count), _p(ws), n,
                                           _stream(), run_ptrs, run_mom, run_nbt)
-    if rc:
-        raise RuntimeError("wsplumb_rowbn_join_forward failed (%d)" % rc)
+    _check(rc, "wsplumb_rowbn_join_forward")
     return out, y, stats[0], stats[1], stats[2], count
 
 
@@ -287,8 +269,7 @@ def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, sta
                                            _p(stats3), _pn(ws_), _pn(stats_s), _pn(mask), n_rois,
                                            M // n_rois if n_rois else 1, _p(g), _p(dx3), _pn(dxs), _p(dwb[0]), _p(dwb[1]),
                                            _p(dwb[2]) if dual else None, _p(coef), _p(ws), n, _stream())
-    if rc:
-        raise RuntimeError("wsplumb_rowbn_join_backward failed (%d)" % rc)
+    _check(rc, "wsplumb_rowbn_join_backward")
     return g, dx3, dxs, dwb[0], dwb[1], dwb[2] if dual else None
 
 
@@ -460,9 +441,7 @@ def taps_usable(x):
 
 
 def _tap_call(name, *args):
-    rc = getattr(lib(), name)(*args, _stream())
-    if rc:
-        raise RuntimeError("%s failed (%d)" % (name, rc))
+    _check(getattr(lib(), name)(*args, _stream()), name)
 
 
 def tap_gather(x, plan, in_pm, R):

@@ -52,6 +52,17 @@ class _RowBatchNormFn(torch.autograd.Function):
         return dx, sum_dy_xhat, sum_dy, None
 
 
+def _side_outputs(ctx, count, placeholder, *side):
+    """Shared end of the fused Functions' forwards: the statistics and the live-row count they return next to the
+    activations carry no gradient.  Without a mask the count is a placeholder view of `placeholder` (unused: no extra
+    launch).  Returns the count to hand out."""
+    if count is None:
+        count = placeholder[0, :1]
+    ctx.mark_non_differentiable(*side, count)
+    ctx.set_materialize_grads(False)                   # no zero-filled gradients for the side outputs
+    return count
+
+
 class _FusedRowBatchNormFn(torch.autograd.Function):
     """The same layer (optionally with its ReLU) on the fused HIP kernels of
     csrc/plumbing/rowbn.hip: 3 passes over the tensor forward, 5 backward, instead of 5 + 14
@@ -61,24 +72,14 @@ class _FusedRowBatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, relu, roi_mask=None, pos_major=False, running=None):
         y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask, pos_major, running=running)
-        ctx.masked, ctx.pos_major = roi_mask is not None, pos_major
-        if ctx.masked:
-            ctx.save_for_backward(x, weight, stats, roi_mask)
-        else:
-            ctx.save_for_backward(x, weight, stats)
-            count = stats[0, :1]                       # placeholder (unused without a mask): no extra launch
-        ctx.relu = relu
+        ctx.save_for_backward(x, weight, stats, roi_mask)
+        ctx.relu, ctx.pos_major = relu, pos_major
         mean, var = stats[0], stats[1]
-        ctx.mark_non_differentiable(mean, var, count)
-        ctx.set_materialize_grads(False)               # no zero-filled gradients for mean / var / count
-        return y, mean, var, count
+        return y, mean, var, _side_outputs(ctx, count, stats, mean, var)
 
     @staticmethod
     def backward(ctx, dy, _dmean, _dvar, _dcount):
-        if ctx.masked:
-            x, weight, stats, roi_mask = ctx.saved_tensors
-        else:
-            (x, weight, stats), roi_mask = ctx.saved_tensors, None
+        x, weight, stats, roi_mask = ctx.saved_tensors
         if dy is None:
             dy = torch.zeros_like(x)
         dx, dw, db = _plumbing.rowbn_backward(x, dy.contiguous(), weight, stats, ctx.relu, roi_mask, ctx.pos_major)
@@ -99,13 +100,9 @@ class _JoinFn(torch.autograd.Function):
         dual = ws is not None
         out, y, st3, sts, stn, count = _plumbing.rowbn_join_forward(
             x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask, running=running)
-        ctx.dual, ctx.masked = dual, roi_mask is not None
+        ctx.dual = dual
         ctx.save_for_backward(x3, other if dual else None, out, w3, ws, wn, st3, sts, stn, roi_mask)
-        if count is None:
-            count = stn[0, :1]                         # placeholder (unused without a mask)
-        ctx.mark_non_differentiable(st3, sts, stn, count)
-        ctx.set_materialize_grads(False)
-        return out, y, st3, sts, stn, count
+        return out, y, st3, sts, stn, _side_outputs(ctx, count, stn, st3, sts, stn)
 
     @staticmethod
     def backward(ctx, dres, dy, *_):
@@ -135,12 +132,8 @@ class _EntryNormFn(torch.autograd.Function):
         ys = _pm_rows(y.view(r, h, w, -1), plan, s)
         ctx.save_for_backward(x, weight, stats, roi_mask)
         ctx.geom = (plan, s, h, w)
-        if count is None:
-            count = stats[0, :1]                       # placeholder (unused without a mask)
         mean, var = stats[0], stats[1]
-        ctx.mark_non_differentiable(mean, var, count)
-        ctx.set_materialize_grads(False)               # no zero-filled gradients for mean / var / count
-        return y, ys, mean, var, count
+        return y, ys, mean, var, _side_outputs(ctx, count, stats, mean, var)
 
     @staticmethod
     def backward(ctx, dy, dys, *_):
@@ -211,28 +204,21 @@ class RowBatchNorm(nn.Module):
             return F.relu(y) if relu else y
         # on the fused route the forward kernels update the running statistics themselves (run is not None)
         run = _plumbing.running_of(self) if fused else None
-        if _ROI_MASK is not None:
-            if fused and x.shape[0] % _ROI_MASK.shape[0] == 0:
-                y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), _ROI_MASK,
-                                                             bool(pos_major), run)
-                if run is not None:
-                    return y
-                n = n[0]
-            else:
-                y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, _ROI_MASK,
-                                                         pos_major)
-            self._track(mean, var, n)
-            return y
-        if fused:
-            y, mean, var, _ = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), None, False,
-                                                         run)
+        mask = _ROI_MASK
+        if fused and (mask is None or x.shape[0] % mask.shape[0] == 0):
+            y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), mask,
+                                                         bool(pos_major) and mask is not None, run)
             if run is not None:
                 return y
+            n = n[0] if mask is not None else x.shape[0]
+        elif mask is not None:
+            y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, mask, pos_major)
         else:
             y, mean, var = _RowBatchNormFn.apply(x, self.weight, self.bias, self.eps)
             if relu:
                 y = F.relu(y)
-        self._track(mean, var, x.shape[0])
+            n = x.shape[0]
+        self._track(mean, var, n)
         return y
 
     def _track(self, mean, var, n):
