@@ -490,6 +490,10 @@ WSSDL_API int wssdl_multi_task_loss_backward(
     const float *bbox_outside_w, int n_rows, int rows_total, int num_classes, const float *grad_losses,
     const void *workspace, float *grad_rpn_cls_score, float *grad_rpn_bbox_pred, float *grad_cls_score,
     float *grad_bbox_pred, wssdl_stream_t stream);
+/* y[i] = expf(x[i]) (which = 0) or log1pf(x[i]) (which = 1) for n f32 values on the device, computed by the
+ * library functions exactly as the loss kernels get them (same translation unit, same compiler flags): what the
+ * tests measure against f64 to fix the allowance of their error bounds. */
+WSSDL_API int wssdl_loss_libm_probe(const float *x, int64_t n, int which, float *y, wssdl_stream_t stream);
 
 /* ---------------------------------------------------------------------- f1 ---
  * MIL bag-instance selection: mil/core.py:11-46 (get_bag_logit) with the selectors

@@ -1,6 +1,7 @@
 """-m gpu: the fused multi-task loss op (csrc/loss.hip) against the oracle's
 f64 restatement of train_bus.py:186-235 / :605-647 and against the chain of torch ops it replaces
-(values and gradients)."""
+(values and gradients).
+The tolerances here stand on test_gpu_loss_reference.py: every element against f64 inside a counted bound."""
 import numpy as np
 import pytest
 

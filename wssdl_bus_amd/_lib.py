@@ -115,6 +115,7 @@ SYMBOLS = {
     "wssdl_multi_task_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wssdl_loss_libm_probe": (_i, [_vp, _i64, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -78,11 +78,6 @@ __device__ __forceinline__ long long rpn_target_off(const MtlArgs &x, long long 
     return ((n * C4 + ch) * x.H + h) * x.W + w;
 }
 
-__device__ __forceinline__ float log_sum_exp2(float a, float b) {
-    // (log1p of the smaller term: see lse_minus_max in common.hip.h)
-    return fmaxf(a, b) + log1pf(expf(-fabsf(a - b)));
-}
-
 // partials: [nb_cls] CE sums, [nb_cls] counts, [nb_box] box sums, then 3 values of the R-CNN block
 __global__ __launch_bounds__(MTL_BLOCK) void mtl_forward_kernel(MtlArgs x, double *__restrict__ partials) {
     __shared__ double scratch[MTL_BLOCK / 64];
@@ -185,9 +180,14 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_backward_kernel(MtlArgs x, cons
             float gb = 0.0f, gf = 0.0f;
             if (l >= 0) {
                 const float bg = x.rpn_cls_score[so], fg = x.rpn_cls_score[so + x.A];
-                const float lse = log_sum_exp2(bg, fg);
+                // softmax in the difference form expf((s_k - max) - lz), lz = log(sum) - max as in the forward: s_k - max
+                // is exactly 0 for the larger score and -|bg - fg| for the other.  Forming max + lz first would round
+                // ulp(|max|) / 2 into the exponent, an error that grows with the scores' common offset
+                const float dlt = -fabsf(bg - fg);
+                const float lz = log1pf(expf(dlt));
+                const float phi = expf(0.0f - lz), plo = expf(dlt - lz);
                 // (two classes: the label's component is minus the other class's probability)
-                const float pb = expf(bg - lse), pf = expf(fg - lse);
+                const float pb = (bg >= fg) ? phi : plo, pf = (bg >= fg) ? plo : phi;
                 gb = (l == 0 ? -pf : pb) * scale;
                 gf = (l == 1 ? -pb : pf) * scale;
             }
@@ -226,11 +226,11 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_backward_kernel(MtlArgs x, cons
                 const float *sc = x.cls_score + (size_t)r * x.K;
                 float m;
                 const float lz = lse_minus_max(sc, x.K, &m);
-                const float lse = m + lz;
-                // (the label's component as -(sum of the other probabilities): accurate when p_l -> 1)
+                // (difference form, see the RPN term above; the label's component as -(sum of the other
+                // probabilities): accurate when p_l -> 1)
                 float others = 0.0f;
                 for (int k = 0; k < x.K; ++k) {
-                    const float pk = expf(sc[k] - lse);
+                    const float pk = expf((sc[k] - m) - lz);
                     gc[k] = pk * sc_ce;
                     others += (k == l) ? 0.0f : pk;
                 }
@@ -247,6 +247,13 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_backward_kernel(MtlArgs x, cons
             }
         }
     }
+}
+
+// expf / log1pf as the kernels of this file get them, element by element (wssdl_loss_libm_probe)
+__global__ __launch_bounds__(MTL_BLOCK) void libm_probe_kernel(const float *__restrict__ x, long long n, int which,
+                                                               float *__restrict__ y) {
+    const long long i = (long long)blockIdx.x * MTL_BLOCK + threadIdx.x;
+    if (i < n) y[i] = which ? log1pf(x[i]) : expf(x[i]);
 }
 
 static int fill_args(MtlArgs *x, const float *rpn_cls_score, const int32_t *rpn_labels, const float *rpn_bbox_pred,
@@ -331,5 +338,13 @@ extern "C" int wssdl_multi_task_loss_backward(
     hipLaunchKernelGGL(mtl_backward_kernel, dim3(x.nb_cls + x.nb_box + row_blocks), dim3(MTL_BLOCK), 0, as_stream(stream), x,
                        static_cast<const MtlState *>(workspace), grad_losses, grad_rpn_cls_score, grad_rpn_bbox_pred,
                        grad_cls_score, grad_bbox_pred);
+    return check_launch();
+}
+
+extern "C" int wssdl_loss_libm_probe(const float *x, int64_t n, int which, float *y, wssdl_stream_t stream) {
+    if (n < 0 || n > 0x7fffffffLL || which < 0 || which > 1) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (n == 0) return WSSDL_OK;
+    if (!x || !y) return WSSDL_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(libm_probe_kernel, dim3(cdiv(n, MTL_BLOCK)), dim3(MTL_BLOCK), 0, as_stream(stream), x, n, which, y);
     return check_launch();
 }

@@ -110,12 +110,13 @@ __global__ __launch_bounds__(256) void mil_loss_backward_kernel(
     const float *s = logits + (size_t)r * K;
     float m;
     const float lz = lse_minus_max(s, K, &m);
-    const float lse = m + lz;
     const float c = grad_loss[0] * scale * cw.w[l] / (float)n_bags;
-    // the label's component is p_l - 1 = -(sum of the other probabilities): the sum keeps its accuracy when p_l -> 1
+    // softmax in the difference form expf((s_k - m) - lz): m + lz formed first would round ulp(|m|) / 2 into the
+    // exponent.  The label's component is p_l - 1 = -(sum of the other probabilities): the sum keeps its accuracy
+    // when p_l -> 1
     float others = 0.0f;
     for (int k = 0; k < K; ++k) {
-        const float pk = expf(s[k] - lse);
+        const float pk = expf((s[k] - m) - lz);
         g[k] = c * pk;
         others += (k == l) ? 0.0f : pk;
     }
