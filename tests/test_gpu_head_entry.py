@@ -6,7 +6,10 @@
 * Block 1's entry gradient (csrc/plumbing/rowbn.hip: wsplumb_rowbn_backward_entry, networks/roi_head.py:
   _EntryNormFn) against the sequence it replaces -- torch's zero-fill, index_add and add, then the plain
   backward -- and the head against its WSSDL_HEAD_UNFUSED_ENTRY=1 route.  torch.equal throughout: the kernels
-  keep every operand and the order of every sum."""
+  keep every operand and the order of every sum.
+
+These route-against-route comparisons stand on test_gpu_headconv_reference.py, which holds both patch routes to a
+plain f64 convolution element by element."""
 import copy
 
 import pytest

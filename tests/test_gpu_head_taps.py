@@ -1,7 +1,10 @@
 """-m gpu: the per-RoI head's 3x3 convolutions over their valid taps only (csrc/plumbing/taps.hip,
 networks/_plumbing.py: TapPlan / TapConv3x3Fn, networks/roi_head.py: the position-major 4x4 section).
 Kernels against the dense patch route (im2col.hip) they replace; the head against its dense route
-(WSSDL_HEAD_DENSE_3X3=1)."""
+(WSSDL_HEAD_DENSE_3X3=1).
+
+These route-against-route comparisons and their 1e-4 tolerance stand on test_gpu_headconv_reference.py, which holds
+both routes to a plain f64 convolution element by element, within bounds counted from the arithmetic."""
 import copy
 
 import pytest
