@@ -260,6 +260,10 @@ def _compare_heads(torch, depth, R, mode, monkeypatch):
 @pytest.mark.parametrize("R", [300, 2000])
 @pytest.mark.parametrize("mode", ["train", "eval", "masked"])
 def test_head_taps_match_dense_route(torch_cuda, depth, R, mode, monkeypatch):
+    """The position-major route against the dense route of the same head, at 1e-4 of each tensor's largest value.
+    Both sides share the head's wiring (shortcut inputs, the norm a join applies, slot order, the final mean, the
+    buffers' n / eps / momentum); that wiring, and the tolerance's footing, stand on
+    test_gpu_network_reference.py, which holds both routes to the f64 statement of tests/network_reference.py."""
     _compare_heads(torch_cuda, depth, R, mode, monkeypatch)
 
 

@@ -89,6 +89,10 @@ def test_roi_pool_ignores_dead_rows(torch_cuda):
 
 
 def test_head_masked_batch_norm_matches_compact_rows(torch_cuda):
+    """The masked head against the same head on the compacted rows: two routes of networks/roi_head.py, so the 2e-3 /
+    5e-3 here say that the mask changes nothing but the rounding.  That either side computes the reference's network
+    at all, with garbage in the dead rows, stands on test_gpu_network_reference.py (masked cases against the f64
+    statement of tests/network_reference.py on the compacted rows)."""
     torch = torch_cuda
     from wssdl_bus_amd.networks import roi_head
     torch.manual_seed(0)

@@ -11,7 +11,12 @@ both_preact boundaries (no residual gradient) and the final-norm join.
 The trunk's convolutions are MIOpen's, and at these shapes its default solvers do not reproduce their own results
 from one call to the next (two runs of the SAME route differed in about 80 of 83 tensors at 6e-7 relative), so no
 bit-level comparison of two runs would mean anything; the `deterministic_convs` fixture asks for the deterministic
-solvers, under which the separate-layer route reproduces itself bit for bit and the joins must equal it."""
+solvers, under which the separate-layer route reproduces itself bit for bit and the joins must equal it.
+
+Both sides are routes of backbones.py and share its wiring (which tensor a shortcut takes, the norm a join applies as
+`nxt`, the hand-over of `pre`, the buffers updated); the reference this bitwise comparison stands on is
+test_gpu_network_reference.py, which holds the join route to the f64 statement of the trunk in
+tests/network_reference.py."""
 import copy
 
 import pytest
