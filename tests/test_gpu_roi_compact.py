@@ -836,3 +836,74 @@ def test_oversized_roi_flags_and_i32_fallback(torch_cuda):
     finally:
         cfg.ROI_POOL_FLAG_CHECK = old
         op.flags_raised()
+
+
+def test_timeline_records_and_plan_segments_of_every_form(torch_cuda):
+    """bench.py reads the timeline records of the RoI-pool pair by name and meta key: every form of the pair, run
+    through RoiPoolFunction with cfg forced, emits exactly these records in this order.  And a plan carries its own
+    segment count: roi_pool_grad_compact(plan=p) without segments= is the call with segments=p.segments, bit for bit."""
+    torch = torch_cuda
+    from wssdl_bus_amd import _lib
+    from wssdl_bus_amd.fast_rcnn.config import cfg
+    from wssdl_bus_amd.roi_pooling_layer import roi_pooling_op as op
+    N, H, W, C = 2, 12, 17, 256
+    rs = np.random.RandomState(7)
+    ft = torch.from_numpy(np.maximum(rs.normal(size=(N, H, W, C)), 0).astype(np.float32)).cuda()
+    rois = {R: torch.from_numpy(_rois_for(rs, R, N, H, W)).cuda() for R in (1024, 64)}    # 1024: the smallest list that takes the window table
+    shape, pooling = ["C", "H", "N", "R", "W"], ["C", "H", "N", "R", "W", "argmax_bytes"]
+    prepare = ("roi_pool_backward_prepare", shape)
+    exact_bwd = [prepare, ("roi_pool_backward", sorted(pooling + ["plan"]))]
+    forms = [
+        # (R, forced cfg, records of the forward, records of the backward)
+        (64, {}, [("roi_pool_forward", pooling)], None),
+        (1024, dict(ROI_POOL_FWD_BLOCKS=False), [("roi_pool_forward_windows", ["R"]), ("roi_pool_forward", pooling)], None),
+        (1024, dict(ROI_POOL_FWD_BLOCKS=True),
+         [("roi_pool_forward_windows", ["R"]), ("roi_pool_forward_blocks_prepare", shape),
+          ("roi_pool_forward", sorted(pooling + ["blocks"]))], None),
+        (1024, dict(ROI_POOL_BWD_EXACT=True), None, exact_bwd),
+        (1024, dict(ROI_POOL_BWD_OWNER=-1, ROI_POOL_BWD_SPLIT=4), None,
+         [prepare, ("roi_pool_backward", sorted(pooling + ["plan", "segments"]))]),
+        (1024, dict(ROI_POOL_BWD_OWNER=9, ROI_POOL_BWD_OWNER_SEGMENTS=1), None,
+         [("roi_pool_backward_prepare", sorted(shape + ["owner"])), ("roi_pool_backward", sorted(pooling + ["owner"]))]),
+        (1024, dict(ROI_POOL_BWD_OWNER=9, ROI_POOL_BWD_OWNER_SEGMENTS=2), None,
+         [("roi_pool_backward_prepare", sorted(shape + ["owner"])),
+          ("roi_pool_backward", sorted(pooling + ["owner", "owner_segments"]))]),
+        (1024, dict(ROI_POOL_COMPACT_ARGMAX=False), [("roi_pool_forward", shape)], [("roi_pool_backward", shape)]),
+    ]
+    keys = ("ROI_POOL_FWD_BLOCKS", "ROI_POOL_BWD_EXACT", "ROI_POOL_BWD_OWNER", "ROI_POOL_BWD_SPLIT",
+            "ROI_POOL_BWD_OWNER_SEGMENTS", "ROI_POOL_COMPACT_ARGMAX", "ROI_POOL_ANNOUNCE_BWD_FORM")
+    old = {k: cfg[k] for k in keys}
+    try:
+        cfg.ROI_POOL_ANNOUNCE_BWD_FORM = False
+        for R, forced, want_fwd, want_bwd in forms:
+            for k in keys[:-1]:
+                cfg[k] = forced.get(k, old[k])
+            _lib.timeline.reset(True)
+            x = ft.clone().requires_grad_(True)
+            top, _ = op.RoiPoolFunction.apply(x, rois[R], 7, 7, 1.0 / 16, None)
+            top.sum().backward()
+            got = [(name, sorted(meta)) for name, _, _, meta in _lib.timeline.records]
+            fwd = [r for r in got if r[0].startswith("roi_pool_forward")]
+            bwd = [r for r in got if r[0].startswith("roi_pool_backward")]
+            assert got == fwd + bwd, (forced, got)                                   # nothing else, forward first
+            assert want_fwd is None or fwd == want_fwd, (forced, fwd)
+            assert want_bwd is None or bwd == want_bwd, (forced, bwd)
+            assert x.grad is not None and bool(torch.isfinite(x.grad).all())
+        # the plan's own segment count: the split form (4 segments on the plan it wants) and the exact form
+        top, arg8 = op.roi_pool_compact(ft, rois[1024], 7, 7, 1.0 / 16)
+        wt = torch.from_numpy(rs.normal(size=tuple(top.shape)).astype(np.float32)).cuda()
+        for forced, segs in ((dict(ROI_POOL_BWD_OWNER=-1, ROI_POOL_BWD_SPLIT=4), 4), (dict(ROI_POOL_BWD_EXACT=True), 1)):
+            for k in keys[:-1]:
+                cfg[k] = forced.get(k, old[k])
+            p = op.prepare_backward((N, H, W, C), rois[1024], 7, 7, 1.0 / 16)
+            assert p.segments == segs and p.plan >= 0 and p.owner < 0
+            _lib.timeline.reset(True)
+            a = op.roi_pool_grad_compact((N, H, W, C), rois[1024], arg8, wt, 7, 7, 1.0 / 16, plan=p)
+            assert _lib.timeline.records[-1][3].get("segments", 1) == segs          # ... is the form that ran
+            b = op.roi_pool_grad_compact((N, H, W, C), rois[1024], arg8, wt, 7, 7, 1.0 / 16, plan=p, segments=p.segments)
+            assert torch.equal(a, b), forced
+        assert not op.flags_raised()
+    finally:
+        for k in keys:
+            cfg[k] = old[k]
+        _lib.timeline.reset(False)

@@ -55,7 +55,7 @@ def chain():
     r = out[0].contiguous()
     top, arg8 = op.roi_pool_compact(feat, r, 7, 7, 1.0 / 16)
     plan = op.prepare_backward(tuple(feat.shape), r, 7, 7, 1.0 / 16)
-    g = op.roi_pool_grad_compact(tuple(feat.shape), r, arg8, top, 7, 7, 1.0 / 16, plan=plan, segments=plan.segments)
+    g = op.roi_pool_grad_compact(tuple(feat.shape), r, arg8, top, 7, 7, 1.0 / 16, plan=plan)
     return at[0], r, top, g
 
 

@@ -63,7 +63,7 @@ for (S, WS, H, W, C, blocks) in ((4, 4, 38, 63, 1024, -1), (0, 2, 38, 63, 1024, 
             plan = op.prepare_backward(tuple(feat.shape), r, 7, 7, 1.0 / 16)
             torch.cuda.synchronize()
             say("  backward lists ok:", plan.variant[:40])
-            g = op.roi_pool_grad_compact(tuple(feat.shape), r, arg8, top, 7, 7, 1.0 / 16, plan=plan, segments=plan.segments)
+            g = op.roi_pool_grad_compact(tuple(feat.shape), r, arg8, top, 7, 7, 1.0 / 16, plan=plan)
             torch.cuda.synchronize()
             say("  RoI pool backward ok")
             op.check_flags()

@@ -48,7 +48,7 @@ for N, H, W, C, R in ((2, 38, 63, 256, 256), (2, 38, 63, 1024, 256), (4, 38, 63,
 
         def lists():
             p = op.prepare_backward(shape, rois, 7, 7, 1.0 / 16)
-            return op.roi_pool_grad_compact(shape, rois, arg8, diff, 7, 7, 1.0 / 16, plan=p, segments=p.segments)
+            return op.roi_pool_grad_compact(shape, rois, arg8, diff, 7, 7, 1.0 / 16, plan=p)
 
         def nolists():
             return op.roi_pool_grad_compact(shape, rois, arg8, diff, 7, 7, 1.0 / 16, use_workspace=False)

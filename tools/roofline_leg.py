@@ -92,7 +92,7 @@ def run(rois_np, N, H, W, C, iters=20, warmup=3, seed=3):
             if compact:
                 op.roi_pool_compact(feat, rois, 7, 7, 1.0 / 16)
                 p = op.prepare_backward(shape, rois, 7, 7, 1.0 / 16)
-                return op.roi_pool_grad_compact(shape, rois, arg, diff, 7, 7, 1.0 / 16, plan=p, segments=p.segments)
+                return op.roi_pool_grad_compact(shape, rois, arg, diff, 7, 7, 1.0 / 16, plan=p)
             op.roi_pool(feat, rois, 7, 7, 1.0 / 16)
             return op.roi_pool_grad(feat, rois, arg, diff, 7, 7, 1.0 / 16)
         for _ in range(warmup):

@@ -478,26 +478,10 @@ static int launch_bwd(const float *top_diff, const int *argmax, const float *roi
     if (blocks > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
     int cshift = 0;
     while ((1 << cshift) < C) ++cshift;
-    const bool cpow2 = (1 << cshift) == C;
-    // cell / W for every cell < H*W by one 24-bit multiply: (cell * magic) >> shift with
-    // cell, magic < 2^24 and cell * magic < 2^32; verified exhaustively (H*W is small)
-    FastDiv dw;
-    dw.magic = 0;
-    dw.shift = 0;
-    bool fast = cpow2 && (long long)H * W < (1 << 16);
-    if (fast) {
-        const unsigned cells = (unsigned)H * (unsigned)W;
-        bool found = false;
-        for (int sft = 8; sft <= 24 && !found; ++sft) {
-            unsigned long long mg = ((1ULL << sft) + (unsigned)W - 1) / (unsigned)W;
-            if (mg >= (1ULL << 24) || mg * (cells ? cells - 1 : 0) >= (1ULL << 32)) continue;
-            bool exact = true;
-            for (unsigned n = 0; n < cells && exact; ++n)
-                exact = (unsigned)((n * mg) >> sft) == n / (unsigned)W;
-            if (exact) { dw.magic = (unsigned)mg; dw.shift = sft; found = true; }
-        }
-        fast = found;
-    }
+    FastDiv dw = {0u, 0};
+    unsigned shift = 0;
+    const bool fast = (1 << cshift) == C && fast_div_by_width(H, W, &dw.magic, &shift);
+    dw.shift = (int)shift;
     if (fast)
         hipLaunchKernelGGL((roi_pool_bwd_kernel<TH, TW, CG, CHUNK, true, MAXB, MINB>), dim3((unsigned)blocks),
                            dim3(CG), 0, st, top_diff, argmax, rois, R, N, H, W, C, PH, PW, scale,
@@ -621,15 +605,7 @@ extern "C" int wssdl_roi_pool_backward(const float *top_diff, const int32_t *arg
     // re-read MORE bytes than 4x8 tiles (32 KiB, 16 waves per CU) and are 5-9 % faster; 8x8
     // tiles (8 waves per CU) re-read 18 % less and are 50-70 % slower whatever the depth of
     // their load batches.
-    // Channels per workgroup: 256 when that still yields enough workgroups to fill the chip,
-    // fewer otherwise (small batches / narrow feature maps).
-    int cg = C > 128 ? 256 : (C > 64 ? 128 : 64);
-    const long long tiles = (long long)cdiv(H, 4) * cdiv(W, 8);       // counted in 4x8 tiles
-    while (cg > 64 && (long long)N * cdiv(C, cg) * tiles < BWD_MIN_WORKGROUPS) cg >>= 1;
-    {       // tuning override
-        const int v = tuning().roi_bwd_cg;
-        if (v == 64 || v == 128 || v == 256) cg = v;
-    }
+    const int cg = fallback_channel_group(N, H, W, C);
     if (cg == 256)
         return launch_bwd<4, 4, 256, 254, 8, 8>(top_diff, argmax, rois, R, N, H, W, C, pooled_h, pooled_w,
                                                 spatial_scale, bottom_diff, st);

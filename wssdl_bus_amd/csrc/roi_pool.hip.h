@@ -70,7 +70,6 @@ __device__ __forceinline__ void cand_range(int d, float bin, int P, int &s, int 
 }
 
 constexpr unsigned TOUCH_GENERIC = 0xfu;
-constexpr long long BWD_MIN_WORKGROUPS = 1024;   // one per workgroup slot of the chip (256 CUs x 4)
 
 template <int TN, int FW = 8>
 __device__ __forceinline__ void touch_axis(int t0, int t1, int rs, int re, float bin, int P, int &p0,
@@ -98,6 +97,49 @@ __device__ __forceinline__ void touch_axis(int t0, int t1, int rs, int re, float
             if (a + k >= s[j] && a + k < e[j]) mask |= 1ull << (FW * k + j);
 }
 
+
+// ---- host rules shared by the launchers -----------------------------------------------------------
+// XCD grid: workgroup b runs on XCD b % 8 (observed), and a kernel that cuts the channels into `slices` wants every
+// workgroup of a slice on the same XCD, so that one L2 holds only that slice of the feature map.  The slices deal
+// evenly over the 8 XCDs when their number is a multiple or a divisor of 8; the grid then carries `groups` groups of
+// work per slice.  These two functions are the host half of three device decodes of blockIdx.x, which they must
+// agree with: roi_pool_fwd_rows_kernel (roi_pool_compact.hip: "blockIdx -> (channel slice, group of RPW items)"),
+// roi_pool_fwd_blocks_kernel (roi_pool_blocks.hip, the same decode) and the three-branch decode at the top of
+// roi_pool_bwd_walk_kernel (roi_pool_walk.hip), whose third branch -- a slice count that is neither -- is the plain
+// groups * slices grid with no XCD placement; the two forwards do not take such a shape (xcd_sliceable).
+inline bool xcd_sliceable(int slices) { return (slices >= 8 && slices % 8 == 0) || (slices > 0 && slices < 8 && 8 % slices == 0); }
+inline long long xcd_grid(long long groups, int slices) {
+    if (slices < 8 && xcd_sliceable(slices)) return 8 * ((groups + 8 / slices - 1) / (8 / slices));   // 8 / slices groups per XCD round
+    return groups * slices;
+}
+
+// cell / W for every cell < H * W by one 24-bit multiply: (cell * magic) >> shift with cell, magic < 2^24 and
+// cell * magic < 2^32 (one full-rate v_mul_u32_u24 on the device); verified exhaustively, H * W < 2^16 is small
+inline bool fast_div_by_width(int H, int W, unsigned *magic, unsigned *shift) {
+    if ((long long)H * W >= (1 << 16)) return false;
+    const unsigned cells = (unsigned)H * (unsigned)W;
+    for (unsigned sft = 8; sft <= 24; ++sft) {
+        const unsigned long long mg = ((1ULL << sft) + (unsigned)W - 1) / (unsigned)W;
+        if (mg >= (1ULL << 24) || mg * (cells ? cells - 1 : 0) >= (1ULL << 32)) continue;
+        bool exact = true;
+        for (unsigned n = 0; n < cells && exact; ++n) exact = (unsigned)((n * mg) >> sft) == n / (unsigned)W;
+        if (exact) { *magic = (unsigned)mg;  *shift = sft;  return true; }
+    }
+    return false;
+}
+
+// channels per workgroup of the two tile-owner fallback backwards (roi_pool.hip, roi_pool_compact.hip): 256 when that
+// still yields enough workgroups to fill the chip, fewer otherwise (small batches / narrow feature maps);
+// "roi_bwd_cg" overrides
+constexpr long long BWD_MIN_WORKGROUPS = 1024;   // one per workgroup slot of the chip (256 CUs x 4)
+inline int fallback_channel_group(int N, int H, int W, int C) {
+    const int v = tuning().roi_bwd_cg;
+    if (v == 64 || v == 128 || v == 256) return v;
+    int cg = C > 128 ? 256 : (C > 64 ? 128 : 64);
+    const long long tiles = (long long)cdiv(H, 4) * cdiv(W, 8);       // counted in 4x8 tiles
+    while (cg > 64 && (long long)N * cdiv(C, cg) * tiles < BWD_MIN_WORKGROUPS) cg >>= 1;
+    return cg;
+}
 
 // wave-uniform forward with the i32 arg-max (roi_pool_compact.hip); WSSDL_ROWS_I32_UNSUPPORTED = shape not taken
 constexpr int WSSDL_ROWS_I32_UNSUPPORTED = -1000;

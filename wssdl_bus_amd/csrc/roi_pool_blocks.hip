@@ -70,8 +70,7 @@ void blocks_zero_region(void *ws, int R, int N, int H, int W, int C, unsigned **
 bool blocks_supported(int R, int N, int H, int W, int C, int PH, int PW) {
     if (PH != 7 || PW != 7 || R < 1 || N < 1 || H < 4 || W < 4 || H > 255 || W > 255) return false;
     if (C % 256 != 0) return false;
-    const int slices = C / 256;
-    if (!((slices >= 8 && slices % 8 == 0) || (slices < 8 && 8 % slices == 0))) return false;
+    if (!xcd_sliceable(C / 256)) return false;
     if ((long long)BLK_TABLES * H * W * C * 4 >= 0x7fffffffLL) return false;       // one buffer resource per image
     if ((long long)N * H * W * C * 4 >= 0x7fffffffLL) return false;                    // ... and one over the map (table build)
     if ((long long)R * 7 >= 0x7fffffffLL || (long long)N * H > (1 << 16)) return false;
@@ -439,7 +438,7 @@ extern "C" int wssdl_roi_pool_forward_compact_blocks(const float *bottom, int N,
     const int parts = (tp == 1 || tp == 4 || tp == 7) ? tp : 2;
     const int slices = C / 256, rpw = 4;
     const long long groups = ((long long)R * 7 * parts + rpw - 1) / rpw;
-    const long long nblocks = slices >= 8 ? groups * slices : 8 * ((groups + 8 / slices - 1) / (8 / slices));
+    const long long nblocks = xcd_grid(groups, slices);
     if (nblocks > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
     const unsigned *order = tuning().roi_fwd_blocks_sort != 0 ? L.order : nullptr;
 #define WSSDL_BLOCKS_LAUNCH(P) \

@@ -749,12 +749,37 @@ extern "C" int wssdl_roi_pool_compact_supported(int H, int W, int C, int pooled_
     return compact_supported(H, W, C, pooled_h, pooled_w) ? 1 : 0;
 }
 
+// ---- argument checks shared by the entry points of the 1-byte path --------------------------------
+// Shape, rounding mode and the empty call, in the order every entry point decides them.  Returns ARGS_PROCEED or the
+// status the entry point returns at once (WSSDL_OK: a no-op).  n_min: 1 where an empty batch is an error (the
+// prepare steps and the table builds), 0 where it is accepted; `noop`: which empty dimension makes the call a no-op
+// -- N == 0 for a backward (no bottom_diff to write), R == 0 for a forward (no top to write).  Pointers, alignment
+// and workspace sizes are each entry point's own.
+constexpr int ARGS_PROCEED = -1;
+enum NoOp { NOOP_NEVER, NOOP_N0, NOOP_R0 };
+static int check_compact_args(int N, int n_min, int R, int H, int W, int C, int PH, int PW, int rounding, NoOp noop) {
+    if (N < n_min || R < 0 || !compact_supported(H, W, C, PH, PW)) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
+    if ((noop == NOOP_N0 && N == 0) || (noop == NOOP_R0 && R == 0)) return WSSDL_OK;
+    return ARGS_PROCEED;
+}
+
+// the tensors of a backward: bottom_diff always, the others when there is a RoI to read
+static bool backward_pointers_ok(const void *top_diff, const void *argmax, const void *rois, int R, const void *bottom_diff) {
+    return bottom_diff && (R == 0 || (top_diff && argmax && rois));
+}
+
+// scratch of the owner forms: present, large enough, 16-byte aligned like the bottom_diff it is merged into
+static bool owner_scratch_ok(const void *scratch, size_t scratch_bytes, size_t need, const void *bottom_diff) {
+    return scratch && scratch_bytes >= need && !(reinterpret_cast<uintptr_t>(scratch) & 15) &&
+           !(reinterpret_cast<uintptr_t>(bottom_diff) & 15);
+}
+
 // windows table: 7 x 7 bins and a shape the wave-uniform kernel takes with 256-channel waves
 static bool window_table_supported(int H, int W, int C, int pooled_h, int pooled_w) {
     if (!compact_supported(H, W, C, pooled_h, pooled_w) || pooled_h != 7 || pooled_w != 7) return false;
     if (C % 256 != 0 || H > 255 || W > 255) return false;
-    const int slices = C / 256;
-    return ((slices >= 8 && slices % 8 == 0) || (slices < 8 && 8 % slices == 0)) && (long long)H * W * C * 4 < 0x7fffffffLL;
+    return xcd_sliceable(C / 256) && (long long)H * W * C * 4 < 0x7fffffffLL;
 }
 
 extern "C" size_t wssdl_roi_pool_forward_windows_bytes(int R, int H, int W, int C, int pooled_h, int pooled_w) {
@@ -765,9 +790,8 @@ extern "C" size_t wssdl_roi_pool_forward_windows_bytes(int R, int H, int W, int 
 extern "C" int wssdl_roi_pool_forward_windows(const float *rois, int R, int N, int H, int W, int C, int pooled_h,
                                               int pooled_w, float spatial_scale, int rounding, void *table,
                                               size_t table_bytes, int32_t *overflow, wssdl_stream_t stream) {
-    if (R < 0 || N < 1 || !window_table_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (R == 0) return WSSDL_OK;
+    if (!window_table_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_compact_args(N, 1, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_R0); rc != ARGS_PROCEED) return rc;
     if (!rois || !table || (reinterpret_cast<uintptr_t>(table) & 31)) return WSSDL_ERR_INVALID_ARGUMENT;
     if (table_bytes < wssdl_roi_pool_forward_windows_bytes(R, H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_WORKSPACE;
     hipLaunchKernelGGL(roi_windows_kernel, dim3(cdiv((long long)R * 7, 256)), dim3(256), 0, as_stream(stream), rois, R, N,
@@ -779,10 +803,9 @@ extern "C" int wssdl_roi_pool_forward_windows_blocks(const float *rois, int R, i
                                                      int pooled_w, float spatial_scale, int rounding, void *table,
                                                      size_t table_bytes, int32_t *overflow, void *blocks,
                                                      size_t blocks_bytes, wssdl_stream_t stream) {
-    if (R < 1 || N < 1 || !window_table_supported(H, W, C, pooled_h, pooled_w) ||
-        !blocks_supported(R, N, H, W, C, pooled_h, pooled_w))
-        return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (!window_table_supported(H, W, C, pooled_h, pooled_w) || !blocks_supported(R, N, H, W, C, pooled_h, pooled_w))
+        return WSSDL_ERR_INVALID_ARGUMENT;           // (blocks_supported: R >= 1 too -- no empty call here)
+    if (const int rc = check_compact_args(N, 1, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_NEVER); rc != ARGS_PROCEED) return rc;
     if (!rois || !table || (reinterpret_cast<uintptr_t>(table) & 31) || !blocks || (reinterpret_cast<uintptr_t>(blocks) & 255))
         return WSSDL_ERR_INVALID_ARGUMENT;
     if (table_bytes < wssdl_roi_pool_forward_windows_bytes(R, H, W, C, pooled_h, pooled_w) ||
@@ -796,9 +819,126 @@ extern "C" int wssdl_roi_pool_forward_windows_blocks(const float *rois, int R, i
     return check_launch();
 }
 
+// ---- forward dispatch: the decision ... -----------------------------------------------------------
+// What a forward launches: the wave-uniform kernel roi_pool_fwd_rows_kernel<cpl, rpw, pws, whole, table, i32, sp> on
+// an XCD grid of `blocks` workgroups, or (SLICED) the round-1 kernel with two bin rows per wave, which takes every
+// shape.
+struct FwdPlan {
+    enum Family { SLICED, ONE_BIN, ROWS } family;
+    int cpl;        // channels per lane: 4 = 256-channel waves, 2 = 128-channel waves
+    int rpw;        // waves per workgroup
+    int pws;        // 7: pooled_w == 7 known at compile time (shared columns, the stores of a row together), else 0
+    int sp;         // ONE_BIN: waves per bin row (7 = a bin each, 4), else 0
+    bool whole;     // a wave walks a whole RoI instead of one bin row
+    int slices;     // channel slices of 64 * cpl
+    long long blocks;
+};
+
+// "roi_fwd_variant": 0 = automatic, 1 = one bin row per wave with a store per bin, 2 = 128-channel waves, 3 = 7
+// one-row waves per workgroup, 4 = one bin row per wave, 5 = a whole RoI per wave, 9 = the sliced round-1 form.
+// `table`: the windows come from the table of roi_windows_kernel (variant 0 then).  `i32`: the reference op's own
+// arg-max (wssdl_roi_pool_forward), which takes the automatic choice with three differences kept from its own
+// launcher: always one wave per bin on a small launch, "roi_fwd_one_bin" + 100 does not reach it, and 128-channel
+// waves know pooled_w == 7 at compile time.
+static FwdPlan plan_forward(int R, int H, int W, int C, int pooled_h, int pooled_w, int variant, bool table, bool i32) {
+    FwdPlan p = {FwdPlan::SLICED, 4, 4, 0, 0, false, 0, 0};
+    const bool map_ok = (long long)H * W * C * 4 < 0x7fffffffLL;       // one buffer resource over an image
+    // a test-sized RoI list (R = 300: 8400 one-row waves) is latency-bound: 0.087 ms on one-row waves, 0.067 on the sliced
+    // kernel (which spreads a bin row over more lanes), 0.056-0.062 on one wave per bin (below) at 63 x 100 x 1024
+    const bool small_launch = variant == 0 && !table && (long long)R * pooled_h * cdiv(C, 256) < 32768;
+    // Small launches (round 6): one wave per BIN.  A launch of R * PH * C / 256 < 32768 one-row waves leaves SIMDs idle and each
+    // wave walks a chain of 7 bins; split seven ways the waves are 7 x as many and a seventh as long.  Same scan per bin, same
+    // bits.  R x C sweep against the sliced kernel (profiles/r06_small_forward_one_bin_sweep.log): 0.45-0.86 x the time
+    // everywhere below the bound, 0.96-1.02 x at it, 1.3 x beyond (where the rows kernel takes over).  "roi_fwd_one_bin":
+    // 7 (default) / 4 = waves per bin row, 0 = the sliced kernel, + 100 = also beyond the bound (experiments).
+    const int split = tuning().roi_fwd_one_bin;
+    const bool beyond = !i32 && split >= 100 && variant == 0 && !table;
+    if ((small_launch || beyond) && split > 0 && C % 256 == 0 && map_ok && xcd_sliceable(C / 256)) {
+        // SPLIT waves per bin row: R * PH * SPLIT * C / 256 waves with ceil(PW / SPLIT) bins each
+        p.sp = (i32 || split % 100 >= 7) ? 7 : 4;
+        p.slices = C / 256;
+        p.blocks = xcd_grid(((long long)R * pooled_h * p.sp + 3) / 4, p.slices);
+        if (p.blocks <= 0x7fffffffLL) { p.family = FwdPlan::ONE_BIN;  return p; }
+        p.sp = 0;
+    }
+    if (variant == 9 || small_launch) return p;          // (a small launch the one-bin form does not take: the sliced kernel)
+    // wave-uniform kernel, 256 (or 128) channels per wave
+    p.cpl = (variant == 2 || C % 256 != 0) ? 2 : 4;
+    p.slices = cdiv(C, 64 * p.cpl);
+    p.rpw = (variant == 3 && p.cpl == 4) ? 7 : 4;
+    if (!xcd_sliceable(p.slices) || !map_ok) return p;
+    // a wave walks a whole RoI when that still gives every SIMD its 8 waves (R * slices >= 8192),
+    // else one (roi, ph) bin row; pooled_w == 7 is known at compile time: the stores of a row are
+    // issued together
+    const bool many = (long long)R * p.slices >= 8192;
+    p.whole = pooled_w == 7 && variant == 5 && many;      // (measured slower: 0.80 against 0.57 ms)
+    if (p.whole || table) p.pws = 7;
+    else if (p.rpw == 7) p.pws = 0;
+    else if (p.cpl == 2) p.pws = (i32 && pooled_w == 7) ? 7 : 0;
+    else p.pws = ((variant == 0 || variant == 4) && pooled_w == 7) ? 7 : 0;
+    const long long items = p.whole ? (long long)R : (long long)R * pooled_h;
+    p.blocks = xcd_grid((items + p.rpw - 1) / p.rpw, p.slices);
+    if (p.blocks <= 0x7fffffffLL) p.family = FwdPlan::ROWS;
+    return p;
+}
+
+// ---- ... and the launch.  Every instantiation of the wave-uniform kernel the library carries, one per line:
+//   X(channels per lane, waves per workgroup, PW at compile time, whole RoI, window table, i32 arg-max, waves per bin row)
+#define WSSDL_FWD_ROWS_KERNELS(X) \
+    X(4, 4, 0, false, false, false, 7)  /* one wave per bin (small launches) */ \
+    X(4, 4, 0, false, false, false, 4)  \
+    X(4, 4, 7, false, true, false, 0)   /* the default on a train-sized list: windows from the table */ \
+    X(4, 4, 7, false, false, false, 0)  /* ... computed in the kernel */ \
+    X(4, 4, 0, false, false, false, 0)  \
+    X(4, 7, 0, false, false, false, 0)  \
+    X(4, 4, 7, true, false, false, 0)   \
+    X(2, 4, 7, true, false, false, 0)   \
+    X(2, 4, 0, false, false, false, 0)  \
+    X(4, 4, 0, false, false, true, 7)   /* the same forms with the reference op's i32 arg-max */ \
+    X(4, 4, 7, false, false, true, 0)   \
+    X(4, 4, 0, false, false, true, 0)   \
+    X(2, 4, 7, false, false, true, 0)   \
+    X(2, 4, 0, false, false, true, 0)
+
+static int launch_fwd_rows(const FwdPlan &p, bool i32, const float *bottom, int N, int H, int W, int C, const float *rois,
+                           int R, int pooled_h, int pooled_w, float spatial_scale, int rounding, float *top,
+                           unsigned char *arg, int32_t *overflow, const unsigned *table, hipStream_t st) {
+#define WSSDL_X(CPL, RPW, PWS, WHOLE, TAB, I32, SP) \
+    if (p.cpl == CPL && p.rpw == RPW && p.pws == PWS && p.whole == WHOLE && (table != nullptr) == TAB && i32 == I32 && p.sp == SP) { \
+        hipLaunchKernelGGL((roi_pool_fwd_rows_kernel<CPL, RPW, PWS, WHOLE, TAB, I32, SP>), dim3((unsigned)p.blocks), dim3(64 * RPW), 0, \
+                           st, bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, arg, overflow, \
+                           p.slices, table); \
+        return check_launch(); \
+    }
+    WSSDL_FWD_ROWS_KERNELS(WSSDL_X)
+#undef WSSDL_X
+    return WSSDL_ERR_INVALID_ARGUMENT;       // (a window table with a form that does not read it)
+}
+
 static int forward_compact(const float *bottom, int N, int H, int W, int C, const float *rois, int R, int pooled_h,
                            int pooled_w, float spatial_scale, int rounding, float *top, uint8_t *argmax8,
-                           int32_t *overflow, const unsigned *table, wssdl_stream_t stream);
+                           int32_t *overflow, const unsigned *table, wssdl_stream_t stream) {
+    if (const int rc = check_compact_args(N, 0, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_R0); rc != ARGS_PROCEED) return rc;
+    if (!bottom || !rois || !top || !argmax8 || N < 1) return WSSDL_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(bottom) & 15) || (reinterpret_cast<uintptr_t>(top) & 15) ||
+        (reinterpret_cast<uintptr_t>(argmax8) & 3))
+        return WSSDL_ERR_INVALID_ARGUMENT;
+    hipStream_t st = as_stream(stream);
+    const int lanes_per_row = C / 32;
+    const int rows_per_block = 256 / lanes_per_row;
+    const long long row_blocks = ((long long)R * pooled_h + rows_per_block - 1) / rows_per_block;
+    if (row_blocks * 8 > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
+    const FwdPlan p = plan_forward(R, H, W, C, pooled_h, pooled_w, table ? 0 : tuning().roi_fwd_variant, table != nullptr, false);
+    if (p.family != FwdPlan::SLICED)
+        return launch_fwd_rows(p, false, bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, argmax8,
+                               overflow, table, st);
+    // less than ~4 workgroups per CU: latency-bound, fetch 2 cells at a time
+    const auto sliced = row_blocks * 8 <= 4096 ? roi_pool_fwd_compact_kernel<2> : roi_pool_fwd_compact_kernel<1>;
+    hipLaunchKernelGGL(sliced, dim3((unsigned)(row_blocks * 8)), dim3(256), 0, st, bottom, N, H, W, C, rois, R, pooled_h,
+                       pooled_w, spatial_scale, rounding, top, reinterpret_cast<unsigned *>(argmax8), overflow, lanes_per_row,
+                       rows_per_block);
+    return check_launch();
+}
 
 extern "C" int wssdl_roi_pool_forward_compact(const float *bottom, int N, int H, int W, int C,
                                               const float *rois, int R, int pooled_h, int pooled_w,
@@ -818,102 +958,6 @@ extern "C" int wssdl_roi_pool_forward_compact_windows(const float *bottom, int N
                            nullptr, static_cast<const unsigned *>(table), stream);
 }
 
-static int forward_compact(const float *bottom, int N, int H, int W, int C, const float *rois, int R, int pooled_h,
-                           int pooled_w, float spatial_scale, int rounding, float *top, uint8_t *argmax8,
-                           int32_t *overflow, const unsigned *table, wssdl_stream_t stream) {
-    if (N < 0 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU)
-        return WSSDL_ERR_INVALID_ARGUMENT;
-    if (R == 0) return WSSDL_OK;
-    if (!bottom || !rois || !top || !argmax8 || N < 1) return WSSDL_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(bottom) & 15) || (reinterpret_cast<uintptr_t>(top) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax8) & 3))
-        return WSSDL_ERR_INVALID_ARGUMENT;
-    hipStream_t st = as_stream(stream);
-    const int lanes_per_row = C / 32;
-    const int rows_per_block = 256 / lanes_per_row;
-    const long long row_blocks = ((long long)R * pooled_h + rows_per_block - 1) / rows_per_block;
-    if (row_blocks * 8 > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
-    unsigned *a8 = reinterpret_cast<unsigned *>(argmax8);
-    int variant = tuning().roi_fwd_variant;
-    if (table) variant = 0;
-    // wave-uniform kernel, 256 (or 128) channels per wave.  Variants: 0 = automatic, 1 = one bin row per
-    // wave with a store per bin, 2 = 128-channel waves, 3 = 7 one-row waves per workgroup, 4 = one bin
-    // row per wave, 5 = a whole RoI per wave, 9 = the sliced round-1 form
-    // a test-sized RoI list (R = 300: 8400 one-row waves) is latency-bound: 0.087 ms on one-row waves, 0.067 on the sliced
-    // kernel (which spreads a bin row over more lanes), 0.056-0.062 on one wave per bin (below) at 63 x 100 x 1024
-    const bool small_launch = variant == 0 && !table && (long long)R * pooled_h * cdiv(C, 256) < 32768;
-    // Small launches (round 6): one wave per BIN.  A launch of R * PH * C / 256 < 32768 one-row waves leaves SIMDs idle and each
-    // wave walks a chain of 7 bins; split seven ways the waves are 7 x as many and a seventh as long.  Same scan per bin, same
-    // bits.  R x C sweep against the sliced kernel (profiles/r06_small_forward_one_bin_sweep.log): 0.45-0.86 x the time
-    // everywhere below the bound, 0.96-1.02 x at it, 1.3 x beyond (where the rows kernel takes over).  "roi_fwd_one_bin":
-    // 7 (default) / 4 = waves per bin row, 0 = the sliced kernel, + 100 = also beyond the bound (experiments).
-    const int split = tuning().roi_fwd_one_bin;
-    if ((small_launch || (split >= 100 && variant == 0 && !table)) && split > 0 && C % 256 == 0 && (long long)H * W * C * 4 < 0x7fffffffLL) {
-        // SPLIT waves per bin row: R * PH * SPLIT * C / 256 waves with ceil(PW / SPLIT) bins each
-        const int slices = C / 256;
-        if ((slices >= 8 && slices % 8 == 0) || (slices < 8 && 8 % slices == 0)) {
-            const int sp = split % 100 >= 7 ? 7 : 4;
-            const long long items = (long long)R * pooled_h * sp;
-            const long long groups = (items + 3) / 4;
-            const long long blocks = slices >= 8 ? groups * slices : 8 * ((groups + 8 / slices - 1) / (8 / slices));
-            if (blocks <= 0x7fffffffLL) {
-#define WSSDL_FWD_SPLIT(SP) \
-    hipLaunchKernelGGL((roi_pool_fwd_rows_kernel<4, 4, 0, false, false, false, SP>), dim3((unsigned)blocks), dim3(256), 0, st, bottom, N, H, \
-                       W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, argmax8, overflow, slices, nullptr)
-                if (sp == 7) WSSDL_FWD_SPLIT(7); else WSSDL_FWD_SPLIT(4);
-#undef WSSDL_FWD_SPLIT
-                return check_launch();
-            }
-        }
-    }
-    if (variant != 9 && !small_launch) {
-        const int cpl = (variant == 2 || C % 256 != 0) ? 2 : 4;
-        const int slices = cdiv(C, 64 * cpl);
-        const int rpw = (variant == 3 && cpl == 4) ? 7 : 4;
-        if (((slices >= 8 && slices % 8 == 0) || (slices < 8 && 8 % slices == 0)) &&
-            (long long)H * W * C * 4 < 0x7fffffffLL) {
-            // a wave walks a whole RoI when that still gives every SIMD its 8 waves (R * slices >= 8192),
-            // else one (roi, ph) bin row; pooled_w == 7 is known at compile time: the stores of a row are
-            // issued together
-            const bool many = (long long)R * slices >= 8192;
-            const bool whole = pooled_w == 7 && variant == 5 && many;      // (measured slower: 0.80 against 0.57 ms)
-            const long long items = whole ? (long long)R : (long long)R * pooled_h;
-            const long long groups = (items + rpw - 1) / rpw;
-            long long blocks = slices >= 8 ? groups * slices : 8 * ((groups + 8 / slices - 1) / (8 / slices));
-            if (blocks <= 0x7fffffffLL) {
-#define WSSDL_FWD_ROWS(CPL, RPW, PWS, WHOLE) \
-    hipLaunchKernelGGL((roi_pool_fwd_rows_kernel<CPL, RPW, PWS, WHOLE, false>), dim3((unsigned)blocks), dim3(64 * RPW), 0, st, \
-                       bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, argmax8, overflow, \
-                       slices, nullptr)
-#define WSSDL_FWD_TAB(CPL) \
-    hipLaunchKernelGGL((roi_pool_fwd_rows_kernel<CPL, 4, 7, false, true>), dim3((unsigned)blocks), dim3(64 * 4), 0, st, \
-                       bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, argmax8, overflow, \
-                       slices, table)
-                if (table && cpl == 4 && rpw == 4 && !whole) WSSDL_FWD_TAB(4);
-                else if (table) return WSSDL_ERR_INVALID_ARGUMENT;
-                else if (variant == 3 && cpl == 4) WSSDL_FWD_ROWS(4, 7, 0, false);
-                else if (cpl == 2) { if (whole) WSSDL_FWD_ROWS(2, 4, 7, true); else WSSDL_FWD_ROWS(2, 4, 0, false); }
-                else if (whole) WSSDL_FWD_ROWS(4, 4, 7, true);
-                else if ((variant == 0 || variant == 4) && pooled_w == 7) WSSDL_FWD_ROWS(4, 4, 7, false);
-                else WSSDL_FWD_ROWS(4, 4, 0, false);
-#undef WSSDL_FWD_ROWS
-#undef WSSDL_FWD_TAB
-                return check_launch();
-            }
-        }
-    }
-    if (row_blocks * 8 <= 4096)      // less than ~4 workgroups per CU: latency-bound, fetch 2 cells at a time
-        hipLaunchKernelGGL(roi_pool_fwd_compact_kernel<2>, dim3((unsigned)(row_blocks * 8)), dim3(256), 0, st,
-                           bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, a8,
-                           overflow, lanes_per_row, rows_per_block);
-    else
-        hipLaunchKernelGGL(roi_pool_fwd_compact_kernel<1>, dim3((unsigned)(row_blocks * 8)), dim3(256), 0, st,
-                           bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, a8,
-                           overflow, lanes_per_row, rows_per_block);
-    return check_launch();
-}
-
 // The wave-uniform forward with the reference op's i32 arg-max (wssdl_roi_pool_forward).  Returns
 // WSSDL_ROWS_I32_UNSUPPORTED when the shape is not one the kernel takes (the caller then runs the sliced kernel).
 int wssdl::launch_fwd_rows_i32(const float *bottom, int N, int H, int W, int C, const float *rois, int R, int pooled_h,
@@ -924,35 +968,10 @@ int wssdl::launch_fwd_rows_i32(const float *bottom, int N, int H, int W, int C, 
         (reinterpret_cast<uintptr_t>(argmax) & 15))
         return WSSDL_ROWS_I32_UNSUPPORTED;
     // (a test-sized RoI list: one wave per bin, as on the 1-byte path; the sliced kernel where that form does not apply)
-    if ((long long)R * pooled_h * cdiv(C, 256) < 32768) {
-        const int sl = C / 256;
-        if (tuning().roi_fwd_one_bin <= 0 || C % 256 != 0 || !((sl >= 8 && sl % 8 == 0) || (sl < 8 && 8 % sl == 0)))
-            return WSSDL_ROWS_I32_UNSUPPORTED;
-        const long long groups7 = ((long long)R * pooled_h * 7 + 3) / 4;
-        const long long blocks7 = sl >= 8 ? groups7 * sl : 8 * ((groups7 + 8 / sl - 1) / (8 / sl));
-        if (blocks7 > 0x7fffffffLL) return WSSDL_ROWS_I32_UNSUPPORTED;
-        hipLaunchKernelGGL((roi_pool_fwd_rows_kernel<4, 4, 0, false, false, true, 7>), dim3((unsigned)blocks7), dim3(256), 0, st, bottom, N,
-                           H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, reinterpret_cast<unsigned char *>(argmax),
-                           nullptr, sl, nullptr);
-        return check_launch();
-    }
-    const int cpl = (C % 256 != 0) ? 2 : 4;
-    const int slices = cdiv(C, 64 * cpl);
-    if (!((slices >= 8 && slices % 8 == 0) || (slices < 8 && 8 % slices == 0))) return WSSDL_ROWS_I32_UNSUPPORTED;
-    const int rpw = 4;
-    const long long items = (long long)R * pooled_h;
-    const long long groups = (items + rpw - 1) / rpw;
-    const long long blocks = slices >= 8 ? groups * slices : 8 * ((groups + 8 / slices - 1) / (8 / slices));
-    if (blocks > 0x7fffffffLL) return WSSDL_ROWS_I32_UNSUPPORTED;
-    unsigned char *a = reinterpret_cast<unsigned char *>(argmax);
-#define WSSDL_FWD_I32(CPL, PWS) \
-    hipLaunchKernelGGL((roi_pool_fwd_rows_kernel<CPL, 4, PWS, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                       bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top, a, nullptr, slices, \
-                       nullptr)
-    if (cpl == 4) { if (pooled_w == 7) WSSDL_FWD_I32(4, 7); else WSSDL_FWD_I32(4, 0); }
-    else { if (pooled_w == 7) WSSDL_FWD_I32(2, 7); else WSSDL_FWD_I32(2, 0); }
-#undef WSSDL_FWD_I32
-    return check_launch();
+    const FwdPlan p = plan_forward(R, H, W, C, pooled_h, pooled_w, 0, false, true);
+    if (p.family == FwdPlan::SLICED) return WSSDL_ROWS_I32_UNSUPPORTED;
+    return launch_fwd_rows(p, true, bottom, N, H, W, C, rois, R, pooled_h, pooled_w, spatial_scale, rounding, top,
+                           reinterpret_cast<unsigned char *>(argmax), nullptr, nullptr, st);
 }
 
 extern "C" int wssdl_roi_argmax_expand(const uint8_t *argmax8, const float *rois, int R, int H, int W,
@@ -991,9 +1010,7 @@ extern "C" int wssdl_roi_pool_backward_prepare(const float *rois, int R, int N, 
                                                int32_t *plan_host, wssdl_stream_t stream) {
     if (!plan_host) return WSSDL_ERR_INVALID_ARGUMENT;
     *plan_host = -1;
-    if (N < 1 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU)
-        return WSSDL_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_compact_args(N, 1, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_NEVER); rc != ARGS_PROCEED) return rc;
     if (!workspace || !walk_supported(R, N, H, W, C, pooled_h, pooled_w)) return WSSDL_OK;   // plan -1: fallback kernel
     if (R > 0 && !rois) return WSSDL_ERR_INVALID_ARGUMENT;
     int plan = -1;
@@ -1019,10 +1036,8 @@ extern "C" int wssdl_roi_pool_backward_compact_split(const float *top_diff, cons
                                                      float spatial_scale, int rounding, float *bottom_diff,
                                                      void *workspace, size_t workspace_bytes, int plan, int segments,
                                                      void *scratch, size_t scratch_bytes, wssdl_stream_t stream) {
-    if (N < 0 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (N == 0) return WSSDL_OK;
-    if (!bottom_diff || (R > 0 && (!top_diff || !argmax8 || !rois))) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_compact_args(N, 0, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_N0); rc != ARGS_PROCEED) return rc;
+    if (!backward_pointers_ok(top_diff, argmax8, rois, R, bottom_diff)) return WSSDL_ERR_INVALID_ARGUMENT;
     if (plan < 0 || !workspace || !walk_supported(R, N, H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
     if (segments < 1) return WSSDL_ERR_INVALID_ARGUMENT;
     if (segments > 1 && (!scratch || scratch_bytes < wssdl_roi_pool_backward_split_scratch_bytes(N, H, W, C, segments)))
@@ -1051,31 +1066,22 @@ extern "C" int wssdl_roi_pool_backward_owner_prepare(const float *rois, int R, i
                                                      int pooled_h, int pooled_w, float spatial_scale, int rounding,
                                                      void *workspace, size_t workspace_bytes, int owner_plan,
                                                      wssdl_stream_t stream) {
-    if (N < 1 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_compact_args(N, 1, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_NEVER); rc != ARGS_PROCEED) return rc;
     if (!workspace || !owner_supported(R, N, H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
     if (R > 0 && !rois) return WSSDL_ERR_INVALID_ARGUMENT;
     return owner_prepare(rois, R, N, H, W, C, pooled_h, pooled_w, spatial_scale, rounding, workspace, workspace_bytes,
                          owner_plan, as_stream(stream));
 }
 
+// the plain owner form is the owner-split form with one wave per tile stream
 extern "C" int wssdl_roi_pool_backward_compact_owner(const float *top_diff, const uint8_t *argmax8, const float *rois,
                                                      int R, int N, int H, int W, int C, int pooled_h, int pooled_w,
                                                      float spatial_scale, int rounding, float *bottom_diff,
                                                      void *workspace, size_t workspace_bytes, int owner_plan,
                                                      void *scratch, size_t scratch_bytes, wssdl_stream_t stream) {
-    if (N < 0 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (N == 0) return WSSDL_OK;
-    if (!bottom_diff || (R > 0 && (!top_diff || !argmax8 || !rois))) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (!workspace || !owner_supported(R, N, H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    const size_t need = owner_scratch_bytes(N, H, W, C, owner_plan);
-    if (need == 0) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (!scratch || scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
-        (reinterpret_cast<uintptr_t>(bottom_diff) & 15))
-        return WSSDL_ERR_WORKSPACE;
-    return launch_owner(top_diff, argmax8, R, N, H, W, C, pooled_h, pooled_w, bottom_diff, workspace, workspace_bytes,
-                        owner_plan, static_cast<float *>(scratch), as_stream(stream));
+    return wssdl_roi_pool_backward_compact_owner_split(top_diff, argmax8, rois, R, N, H, W, C, pooled_h, pooled_w, spatial_scale,
+                                                       rounding, bottom_diff, workspace, workspace_bytes, owner_plan, 1, scratch,
+                                                       scratch_bytes, stream);
 }
 
 extern "C" int wssdl_roi_pool_backward_owner_segments(int R, int N, int H, int W, int C) {
@@ -1092,16 +1098,12 @@ extern "C" int wssdl_roi_pool_backward_compact_owner_split(const float *top_diff
                                                            void *workspace, size_t workspace_bytes, int owner_plan,
                                                            int segments, void *scratch, size_t scratch_bytes,
                                                            wssdl_stream_t stream) {
-    if (N < 0 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (N == 0) return WSSDL_OK;
-    if (!bottom_diff || (R > 0 && (!top_diff || !argmax8 || !rois))) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_compact_args(N, 0, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_N0); rc != ARGS_PROCEED) return rc;
+    if (!backward_pointers_ok(top_diff, argmax8, rois, R, bottom_diff)) return WSSDL_ERR_INVALID_ARGUMENT;
     if (!workspace || !owner_supported(R, N, H, W, C, pooled_h, pooled_w) || segments < 1) return WSSDL_ERR_INVALID_ARGUMENT;
     const size_t need = owner_scratch_bytes(N, H, W, C, owner_plan, segments);
     if (need == 0) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (!scratch || scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
-        (reinterpret_cast<uintptr_t>(bottom_diff) & 15))
-        return WSSDL_ERR_WORKSPACE;
+    if (!owner_scratch_ok(scratch, scratch_bytes, need, bottom_diff)) return WSSDL_ERR_WORKSPACE;
     return launch_owner(top_diff, argmax8, R, N, H, W, C, pooled_h, pooled_w, bottom_diff, workspace, workspace_bytes,
                         owner_plan, static_cast<float *>(scratch), as_stream(stream), false, segments);
 }
@@ -1110,15 +1112,15 @@ extern "C" int wssdl_roi_pool_backward_owner_i32(const float *top_diff, const in
                                                  int H, int W, int C, int pooled_h, int pooled_w, float spatial_scale,
                                                  float *bottom_diff, void *workspace, size_t workspace_bytes, int owner_plan,
                                                  void *scratch, size_t scratch_bytes, wssdl_stream_t stream) {
+    // (the reference op's own arg-max: no rounding mode, and any shape the i32 walk takes -- not only compact_supported ones)
     if (N < 0 || R < 0 || H < 1 || W < 1 || C < 1 || pooled_h < 1 || pooled_w < 1) return WSSDL_ERR_INVALID_ARGUMENT;
     if (N == 0) return WSSDL_OK;
-    if (!bottom_diff || (R > 0 && (!top_diff || !argmax || !rois))) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (!backward_pointers_ok(top_diff, argmax, rois, R, bottom_diff)) return WSSDL_ERR_INVALID_ARGUMENT;
     if (!workspace || !owner_supported(R, N, H, W, C, pooled_h, pooled_w) || !walk_i32_supported(R, N, H, W, C, pooled_h, pooled_w))
         return WSSDL_ERR_INVALID_ARGUMENT;
     const size_t need = owner_scratch_bytes(N, H, W, C, owner_plan);
     if (need == 0) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (!scratch || scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
-        (reinterpret_cast<uintptr_t>(bottom_diff) & 15) || (reinterpret_cast<uintptr_t>(argmax) & 7) ||
+    if (!owner_scratch_ok(scratch, scratch_bytes, need, bottom_diff) || (reinterpret_cast<uintptr_t>(argmax) & 7) ||
         (reinterpret_cast<uintptr_t>(top_diff) & 7))
         return WSSDL_ERR_WORKSPACE;
     // (the lists carry window starts this path does not read: the rounding mode does not matter)
@@ -1135,11 +1137,8 @@ extern "C" int wssdl_roi_pool_backward_compact(const float *top_diff, const uint
                                                int pooled_h, int pooled_w, float spatial_scale,
                                                int rounding, float *bottom_diff, void *workspace,
                                                size_t workspace_bytes, int plan, wssdl_stream_t stream) {
-    if (N < 0 || R < 0 || !compact_supported(H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (rounding != WSSDL_ROI_ROUND_CUDA && rounding != WSSDL_ROI_ROUND_CPU)
-        return WSSDL_ERR_INVALID_ARGUMENT;
-    if (N == 0) return WSSDL_OK;
-    if (!bottom_diff || (R > 0 && (!top_diff || !argmax8 || !rois))) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_compact_args(N, 0, R, H, W, C, pooled_h, pooled_w, rounding, NOOP_N0); rc != ARGS_PROCEED) return rc;
+    if (!backward_pointers_ok(top_diff, argmax8, rois, R, bottom_diff)) return WSSDL_ERR_INVALID_ARGUMENT;
     hipStream_t st = as_stream(stream);
     if (plan >= 0) {          // lists prepared by wssdl_roi_pool_backward_prepare: the walk kernel alone
         if (!workspace || !walk_supported(R, N, H, W, C, pooled_h, pooled_w)) return WSSDL_ERR_INVALID_ARGUMENT;
@@ -1148,14 +1147,7 @@ extern "C" int wssdl_roi_pool_backward_compact(const float *top_diff, const uint
     }
     const int variant = tuning().roi_bwdc_variant;      // tuning: fallback kernel shapes
     // fallback: tile-owner kernel with the RoI filter inside (no workspace; any pooled size)
-    // channels per workgroup: 256 when that still yields enough workgroups to fill the chip
-    int cg = C > 128 ? 256 : (C > 64 ? 128 : 64);
-    const long long tiles = (long long)cdiv(H, 4) * cdiv(W, 8);       // counted in 4x8 tiles
-    while (cg > 64 && (long long)N * cdiv(C, cg) * tiles < BWD_MIN_WORKGROUPS) cg >>= 1;
-    {       // tuning override
-        const int v = tuning().roi_bwd_cg;
-        if (v == 64 || v == 128 || v == 256) cg = v;
-    }
+    const int cg = fallback_channel_group(N, H, W, C);
 #define WSSDL_BWDC(TH, TW, CGV, CHUNK, MAXB, MINB) \
     launch_bwd_c<TH, TW, CGV, CHUNK, MAXB, MINB>(top_diff, argmax8, rois, R, N, H, W, C, pooled_h, pooled_w, \
                                                  spatial_scale, rounding, bottom_diff, st)

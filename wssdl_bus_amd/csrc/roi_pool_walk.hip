@@ -40,6 +40,8 @@
 // the launch.  The free-running walk below stays.
 #include "roi_pool.hip.h"
 
+#include <type_traits>
+
 namespace wssdl {
 
 constexpr unsigned ARG8_EMPTY_W = 0xffu;
@@ -799,41 +801,44 @@ __global__ __launch_bounds__(256) void walk_merge_split_kernel(float *__restrict
 }
 
 // A plan = tile shape, records in flight, the waves per SIMD the launch bounds ask for and the
-// channels per lane.  wssdl_set_tuning("roi_bwd_plan", id) overrides the choice of walk_plan_auto.
+// channels per lane.  wssdl_set_tuning("roi_bwd_plan", id) overrides the choice of walk_plan_auto.  Last column: the
+// i32 form of the walk (the reference op's own arg-max, wssdl_roi_pool_backward_ws) is instantiated for the plan --
+// the ones walk_plan_auto can pick and the larger tiles that path prefers.  This column is the only list of them.
 struct WalkPlan {
     int th, tw, depth, minw, cpl;
+    bool i32;
 };
 
 #define WSSDL_WALK_PLANS(X) \
-    X(0, 4, 4, 2, 5, 2)  \
-    X(1, 4, 8, 2, 2, 2)  \
-    X(2, 8, 8, 3, 1, 2)  \
-    X(3, 4, 8, 3, 2, 2)  \
-    X(4, 8, 8, 4, 1, 2)  \
-    X(5, 4, 4, 3, 4, 2)  \
-    X(6, 8, 8, 4, 2, 1)  /* one channel per lane: 8x8 tiles at 4x8's LDS */ \
-    X(7, 8, 8, 3, 2, 1)  \
-    X(8, 8, 8, 2, 2, 1)  \
-    X(9, 6, 8, 2, 1, 2)  /* fewer border re-reads (1.52 against 1.68), 6 waves per CU */ \
-    X(10, 5, 8, 2, 1, 2) /* 1.58, 7 waves per CU */ \
-    X(11, 6, 6, 2, 2, 2) /* 1.60, 8 waves per CU */ \
-    X(12, 6, 8, 3, 1, 2) \
-    X(13, 6, 6, 3, 2, 2) \
-    X(14, 6, 7, 2, 1, 2) \
-    X(15, 7, 6, 2, 1, 2) \
-    X(16, 5, 7, 2, 2, 2) \
-    X(17, 7, 7, 2, 1, 2) \
-    X(18, 2, 4, 3, 4, 2) /* small launches: short slot chains per wave */ \
-    X(19, 2, 2, 3, 4, 2) \
-    X(20, 3, 4, 3, 4, 2) \
-    X(21, 2, 2, 3, 4, 1) /* small launches, 64-channel waves: twice the waves */ \
-    X(22, 2, 4, 3, 4, 1) \
-    X(23, 4, 4, 3, 4, 1) \
-    X(24, 3, 4, 3, 4, 1) \
-    X(25, 6, 6, 3, 4, 1)
+    X(0, 4, 4, 2, 5, 2, false)  \
+    X(1, 4, 8, 2, 2, 2, false)  \
+    X(2, 8, 8, 3, 1, 2, false)  \
+    X(3, 4, 8, 3, 2, 2, false)  \
+    X(4, 8, 8, 4, 1, 2, true)  \
+    X(5, 4, 4, 3, 4, 2, true)  \
+    X(6, 8, 8, 4, 2, 1, false)  /* one channel per lane: 8x8 tiles at 4x8's LDS */ \
+    X(7, 8, 8, 3, 2, 1, false)  \
+    X(8, 8, 8, 2, 2, 1, false)  \
+    X(9, 6, 8, 2, 1, 2, true)  /* fewer border re-reads (1.52 against 1.68), 6 waves per CU */ \
+    X(10, 5, 8, 2, 1, 2, false) /* 1.58, 7 waves per CU */ \
+    X(11, 6, 6, 2, 2, 2, true) /* 1.60, 8 waves per CU */ \
+    X(12, 6, 8, 3, 1, 2, true) \
+    X(13, 6, 6, 3, 2, 2, true) \
+    X(14, 6, 7, 2, 1, 2, true) \
+    X(15, 7, 6, 2, 1, 2, false) \
+    X(16, 5, 7, 2, 2, 2, false) \
+    X(17, 7, 7, 2, 1, 2, true) \
+    X(18, 2, 4, 3, 4, 2, true) /* small launches: short slot chains per wave */ \
+    X(19, 2, 2, 3, 4, 2, true) \
+    X(20, 3, 4, 3, 4, 2, false) \
+    X(21, 2, 2, 3, 4, 1, true) /* small launches, 64-channel waves: twice the waves */ \
+    X(22, 2, 4, 3, 4, 1, true) \
+    X(23, 4, 4, 3, 4, 1, true) \
+    X(24, 3, 4, 3, 4, 1, false) \
+    X(25, 6, 6, 3, 4, 1, false)
 
 static const WalkPlan kWalkPlans[] = {
-#define WSSDL_X(ID, TH, TW, D, MW, CPL) {TH, TW, D, MW, CPL},
+#define WSSDL_X(ID, TH, TW, D, MW, CPL, I32) {TH, TW, D, MW, CPL, I32},
     WSSDL_WALK_PLANS(WSSDL_X)
 #undef WSSDL_X
 };
@@ -920,12 +925,15 @@ size_t walk_flags_offset(int R, int N, int H, int W, int PH, int PW) {
     return (size_t)(reinterpret_cast<char *>(ws.total) - reinterpret_cast<char *>(0x1000));
 }
 
-template <int TH, int TW>
-static int prepare_t(const float *rois, int R, int N, int H, int W, int C, int PH, int PW, float scale,
-                     int rounding, void *workspace, size_t workspace_bytes, hipStream_t st) {
-    const int tiles_h = cdiv(H, TH), tiles_w = cdiv(W, TW), tiles = tiles_h * tiles_w;
+// The per-tile lists of a list-driven backward (exact walk and bin-owner form alike): a memset and five launches on
+// tiles that repeat every th x tw cells.  The forms differ in the kernel that writes the axis tables (`launch_axes`)
+// and in the last argument of walk_fill_kernel (`lean_rw`: the region width of a lean owner plan, else 0).
+template <typename LaunchAxes>
+static int prepare_lists(const float *rois, int R, int N, int H, int W, int C, int PH, int PW, int th, int tw,
+                         void *workspace, size_t workspace_bytes, hipStream_t st, int lean_rw, LaunchAxes launch_axes) {
+    const int tiles_h = cdiv(H, th), tiles_w = cdiv(W, tw), tiles = tiles_h * tiles_w;
     const int items = N * tiles;
-    const long long cap = walk_record_bound(R, N, H, W, PH, PW, TH, TW);
+    const long long cap = walk_record_bound(R, N, H, W, PH, PW, th, tw);      // (owner form: a chain lists a bin no more often than the exact form)
     WalkWs ws;
     if (carve_walk(workspace, R, N, tiles_h, tiles_w, cap, &ws) > workspace_bytes) return WSSDL_ERR_WORKSPACE;
     const unsigned total_elems = (unsigned)((long long)R * PH * PW * C);
@@ -934,8 +942,7 @@ static int prepare_t(const float *rois, int R, int N, int H, int W, int C, int P
     if (e != hipSuccess) { set_last_error(e);  return WSSDL_ERR_LAUNCH; }
     if (R > 0) {
         hipLaunchKernelGGL(walk_span_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, rois, R, N, ws.img_span);
-        hipLaunchKernelGGL((walk_axes_kernel<TH, TW>), dim3(cdiv((long long)R * (tiles_h + tiles_w), 256)), dim3(256), 0,
-                           st, rois, R, N, H, W, PH, PW, scale, rounding, tiles_h, tiles_w, ws.rowtab, ws.coltab);
+        launch_axes(dim3(cdiv((long long)R * (tiles_h + tiles_w), 256)), tiles_h, tiles_w, ws);
     }
     hipLaunchKernelGGL(walk_count_kernel, dim3(items), dim3(FILL_BLOCK), 0, st, rois, R, tiles_h, tiles_w,
                        ws.img_span, ws.rowtab, ws.coltab, ws.tile_slots);
@@ -943,7 +950,7 @@ static int prepare_t(const float *rois, int R, int N, int H, int W, int C, int P
                        ws.total);
     hipLaunchKernelGGL(walk_fill_kernel, dim3(items), dim3(FILL_BLOCK), 0, st, rois, C, PW, PH * PW, R, tiles_h,
                        tiles_w, ws.img_span, ws.rowtab, ws.coltab, ws.tile_off, ws.tile_slots, ws.slots, cap,
-                       total_elems, ws.total, 0);
+                       total_elems, ws.total, lean_rw);
     return check_launch();
 }
 
@@ -954,7 +961,11 @@ int walk_prepare(const float *rois, int R, int N, int H, int W, int C, int PH, i
     int rc = WSSDL_ERR_INVALID_ARGUMENT;
 #define WSSDL_PREP(TH, TW) \
     if (p.th == TH && p.tw == TW) \
-        rc = prepare_t<TH, TW>(rois, R, N, H, W, C, PH, PW, scale, rounding, workspace, workspace_bytes, st);
+        rc = prepare_lists(rois, R, N, H, W, C, PH, PW, TH, TW, workspace, workspace_bytes, st, 0, \
+                           [&](dim3 grid, int tiles_h, int tiles_w, const WalkWs &ws) { \
+                               hipLaunchKernelGGL((walk_axes_kernel<TH, TW>), grid, dim3(256), 0, st, rois, R, N, H, W, PH, PW, \
+                                                  scale, rounding, tiles_h, tiles_w, ws.rowtab, ws.coltab); \
+                           });
     WSSDL_PREP(2, 2) WSSDL_PREP(2, 4) WSSDL_PREP(3, 4) WSSDL_PREP(4, 4) WSSDL_PREP(4, 8) WSSDL_PREP(5, 7)
     WSSDL_PREP(5, 8) WSSDL_PREP(6, 6) WSSDL_PREP(6, 7) WSSDL_PREP(6, 8) WSSDL_PREP(7, 6) WSSDL_PREP(7, 7)
     WSSDL_PREP(8, 8)
@@ -976,73 +987,73 @@ __global__ __launch_bounds__(256) void walk_combine_kernel(float *__restrict__ b
     reinterpret_cast<float4v *>(bottom_diff)[i] = o;
 }
 
-// cell / W by one 24-bit multiply for every cell of the map (as in roi_pool.hip: launch_bwd), C = 2^cshift
+// i32 arg-max: index -> cell by a shift (C = 2^cshift), cell -> (h, w) by the 24-bit multiply of fast_div_by_width
 static bool walk_i32_params(int H, int W, int C, WalkI32 *q) {
     int cshift = 0;
     while ((1 << cshift) < C) ++cshift;
-    if ((1 << cshift) != C || (long long)H * W >= (1 << 16)) return false;
-    const unsigned cells = (unsigned)H * (unsigned)W;
-    for (unsigned sft = 8; sft <= 24; ++sft) {
-        const unsigned long long mg = ((1ULL << sft) + (unsigned)W - 1) / (unsigned)W;
-        if (mg >= (1ULL << 24) || mg * (cells ? cells - 1 : 0) >= (1ULL << 32)) continue;
-        bool exact = true;
-        for (unsigned n = 0; n < cells && exact; ++n) exact = (unsigned)((n * mg) >> sft) == n / (unsigned)W;
-        if (exact) {
-            q->cshift = cshift;  q->magic = (unsigned)mg;  q->shift = sft;
-            return true;
-        }
-    }
-    return false;
+    if ((1 << cshift) != C) return false;
+    q->cshift = cshift;
+    return fast_div_by_width(H, W, &q->magic, &q->shift);
 }
 
-// the plans the i32 form of the walk is instantiated for (launch_walk_t: I32_BUILT)
-bool walk_i32_plan_built(int id) {
-    return id == 11 || id == 5 || id == 23 || id == 18 || id == 22 || id == 19 || id == 21 || id == 9 || id == 12 ||
-           id == 17 || id == 4 || id == 13 || id == 14;
-}
+bool walk_i32_plan_built(int id) { return id >= 0 && id < WALK_PLANS && kWalkPlans[id].i32; }
 
 bool walk_i32_supported(int R, int N, int H, int W, int C, int PH, int PW) {
     WalkI32 q;
     return walk_supported(R, N, H, W, C, PH, PW) && walk_i32_params(H, W, C, &q);
 }
 
-template <int ID, int TH, int TW, int DEPTH, int MINW, int CPL>
-static int launch_walk_t(const float *top_diff, const unsigned char *arg8, int R, int N, int H, int W, int C,
-                         int PH, int PW, float *bottom_diff, void *workspace, size_t workspace_bytes,
-                         hipStream_t st, int nseg, float *partial, bool i32) {
-    const int tiles_h = cdiv(H, TH), tiles_w = cdiv(W, TW), tiles = tiles_h * tiles_w;
+// The one launcher of the list-driven backward: exact walk, split walk (nseg > 1), bin-owner form (OWN) and its
+// split.  KH x KW is the kernel's tile (exact / split) or region (owner forms); the tiles repeat every SH x SW cells
+// (= KH x KW unless OWN).  Shared: the carving of the workspace, the grid (xcd_grid <-> the decode at the top of
+// roi_pool_bwd_walk_kernel), the i32 gate and the kernel's argument list.  Per form: the template arguments, what
+// `extra` is (the split walk's partial sums [nseg - 1][N*H*W*C]; the owner forms' halo / region buffers) and the
+// launch that folds it into bottom_diff afterwards.  I32_BUILT: the plan table's last column.
+template <int KH, int KW, int SH, int SW, int DEPTH, int MINW, int CPL, bool OWN, int AUX, bool I32_BUILT>
+static int launch_lists(const float *top_diff, const unsigned char *arg8, int R, int N, int H, int W, int C, int PH,
+                        int PW, float *bottom_diff, void *workspace, size_t workspace_bytes, hipStream_t st, int nseg,
+                        float *extra, bool i32) {
+    const int tiles_h = cdiv(H, SH), tiles_w = cdiv(W, SW), tiles = tiles_h * tiles_w;
     const int items = N * tiles;
+    if (nseg < 1 || nseg > WALK_MAX_SEGMENTS || (OWN && i32 && nseg != 1)) return WSSDL_ERR_INVALID_ARGUMENT;
     WalkWs ws;
-    if (carve_walk(workspace, R, N, tiles_h, tiles_w, walk_record_bound(R, N, H, W, PH, PW, TH, TW), &ws) > workspace_bytes)
+    if (carve_walk(workspace, R, N, tiles_h, tiles_w, walk_record_bound(R, N, H, W, PH, PW, SH, SW), &ws) > workspace_bytes)
         return WSSDL_ERR_WORKSPACE;
     const unsigned total_elems = (unsigned)((long long)R * PH * PW * C);
     const int G = cdiv(C, 64 * CPL);
-    long long blocks;
-    if ((G & 7) == 0) blocks = (long long)items * G;
-    else if (G < 8 && (8 % G) == 0) blocks = 8LL * cdiv(items, 8 / G);
-    else blocks = (long long)items * G;
+    const long long blocks = xcd_grid(items, G);
     if (blocks > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
-    const unsigned long long seg_stride = (unsigned long long)N * H * W * C;
+    const unsigned long long seg_stride = OWN ? 0ull : (unsigned long long)N * H * W * C;
     WalkI32 q = {0, 0u, 0u};
-    // (the i32 form is only built for the plans walk_plan_auto can pick)
-    constexpr bool I32_BUILT = ID == 11 || ID == 5 || ID == 23 || ID == 18 || ID == 22 || ID == 19 || ID == 21 ||
-                               ID == 9 || ID == 12 || ID == 17 || ID == 4 || ID == 13 || ID == 14;      // == walk_i32_plan_built(ID)
     if (i32 && !I32_BUILT) return WSSDL_ERR_INVALID_ARGUMENT;
+    auto launch = [&](auto i32_form) {
+        hipLaunchKernelGGL((roi_pool_bwd_walk_kernel<KH, KW, DEPTH, MINW, CPL, decltype(i32_form)::value, OWN, AUX>),
+                           dim3((unsigned)blocks, (unsigned)nseg), dim3(64), 0, st, top_diff, arg8,
+                           reinterpret_cast<const unsigned *>(ws.slots), ws.tile_off, ws.tile_slots, ws.order, items, tiles_w,
+                           tiles, G, H, W, C, total_elems, bottom_diff, nseg, extra, seg_stride, q, SH, SW);
+    };
     if constexpr (I32_BUILT) if (i32) {
         if (!walk_i32_params(H, W, C, &q)) return WSSDL_ERR_INVALID_ARGUMENT;
-        hipLaunchKernelGGL((roi_pool_bwd_walk_kernel<TH, TW, DEPTH, MINW, CPL, true>), dim3((unsigned)blocks, (unsigned)nseg),
-                           dim3(64), 0, st, top_diff, arg8, reinterpret_cast<const unsigned *>(ws.slots), ws.tile_off,
-                           ws.tile_slots, ws.order, items, tiles_w, tiles, G, H, W, C, total_elems, bottom_diff, nseg, partial,
-                           seg_stride, q, TH, TW);
+        launch(std::true_type());
     }
-    if (!i32)
-    hipLaunchKernelGGL((roi_pool_bwd_walk_kernel<TH, TW, DEPTH, MINW, CPL, false>), dim3((unsigned)blocks, (unsigned)nseg), dim3(64),
-                       0, st, top_diff, arg8, reinterpret_cast<const unsigned *>(ws.slots), ws.tile_off, ws.tile_slots,
-                       ws.order, items, tiles_w, tiles, G, H, W, C, total_elems, bottom_diff, nseg, partial, seg_stride, q, TH, TW);
-    if (nseg > 1) {
-        const long long n4 = (long long)(seg_stride / 4);          // C is even and walk_split_supported asks C % 4 == 0
-        hipLaunchKernelGGL(walk_combine_kernel, dim3((unsigned)cdiv(n4, 256)), dim3(256), 0, st, bottom_diff, partial, n4,
-                           nseg - 1, seg_stride);
+    if (!i32) launch(std::false_type());
+    if constexpr (!OWN) {
+        if (nseg > 1) {
+            const long long n4 = (long long)(seg_stride / 4);          // C is even and launch_walk asks C % 4 == 0
+            hipLaunchKernelGGL(walk_combine_kernel, dim3((unsigned)cdiv(n4, 256)), dim3(256), 0, st, bottom_diff, extra, n4,
+                               nseg - 1, seg_stride);
+        }
+    } else if (nseg > 1) {
+        const long long cells = (long long)N * H * W;
+        if (cells > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
+        hipLaunchKernelGGL(walk_merge_split_kernel, dim3((unsigned)cells), dim3(256), 0, st, bottom_diff, extra, N, H, W, C / 4,
+                           tiles_h, tiles_w, KH, KW, SH, SW, nseg);
+    } else {
+        constexpr int HH = KH - SH, HW = KW - SW;
+        constexpr int ncell = SH * SW - (SH - HH) * (SW - HW);
+        if (ncell > 0)
+            hipLaunchKernelGGL(walk_merge_kernel, dim3((unsigned)items, (unsigned)ncell), dim3(256), 0, st, bottom_diff, extra, H, W,
+                               C / 4, tiles_h, tiles_w, KH, KW, SH, SW);
     }
     return check_launch();
 }
@@ -1052,9 +1063,9 @@ int launch_walk(const float *top_diff, const unsigned char *arg8, int R, int N, 
                 int nseg, float *partial, bool i32) {
     if (nseg < 1 || nseg > WALK_MAX_SEGMENTS || (nseg > 1 && (!partial || (C & 3)))) return WSSDL_ERR_INVALID_ARGUMENT;
     switch (plan) {
-#define WSSDL_X(ID, TH, TW, D, MW, CPL) \
-        case ID: return launch_walk_t<ID, TH, TW, D, MW, CPL>(top_diff, arg8, R, N, H, W, C, PH, PW, bottom_diff, workspace, \
-                                                         workspace_bytes, st, nseg, partial, i32);
+#define WSSDL_X(ID, TH, TW, D, MW, CPL, I32) \
+        case ID: return launch_lists<TH, TW, TH, TW, D, MW, CPL, false, 0, I32>(top_diff, arg8, R, N, H, W, C, PH, PW, bottom_diff, \
+                                                                           workspace, workspace_bytes, st, nseg, partial, i32);
         WSSDL_WALK_PLANS(WSSDL_X)
 #undef WSSDL_X
         default: return WSSDL_ERR_INVALID_ARGUMENT;
@@ -1063,26 +1074,26 @@ int launch_walk(const float *top_diff, const unsigned char *arg8, int R, int N, 
 
 
 // ---- bin-owner form: plans, prepare, launch ----------------------------------------------------
-//   X(id, region h, region w, tile h, tile w, records in flight, waves per SIMD asked for, channels per lane, cache policy: bits 0-4 of the data loads (gfx950: 1 = sc0, 2 = nt, 16 = sc1), 64 = non-temporal stores, 128 = lean decode)
+//   X(id, region h, region w, tile h, tile w, records in flight, waves per SIMD asked for, channels per lane, cache policy: bits 0-4 of the data loads (gfx950: 1 = sc0, 2 = nt, 16 = sc1), 64 = non-temporal stores, 128 = lean decode; the i32 form is built -- tools/bwd_fixed_sweep.py --i32-owner)
 #define WSSDL_OWNER_PLANS(X) \
-    X(0, 6, 7, 4, 5, 2, 1, 2, 66)  /* the default: 128-channel waves, 21.5 KiB of LDS (7 waves per CU), halo 2 x 2 */ \
-    X(1, 6, 6, 4, 4, 2, 2, 2, 66)  /* at the exact walk's LDS (18.5 KiB) */ \
-    X(2, 8, 8, 6, 6, 3, 2, 1, 66)  /* 64-channel waves, 16.25 KiB: the fewest bytes (1.20 x moved) */ \
-    X(3, 7, 8, 5, 6, 2, 2, 1, 66)  \
-    X(4, 6, 6, 4, 4, 2, 2, 2, 0)   /* plan 1 with plain loads and stores (the A/B of the cache policy) */ \
-    X(5, 7, 7, 5, 5, 2, 1, 2, 66)  /* 25 KiB: 6 waves per CU */ \
-    X(6, 5, 5, 4, 4, 2, 2, 2, 66)  /* halo 1: 13.3 KiB, 12 waves per CU */ \
-    X(7, 6, 7, 5, 5, 2, 1, 2, 66)  /* halo 1 x 2 */ \
-    X(8, 6, 7, 4, 5, 2, 1, 2, 66 + 128)  /* plan 0 with the lean decode (intervals in code space) */ \
-    X(9, 6, 6, 4, 4, 2, 2, 2, 66 + 128)  /* plan 1 ... */ \
-    X(10, 6, 7, 4, 5, 3, 1, 2, 66 + 128) \
-    X(11, 7, 7, 5, 5, 2, 1, 2, 66 + 128)
+    X(0, 6, 7, 4, 5, 2, 1, 2, 66, true)  /* the default: 128-channel waves, 21.5 KiB of LDS (7 waves per CU), halo 2 x 2 */ \
+    X(1, 6, 6, 4, 4, 2, 2, 2, 66, true)  /* at the exact walk's LDS (18.5 KiB) */ \
+    X(2, 8, 8, 6, 6, 3, 2, 1, 66, false)  /* 64-channel waves, 16.25 KiB: the fewest bytes (1.20 x moved) */ \
+    X(3, 7, 8, 5, 6, 2, 2, 1, 66, false)  \
+    X(4, 6, 6, 4, 4, 2, 2, 2, 0, false)   /* plan 1 with plain loads and stores (the A/B of the cache policy) */ \
+    X(5, 7, 7, 5, 5, 2, 1, 2, 66, false)  /* 25 KiB: 6 waves per CU */ \
+    X(6, 5, 5, 4, 4, 2, 2, 2, 66, false)  /* halo 1: 13.3 KiB, 12 waves per CU */ \
+    X(7, 6, 7, 5, 5, 2, 1, 2, 66, false)  /* halo 1 x 2 */ \
+    X(8, 6, 7, 4, 5, 2, 1, 2, 66 + 128, false)  /* plan 0 with the lean decode (intervals in code space) */ \
+    X(9, 6, 6, 4, 4, 2, 2, 2, 66 + 128, false)  /* plan 1 ... */ \
+    X(10, 6, 7, 4, 5, 3, 1, 2, 66 + 128, false) \
+    X(11, 7, 7, 5, 5, 2, 1, 2, 66 + 128, false)
 
 struct OwnerPlan {
     int rh, rw, sh, sw, depth, minw, cpl;
 };
 static const OwnerPlan kOwnerPlans[] = {
-#define WSSDL_X(ID, RH, RW, SH, SW, D, MW, CPL, AUX) {RH, RW, SH, SW, D, MW, CPL},
+#define WSSDL_X(ID, RH, RW, SH, SW, D, MW, CPL, AUX, I32) {RH, RW, SH, SW, D, MW, CPL},
     WSSDL_OWNER_PLANS(WSSDL_X)
 #undef WSSDL_X
 };
@@ -1143,97 +1154,30 @@ int owner_split_segments(int R, int N, int H, int W, int C) {
     return (long long)N * C < 2048 ? 2 : 1;
 }
 
-template <int RH, int RW, int SH, int SW>
-static int prepare_own_t(const float *rois, int R, int N, int H, int W, int C, int PH, int PW, float scale,
-                         int rounding, void *workspace, size_t workspace_bytes, hipStream_t st, bool lean) {
-    const int tiles_h = cdiv(H, SH), tiles_w = cdiv(W, SW), tiles = tiles_h * tiles_w;
-    const int items = N * tiles;
-    const long long cap = walk_record_bound(R, N, H, W, PH, PW, SH, SW);      // a chain lists a bin no more often than the exact form
-    WalkWs ws;
-    if (carve_walk(workspace, R, N, tiles_h, tiles_w, cap, &ws) > workspace_bytes) return WSSDL_ERR_WORKSPACE;
-    const unsigned total_elems = (unsigned)((long long)R * PH * PW * C);
-    hipError_t e = hipMemsetAsync(ws.img_span, 0, (char *)ws.tile_slots - (char *)ws.img_span, st);
-    if (e != hipSuccess) { set_last_error(e);  return WSSDL_ERR_LAUNCH; }
-    if (R > 0) {
-        hipLaunchKernelGGL(walk_span_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, rois, R, N, ws.img_span);
-        hipLaunchKernelGGL((walk_axes_own_kernel<RH, RW, SH, SW>), dim3(cdiv((long long)R * (tiles_h + tiles_w), 256)),
-                           dim3(256), 0, st, rois, R, N, H, W, PH, PW, scale, rounding, tiles_h, tiles_w, ws.rowtab, ws.coltab);
-    }
-    hipLaunchKernelGGL(walk_count_kernel, dim3(items), dim3(FILL_BLOCK), 0, st, rois, R, tiles_h, tiles_w,
-                       ws.img_span, ws.rowtab, ws.coltab, ws.tile_slots);
-    hipLaunchKernelGGL(walk_order_kernel, dim3(1), dim3(1024), 0, st, ws.tile_slots, items, ws.tile_off, ws.order,
-                       ws.total);
-    hipLaunchKernelGGL(walk_fill_kernel, dim3(items), dim3(FILL_BLOCK), 0, st, rois, C, PW, PH * PW, R, tiles_h,
-                       tiles_w, ws.img_span, ws.rowtab, ws.coltab, ws.tile_off, ws.tile_slots, ws.slots, cap,
-                       total_elems, ws.total, lean ? RW : 0);
-    return check_launch();
-}
-
 int owner_prepare(const float *rois, int R, int N, int H, int W, int C, int PH, int PW, float scale, int rounding,
                   void *workspace, size_t workspace_bytes, int plan, hipStream_t st) {
     switch (plan) {
-#define WSSDL_X(ID, RH, RW, SH, SW, D, MW, CPL, AUX) \
-        case ID: return prepare_own_t<RH, RW, SH, SW>(rois, R, N, H, W, C, PH, PW, scale, rounding, workspace, workspace_bytes, st, \
-                                                      ((AUX) & 128) != 0 && (C % (64 * CPL)) == 0);
+        // (lean_rw: the lists of a lean plan are in the lean format exactly when C fills whole waves)
+#define WSSDL_X(ID, RH, RW, SH, SW, D, MW, CPL, AUX, I32) \
+        case ID: return prepare_lists(rois, R, N, H, W, C, PH, PW, SH, SW, workspace, workspace_bytes, st, \
+                                      (((AUX) & 128) != 0 && (C % (64 * CPL)) == 0) ? RW : 0, \
+                                      [&](dim3 grid, int tiles_h, int tiles_w, const WalkWs &ws) { \
+                                          hipLaunchKernelGGL((walk_axes_own_kernel<RH, RW, SH, SW>), grid, dim3(256), 0, st, rois, R, N, \
+                                                             H, W, PH, PW, scale, rounding, tiles_h, tiles_w, ws.rowtab, ws.coltab); \
+                                      });
         WSSDL_OWNER_PLANS(WSSDL_X)
 #undef WSSDL_X
         default: return WSSDL_ERR_INVALID_ARGUMENT;
     }
 }
 
-template <int ID, int RH, int RW, int SH, int SW, int DEPTH, int MINW, int CPL, int AUX>
-static int launch_owner_t(const float *top_diff, const unsigned char *arg8, int R, int N, int H, int W, int C, int PH,
-                          int PW, float *bottom_diff, void *workspace, size_t workspace_bytes, float *halo, hipStream_t st,
-                          bool i32, int nseg) {
-    const int tiles_h = cdiv(H, SH), tiles_w = cdiv(W, SW), tiles = tiles_h * tiles_w;
-    const int items = N * tiles;
-    if (nseg < 1 || nseg > WALK_MAX_SEGMENTS || (i32 && nseg != 1)) return WSSDL_ERR_INVALID_ARGUMENT;
-    WalkWs ws;
-    if (carve_walk(workspace, R, N, tiles_h, tiles_w, walk_record_bound(R, N, H, W, PH, PW, SH, SW), &ws) > workspace_bytes)
-        return WSSDL_ERR_WORKSPACE;
-    const unsigned total_elems = (unsigned)((long long)R * PH * PW * C);
-    const int G = cdiv(C, 64 * CPL);
-    long long blocks;
-    if ((G & 7) == 0) blocks = (long long)items * G;
-    else if (G < 8 && (8 % G) == 0) blocks = 8LL * cdiv(items, 8 / G);
-    else blocks = (long long)items * G;
-    if (blocks > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
-    WalkI32 q = {0, 0u, 0u};
-    // (the i32 arg-max -- the reference op's own layout -- is built for owner plans 0 and 1: tools/bwd_fixed_sweep.py --i32-owner)
-    constexpr bool I32_BUILT = ID == 0 || ID == 1;
-    if (i32 && !I32_BUILT) return WSSDL_ERR_INVALID_ARGUMENT;
-    if constexpr (I32_BUILT) if (i32) {
-        if (!walk_i32_params(H, W, C, &q)) return WSSDL_ERR_INVALID_ARGUMENT;
-        hipLaunchKernelGGL((roi_pool_bwd_walk_kernel<RH, RW, DEPTH, MINW, CPL, true, true, AUX>), dim3((unsigned)blocks, 1u), dim3(64),
-                           0, st, top_diff, arg8, reinterpret_cast<const unsigned *>(ws.slots), ws.tile_off, ws.tile_slots,
-                           ws.order, items, tiles_w, tiles, G, H, W, C, total_elems, bottom_diff, 1, halo, 0ull, q, SH, SW);
-    }
-    if (!i32)
-    hipLaunchKernelGGL((roi_pool_bwd_walk_kernel<RH, RW, DEPTH, MINW, CPL, false, true, AUX>), dim3((unsigned)blocks, (unsigned)nseg), dim3(64),
-                       0, st, top_diff, arg8, reinterpret_cast<const unsigned *>(ws.slots), ws.tile_off, ws.tile_slots,
-                       ws.order, items, tiles_w, tiles, G, H, W, C, total_elems, bottom_diff, nseg, halo, 0ull, q, SH, SW);
-    if (nseg > 1) {
-        const long long cells = (long long)N * H * W;
-        if (cells > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
-        hipLaunchKernelGGL(walk_merge_split_kernel, dim3((unsigned)cells), dim3(256), 0, st, bottom_diff, halo, N, H, W, C / 4,
-                           tiles_h, tiles_w, RH, RW, SH, SW, nseg);
-        return check_launch();
-    }
-    constexpr int HH = RH - SH, HW = RW - SW;
-    constexpr int ncell = SH * SW - (SH - HH) * (SW - HW);
-    if (ncell > 0)
-        hipLaunchKernelGGL(walk_merge_kernel, dim3((unsigned)items, (unsigned)ncell), dim3(256), 0, st, bottom_diff, halo, H, W,
-                           C / 4, tiles_h, tiles_w, RH, RW, SH, SW);
-    return check_launch();
-}
-
 int launch_owner(const float *top_diff, const unsigned char *arg8, int R, int N, int H, int W, int C, int PH, int PW,
                  float *bottom_diff, void *workspace, size_t workspace_bytes, int plan, float *halo, hipStream_t st, bool i32,
                  int nseg) {
     switch (plan) {
-#define WSSDL_X(ID, RH, RW, SH, SW, D, MW, CPL, AUX) \
-        case ID: return launch_owner_t<ID, RH, RW, SH, SW, D, MW, CPL, AUX>(top_diff, arg8, R, N, H, W, C, PH, PW, bottom_diff, workspace, \
-                                                                workspace_bytes, halo, st, i32, nseg);
+#define WSSDL_X(ID, RH, RW, SH, SW, D, MW, CPL, AUX, I32) \
+        case ID: return launch_lists<RH, RW, SH, SW, D, MW, CPL, true, AUX, I32>(top_diff, arg8, R, N, H, W, C, PH, PW, bottom_diff, \
+                                                                            workspace, workspace_bytes, st, nseg, halo, i32);
         WSSDL_OWNER_PLANS(WSSDL_X)
 #undef WSSDL_X
         default: return WSSDL_ERR_INVALID_ARGUMENT;

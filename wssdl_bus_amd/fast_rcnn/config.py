@@ -118,7 +118,8 @@ __C.ROI_POOL_FLAG_CHECK = "deferred"
 # rows kernel).  The tables are 3.75 x the feature map, allocated per call.
 __C.ROI_POOL_FWD_BLOCKS = 'auto'
 # RoI-pool backward of the training path on launches with few images (<= 4) and many RoIs per image (>= 1000):
-# 'auto' = the library's rule (wssdl_roi_pool_backward_split_segments: 4 segments there, the exact walk
+# 'auto' = the library's rule (wssdl_roi_pool_backward_split_segments, for N * C <= 3072 (image, channel) pairs: 8
+# segments below 2048 pairs; 4 at 2048 pairs on one or two images and at 2049-3072 pairs on three; the exact walk
 # everywhere else), an int = that many segments, 0 = always the exact walk.  The split form is deterministic but
 # associates each element's f32 sum differently from the reference (within ~1e-7 of it; north_star's tolerance
 # for RoI pooling is 1e-5); the parity tests of the gradient run the exact walk.
@@ -126,11 +127,13 @@ __C.ROI_POOL_BWD_SPLIT = 'auto'
 # RoI-pool backward of the training path on train-sized launches: the bin-owner form (round 5: every bin read once by
 # the tile of its window's first cell, halos merged in a fixed order; 10-25 % faster than the exact walk,
 # deterministic, within ~1e-6 of the reference's ordered sum).  'auto' = the library's rule
-# (wssdl_roi_pool_backward_owner_plan_for: R >= 1536 RoIs, C % 128 == 0, N * C >= 2048 (image, channel) pairs, pooled
-# size <= 8 x 8 -> owner plan 8; anything else -1 = the split form / exact walk), an int = that owner plan, -1 = never.
+# (wssdl_roi_pool_backward_owner_plan_for: R >= 1536 RoIs, C % 128 == 0, pooled size <= 8 x 8; from N * C = 512
+# (image, channel) pairs owner plan 9, from 1024 pairs owner plan 8, and below 2048 pairs two waves per tile stream
+# (ROI_POOL_BWD_OWNER_SEGMENTS); anything else -1 = the split form / exact walk), an int = that owner plan, -1 = never.
 # Takes precedence over the split form.  Its halo scratch is N * tiles * 42 cells * C * 4 bytes per backward call
-# (179 MB at 8 x 38 x 63 x 1024, 2.3 x bottom_diff; only the halo cells are touched).  train_bus prints the form the
-# first backward of a run takes (BackwardPlan.variant).
+# (179 MB at 8 x 38 x 63 x 1024, 2.3 x bottom_diff; only the halo cells are touched).
+# roi_pooling_op._announce_backward_form prints the form the first backward of each launch class takes
+# (BackwardPlan.variant).
 __C.ROI_POOL_BWD_OWNER = 'auto'
 # waves per tile stream of the bin-owner form: 'auto' = the library's rule (wssdl_roi_pool_backward_owner_segments: more
 # than one on launches with few (image, channel) pairs, whose longest streams the whole chip would otherwise wait for),

@@ -30,6 +30,31 @@ def _check_inputs(bottom_data, bottom_rois):
         raise ValueError("rois must be [R, 5]")
 
 
+class _Geom(object):
+    """What every entry point below hands to the C ABI: the feature map's shape, the length of the RoI list, the
+    int-cast pooled sizes, the scale as a float and the rounding mode (cfg.ROI_POOL_ROUNDING unless given)."""
+
+    def __init__(self, shape, rois, pooled_height, pooled_width, spatial_scale, rounding=None):
+        self.nhwc = self.N, self.H, self.W, self.C = tuple(int(v) for v in shape)
+        self.R = int(rois.shape[0])
+        self.pooled = self.ph, self.pw = int(pooled_height), int(pooled_width)
+        self.scale = float(spatial_scale)
+        self.mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
+
+    def meta(self, **extra):
+        """The timeline record's meta dict: the launch shape plus what is particular to the form."""
+        return dict(N=self.N, H=self.H, W=self.W, C=self.C, R=self.R, **extra)
+
+    def top_shape(self):
+        return (self.R, self.ph, self.pw, self.C)
+
+
+def _run(name, meta, export, *args):
+    """One C-ABI call on the current stream: timed under `name` (bench.py reads these records), its status checked."""
+    with _lib.timed(name, meta):
+        _lib.check(getattr(_lib.lib(), export)(*(args + (_lib.stream(),))), export)
+
+
 def roi_pool(bottom_data, bottom_rois, pooled_height, pooled_width, spatial_scale, name=None,
              rounding=None):
     """Forward op: returns ``(top_data, argmax)`` like the TF op's two outputs."""
@@ -37,16 +62,12 @@ def roi_pool(bottom_data, bottom_rois, pooled_height, pooled_width, spatial_scal
     data = _lib.to_device(bottom_data, torch.float32)
     rois = _lib.to_device(bottom_rois, torch.float32, data.device)
     _check_inputs(data, rois)
-    N, H, W, C = data.shape
-    R = rois.shape[0]
-    mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
-    top = torch.empty((R, pooled_height, pooled_width, C), dtype=torch.float32, device=data.device)
-    arg = torch.empty((R, pooled_height, pooled_width, C), dtype=torch.int32, device=data.device)
-    with torch.cuda.device(data.device), _lib.timed("roi_pool_forward", dict(N=N, H=H, W=W, C=C, R=R)):
-        _lib.check(_lib.lib().wssdl_roi_pool_forward(
-            _lib.ptr(data), N, H, W, C, _lib.ptr(rois), R, int(pooled_height), int(pooled_width),
-            float(spatial_scale), mode, _lib.ptr(top), _lib.ptr(arg), _lib.stream()),
-            "wssdl_roi_pool_forward")
+    g = _Geom(data.shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
+    top = torch.empty(g.top_shape(), dtype=torch.float32, device=data.device)
+    arg = torch.empty(g.top_shape(), dtype=torch.int32, device=data.device)
+    with torch.cuda.device(data.device):
+        _run("roi_pool_forward", g.meta(), "wssdl_roi_pool_forward", _lib.ptr(data), g.N, g.H, g.W, g.C, _lib.ptr(rois), g.R,
+             g.ph, g.pw, g.scale, g.mode, _lib.ptr(top), _lib.ptr(arg))
     if as_np:
         return top.cpu().numpy(), arg.cpu().numpy()
     return top, arg
@@ -68,19 +89,15 @@ def roi_pool_grad(bottom_data, bottom_rois, argmax, grad, pooled_height, pooled_
         raise ValueError("argmax_data must be 4-dimensional")
     if g.dim() != 4:
         raise ValueError("out_backprop must be 4-dimensional")
-    N, H, W, C = shape
+    q = _Geom(shape, rois, pooled_height, pooled_width, spatial_scale)
     out = torch.empty(shape, dtype=torch.float32, device=g.device)
-    L = _lib.lib()
     with torch.cuda.device(g.device):
         # the list-driven kernels read the i32 arg-max too when they get a workspace for their lists
         # (wssdl_roi_pool_backward_ws; shapes they do not take run the kernel of wssdl_roi_pool_backward)
-        nws = L.wssdl_roi_pool_backward_workspace_bytes(rois.shape[0], N, H, W, int(pooled_height), int(pooled_width))
+        nws = _lib.lib().wssdl_roi_pool_backward_workspace_bytes(q.R, q.N, q.H, q.W, q.ph, q.pw)
         ws = torch.empty((nws,), dtype=torch.uint8, device=g.device) if nws else None
-        with _lib.timed("roi_pool_backward", dict(N=N, H=H, W=W, C=C, R=rois.shape[0])):
-            _lib.check(L.wssdl_roi_pool_backward_ws(
-                _lib.ptr(g), _lib.ptr(arg), _lib.ptr(rois), rois.shape[0], N, H, W, C,
-                int(pooled_height), int(pooled_width), float(spatial_scale), _lib.ptr(out), _lib.ptr(ws), nws,
-                _lib.stream()), "wssdl_roi_pool_backward_ws")
+        _run("roi_pool_backward", q.meta(), "wssdl_roi_pool_backward_ws", _lib.ptr(g), _lib.ptr(arg), _lib.ptr(rois), q.R,
+             q.N, q.H, q.W, q.C, q.ph, q.pw, q.scale, _lib.ptr(out), _lib.ptr(ws), nws)
     return out.cpu().numpy() if as_np else out
 
 
@@ -192,7 +209,8 @@ def poll_flags():
 def check_flags():
     """Synchronising check: raises HipCallError if any compact RoI-pool call raised a flag, or if an earlier sync-free
     poll swallowed an NMS time-out (a step that was applied with an image's proposals missing: tainted_steps()).  The
-    train loop calls this before it writes a snapshot."""
+    caller must call it -- before it writes a snapshot or reports a result; the package's own training loop does not
+    (it polls with poll_flags())."""
     for f in list(_device_flags.values()):
         _DeviceFlags._raise(f.read_and_clear())
     if _tainted["steps"]:
@@ -225,63 +243,56 @@ def compact_overflowed(device=None):
 _WINDOW_TABLE_MIN_ROIS = 1024
 
 
+def _forward_form(g):
+    """Which form the compact forward of this launch takes, decided once: ('small', 0, 0), ('windows', table bytes, 0)
+    or ('blocks', table bytes, block-table bytes)."""
+    L = _lib.lib()
+    # the window table: a launch of its own only pays off on a train-sized RoI list
+    nwin = L.wssdl_roi_pool_forward_windows_bytes(g.R, g.H, g.W, g.C, g.ph, g.pw) \
+        if (g.R >= _WINDOW_TABLE_MIN_ROIS and _lib.get_tuning("roi_fwd_variant") == 0) else 0
+    if not nwin:
+        return "small", 0, 0
+    # many proposals per image (large, overlapping windows): block-maximum tables of this step's feature map,
+    # four table reads per bin instead of a scan of its cells (csrc/roi_pool_blocks.hip; same bits)
+    want_blocks = cfg.get("ROI_POOL_FWD_BLOCKS", "auto")
+    if want_blocks == "auto":
+        want_blocks = L.wssdl_roi_pool_forward_blocks_auto(g.R, g.N, g.H, g.W, g.C, g.ph, g.pw)
+    nblk = L.wssdl_roi_pool_forward_blocks_bytes(g.R, g.N, g.H, g.W, g.C, g.ph, g.pw) if want_blocks else 0
+    return ("blocks" if nblk else "windows"), nwin, nblk
+
+
 def roi_pool_compact(data, rois, pooled_height, pooled_width, spatial_scale, rounding=None):
     """GPU tensors in, ``(top_data f32, argmax8 u8)`` out."""
     _check_inputs(data, rois)
-    N, H, W, C = data.shape
-    R = rois.shape[0]
-    mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
-    top = torch.empty((R, pooled_height, pooled_width, C), dtype=torch.float32, device=data.device)
-    arg8 = torch.empty((R, pooled_height, pooled_width, C), dtype=torch.uint8, device=data.device)
-    L = _lib.lib()
+    g = _Geom(data.shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
+    top = torch.empty(g.top_shape(), dtype=torch.float32, device=data.device)
+    arg8 = torch.empty(g.top_shape(), dtype=torch.uint8, device=data.device)
     with torch.cuda.device(data.device):
-        # (a launch of its own only pays off on a train-sized RoI list)
-        nwin = L.wssdl_roi_pool_forward_windows_bytes(R, H, W, C, int(pooled_height), int(pooled_width)) \
-            if (R >= _WINDOW_TABLE_MIN_ROIS and _lib.get_tuning("roi_fwd_variant") == 0) else 0
-        if nwin:
+        form, nwin, nblk = _forward_form(g)
+        table = torch.empty((nwin,), dtype=torch.uint8, device=data.device) if nwin else None
+        blocks = torch.empty((nblk,), dtype=torch.uint8, device=data.device) if nblk else None
+        p = dict(data=_lib.ptr(data), rois=_lib.ptr(rois), top=_lib.ptr(top), arg8=_lib.ptr(arg8),
+                 flag=_lib.ptr(_overflow_flag(data.device)), table=_lib.ptr(table), blocks=_lib.ptr(blocks))
+        nhwc, pooled, pooling = g.nhwc, g.pooled, g.meta(argmax_bytes=1)
+        if form == "small":
+            steps = [("roi_pool_forward", pooling, "wssdl_roi_pool_forward_compact",
+                      (p["data"],) + nhwc + (p["rois"], g.R) + pooled + (g.scale, g.mode, p["top"], p["arg8"], p["flag"]))]
+        elif form == "windows":
             # the RoI geometry once per (roi, bin row) into a table, then the pooling kernel reads it with
             # scalar loads (two launches, timed apart: the second is the kernel the roofline is quoted on)
-            table = torch.empty((nwin,), dtype=torch.uint8, device=data.device)
-            # many proposals per image (large, overlapping windows): block-maximum tables of this step's feature map,
-            # four table reads per bin instead of a scan of its cells (csrc/roi_pool_blocks.hip; same bits)
-            want_blocks = cfg.get("ROI_POOL_FWD_BLOCKS", "auto")
-            if want_blocks == "auto":
-                want_blocks = L.wssdl_roi_pool_forward_blocks_auto(R, N, H, W, C, int(pooled_height), int(pooled_width))
-            nblk = L.wssdl_roi_pool_forward_blocks_bytes(R, N, H, W, C, int(pooled_height), int(pooled_width)) \
-                if want_blocks else 0
-            if nblk:
-                blocks = torch.empty((nblk,), dtype=torch.uint8, device=data.device)
-                with _lib.timed("roi_pool_forward_windows", dict(R=R)):
-                    _lib.check(L.wssdl_roi_pool_forward_windows_blocks(
-                        _lib.ptr(rois), R, N, H, W, C, int(pooled_height), int(pooled_width), float(spatial_scale), mode,
-                        _lib.ptr(table), nwin, _lib.ptr(_overflow_flag(data.device)), _lib.ptr(blocks), nblk,
-                        _lib.stream()), "wssdl_roi_pool_forward_windows_blocks")
-                with _lib.timed("roi_pool_forward_blocks_prepare", dict(N=N, H=H, W=W, C=C, R=R)):
-                    _lib.check(L.wssdl_roi_pool_forward_blocks_prepare(
-                        _lib.ptr(data), N, H, W, C, R, int(pooled_height), int(pooled_width), _lib.ptr(table),
-                        _lib.ptr(blocks), nblk, _lib.stream()), "wssdl_roi_pool_forward_blocks_prepare")
-                with _lib.timed("roi_pool_forward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1, blocks=1)):
-                    _lib.check(L.wssdl_roi_pool_forward_compact_blocks(
-                        _lib.ptr(data), N, H, W, C, R, int(pooled_height), int(pooled_width), _lib.ptr(table),
-                        _lib.ptr(blocks), nblk, _lib.ptr(top), _lib.ptr(arg8), _lib.stream()),
-                        "wssdl_roi_pool_forward_compact_blocks")
-                return top, arg8
-            with _lib.timed("roi_pool_forward_windows", dict(R=R)):
-                _lib.check(L.wssdl_roi_pool_forward_windows(
-                    _lib.ptr(rois), R, N, H, W, C, int(pooled_height), int(pooled_width), float(spatial_scale), mode,
-                    _lib.ptr(table), nwin, _lib.ptr(_overflow_flag(data.device)), _lib.stream()),
-                    "wssdl_roi_pool_forward_windows")
-            with _lib.timed("roi_pool_forward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1)):
-                _lib.check(L.wssdl_roi_pool_forward_compact_windows(
-                    _lib.ptr(data), N, H, W, C, _lib.ptr(rois), R, int(pooled_height), int(pooled_width),
-                    float(spatial_scale), mode, _lib.ptr(table), _lib.ptr(top), _lib.ptr(arg8), _lib.stream()),
-                    "wssdl_roi_pool_forward_compact_windows")
+            steps = [("roi_pool_forward_windows", dict(R=g.R), "wssdl_roi_pool_forward_windows",
+                      (p["rois"], g.R) + nhwc + pooled + (g.scale, g.mode, p["table"], nwin, p["flag"])),
+                     ("roi_pool_forward", pooling, "wssdl_roi_pool_forward_compact_windows",
+                      (p["data"],) + nhwc + (p["rois"], g.R) + pooled + (g.scale, g.mode, p["table"], p["top"], p["arg8"]))]
         else:
-            with _lib.timed("roi_pool_forward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1)):
-                _lib.check(L.wssdl_roi_pool_forward_compact(
-                    _lib.ptr(data), N, H, W, C, _lib.ptr(rois), R, int(pooled_height), int(pooled_width),
-                    float(spatial_scale), mode, _lib.ptr(top), _lib.ptr(arg8), _lib.ptr(_overflow_flag(data.device)),
-                    _lib.stream()), "wssdl_roi_pool_forward_compact")
+            steps = [("roi_pool_forward_windows", dict(R=g.R), "wssdl_roi_pool_forward_windows_blocks",
+                      (p["rois"], g.R) + nhwc + pooled + (g.scale, g.mode, p["table"], nwin, p["flag"], p["blocks"], nblk)),
+                     ("roi_pool_forward_blocks_prepare", g.meta(), "wssdl_roi_pool_forward_blocks_prepare",
+                      (p["data"],) + nhwc + (g.R,) + pooled + (p["table"], p["blocks"], nblk)),
+                     ("roi_pool_forward", g.meta(argmax_bytes=1, blocks=1), "wssdl_roi_pool_forward_compact_blocks",
+                      (p["data"],) + nhwc + (g.R,) + pooled + (p["table"], p["blocks"], nblk, p["top"], p["arg8"]))]
+        for name, meta, export, args in steps:
+            _run(name, meta, export, *args)
     return top, arg8
 
 
@@ -297,6 +308,23 @@ class BackwardPlan(object):
         self.segments, self.variant = 1, "exact walk: the reference's summation order, bit for bit"
 
 
+def _prepare_lists(g, rois, export, meta, plan_arg, built=lambda: True):
+    """The shared body of the two prepare steps: allocate the list workspace, make the timed call, and OR the status
+    block's error word into the deferred flag [1] (device side, no read-back) when `built()` says lists exist.
+    Returns (workspace, its size)."""
+    L = _lib.lib()
+    with torch.cuda.device(rois.device):
+        nws = L.wssdl_roi_pool_backward_workspace_bytes(g.R, g.N, g.H, g.W, g.ph, g.pw)
+        ws = torch.empty((nws,), dtype=torch.uint8, device=rois.device) if nws else None
+        with _lib.timed("roi_pool_backward_prepare", meta):
+            _lib.check(getattr(L, export)(_lib.ptr(rois), g.R, g.N, g.H, g.W, g.C, g.ph, g.pw, g.scale, g.mode, _lib.ptr(ws),
+                                          nws, plan_arg, _lib.stream()), export)
+            if built():
+                off = L.wssdl_roi_pool_backward_status_offset(g.R, g.N, g.H, g.W, g.ph, g.pw)
+                _flags(rois.device).flags[1:2].bitwise_or_(ws[off + 4:off + 8].view(torch.int32))
+    return ws, nws
+
+
 def roi_pool_grad_prepare(shape, rois, pooled_height, pooled_width, spatial_scale, rounding=None, segments=1):
     """Build the lists that drive the compact backward.  They depend on the RoIs and the shapes
     only, so the autograd pair does this right behind the forward (off the backward's path).
@@ -304,22 +332,10 @@ def roi_pool_grad_prepare(shape, rois, pooled_height, pooled_width, spatial_scal
     if segments > 1 and _lib.get_tuning("roi_bwd_plan") < 0:
         with _lib.tuned(roi_bwd_plan=int(_lib.lib().wssdl_roi_pool_backward_split_plan())):
             return roi_pool_grad_prepare(shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
-    N, H, W, C = shape
-    mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
-    L = _lib.lib()
-    R = rois.shape[0]
-    plan = ctypes.c_int32(-1)
-    with torch.cuda.device(rois.device):
-        nws = L.wssdl_roi_pool_backward_workspace_bytes(R, N, H, W, int(pooled_height), int(pooled_width))
-        ws = torch.empty((nws,), dtype=torch.uint8, device=rois.device) if nws else None
-        with _lib.timed("roi_pool_backward_prepare", dict(N=N, H=H, W=W, C=C, R=R)):
-            _lib.check(L.wssdl_roi_pool_backward_prepare(
-                _lib.ptr(rois), R, N, H, W, C, int(pooled_height), int(pooled_width), float(spatial_scale),
-                mode, _lib.ptr(ws), nws, ctypes.byref(plan), _lib.stream()), "wssdl_roi_pool_backward_prepare")
-            if plan.value >= 0:
-                # the status block's error word joins the deferred flags (device-side OR, no read-back)
-                off = L.wssdl_roi_pool_backward_status_offset(R, N, H, W, int(pooled_height), int(pooled_width))
-                _flags(rois.device).flags[1:2].bitwise_or_(ws[off + 4:off + 8].view(torch.int32))
+    g = _Geom(shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
+    plan = ctypes.c_int32(-1)          # (-1 afterwards: no lists, the backward filters the RoIs itself)
+    ws, nws = _prepare_lists(g, rois, "wssdl_roi_pool_backward_prepare", g.meta(), ctypes.byref(plan),
+                             built=lambda: plan.value >= 0)
     return BackwardPlan(ws, nws, int(plan.value))
 
 
@@ -352,19 +368,8 @@ def owner_segments(shape, R):
 
 def roi_pool_grad_prepare_owner(shape, rois, pooled_height, pooled_width, spatial_scale, owner, rounding=None):
     """Lists of the bin-owner form (every bin listed once, by the tile of its window's first cell)."""
-    N, H, W, C = shape
-    mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
-    L = _lib.lib()
-    R = rois.shape[0]
-    with torch.cuda.device(rois.device):
-        nws = L.wssdl_roi_pool_backward_workspace_bytes(R, N, H, W, int(pooled_height), int(pooled_width))
-        ws = torch.empty((nws,), dtype=torch.uint8, device=rois.device)
-        with _lib.timed("roi_pool_backward_prepare", dict(N=N, H=H, W=W, C=C, R=R, owner=int(owner))):
-            _lib.check(L.wssdl_roi_pool_backward_owner_prepare(
-                _lib.ptr(rois), R, N, H, W, C, int(pooled_height), int(pooled_width), float(spatial_scale),
-                mode, _lib.ptr(ws), nws, int(owner), _lib.stream()), "wssdl_roi_pool_backward_owner_prepare")
-            off = L.wssdl_roi_pool_backward_status_offset(R, N, H, W, int(pooled_height), int(pooled_width))
-            _flags(rois.device).flags[1:2].bitwise_or_(ws[off + 4:off + 8].view(torch.int32))
+    g = _Geom(shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
+    ws, nws = _prepare_lists(g, rois, "wssdl_roi_pool_backward_owner_prepare", g.meta(owner=int(owner)), int(owner))
     return BackwardPlan(ws, nws, -1, owner=int(owner))
 
 
@@ -405,76 +410,66 @@ def split_segments(shape, R):
     return max(1, int(v))
 
 
+class _PlanSegments(int):
+    """The default of `segments=` below: reads as 1, and lets the call tell "not passed" from an explicit 1."""
+
+
+_PLAN_SEGMENTS = _PlanSegments(1)
+
+
+def _backward_form(g, plan, segments):
+    """The one place that maps a plan to its launch: (export, the arguments between the workspace and the scratch,
+    the scratch-size query or None, what the form adds to the timeline record's meta)."""
+    L, shape = _lib.lib(), g.nhwc
+    if plan.owner >= 0 and int(plan.owner_segments) > 1:
+        nseg = int(plan.owner_segments)
+        return ("wssdl_roi_pool_backward_compact_owner_split", (plan.owner, nseg),
+                lambda: L.wssdl_roi_pool_backward_owner_split_scratch_bytes(*(shape + (plan.owner, nseg))),
+                dict(owner=plan.owner, owner_segments=nseg))
+    if plan.owner >= 0:
+        return ("wssdl_roi_pool_backward_compact_owner", (plan.owner,),
+                lambda: L.wssdl_roi_pool_backward_owner_scratch_bytes(*(shape + (plan.owner,))), dict(owner=plan.owner))
+    if segments > 1:
+        return ("wssdl_roi_pool_backward_compact_split", (plan.plan, segments),
+                lambda: L.wssdl_roi_pool_backward_split_scratch_bytes(*(shape + (segments,))),
+                dict(plan=plan.plan, segments=segments))
+    return "wssdl_roi_pool_backward_compact", (plan.plan,), None, dict(plan=plan.plan)
+
+
 def roi_pool_grad_compact(shape, rois, arg8, grad, pooled_height, pooled_width, spatial_scale,
-                          rounding=None, use_workspace=True, plan=None, segments=1):
-    """bottom_diff from the 1-byte arg-max.  `plan` = what roi_pool_grad_prepare returned for these
-    RoIs (prepared here when None and use_workspace).  `segments` > 1: the split form
-    (wssdl_roi_pool_backward_compact_split; deterministic, not bit-ordered -- see split_segments)."""
-    N, H, W, C = shape
-    mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
+                          rounding=None, use_workspace=True, plan=None, segments=_PLAN_SEGMENTS):
+    """bottom_diff from the 1-byte arg-max.  `plan` = what roi_pool_grad_prepare / prepare_backward returned for these
+    RoIs (prepared here when None and use_workspace); its owner plan and segment counts choose the form.  `segments`,
+    when passed, overrides the plan's own: > 1 is the split form (wssdl_roi_pool_backward_compact_split;
+    deterministic, not bit-ordered -- see split_segments), 1 the exact walk."""
+    g = _Geom(shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
     out = torch.empty(shape, dtype=torch.float32, device=grad.device)
-    L = _lib.lib()
-    R = rois.shape[0]
     if plan is None and use_workspace:
         plan = roi_pool_grad_prepare(shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
-    if plan is not None and plan.owner >= 0 and getattr(plan, "owner_segments", 1) > 1:
-        nseg = int(plan.owner_segments)
-        with torch.cuda.device(grad.device):
-            nscr = L.wssdl_roi_pool_backward_owner_split_scratch_bytes(N, H, W, C, plan.owner, nseg)
-            scratch = torch.empty((nscr,), dtype=torch.uint8, device=grad.device)
-            with _lib.timed("roi_pool_backward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1, owner=plan.owner,
-                                                      owner_segments=nseg)):
-                _lib.check(L.wssdl_roi_pool_backward_compact_owner_split(
-                    _lib.ptr(grad), _lib.ptr(arg8), _lib.ptr(rois), R, N, H, W, C,
-                    int(pooled_height), int(pooled_width), float(spatial_scale), mode, _lib.ptr(out),
-                    _lib.ptr(plan.workspace), plan.nbytes, plan.owner, nseg, _lib.ptr(scratch), nscr,
-                    _lib.stream()), "wssdl_roi_pool_backward_compact_owner_split")
-        return out
-    if plan is not None and plan.owner >= 0:
-        with torch.cuda.device(grad.device):
-            nscr = L.wssdl_roi_pool_backward_owner_scratch_bytes(N, H, W, C, plan.owner)
-            scratch = torch.empty((nscr,), dtype=torch.uint8, device=grad.device)
-            with _lib.timed("roi_pool_backward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1, owner=plan.owner)):
-                _lib.check(L.wssdl_roi_pool_backward_compact_owner(
-                    _lib.ptr(grad), _lib.ptr(arg8), _lib.ptr(rois), R, N, H, W, C,
-                    int(pooled_height), int(pooled_width), float(spatial_scale), mode, _lib.ptr(out),
-                    _lib.ptr(plan.workspace), plan.nbytes, plan.owner, _lib.ptr(scratch), nscr,
-                    _lib.stream()), "wssdl_roi_pool_backward_compact_owner")
-        return out
-    if plan is None or plan.plan < 0:
-        plan = BackwardPlan(None, 0, -1)
-    segments = int(segments) if plan.plan >= 0 else 1
-    if segments > 1:
-        with torch.cuda.device(grad.device):
-            nscr = L.wssdl_roi_pool_backward_split_scratch_bytes(N, H, W, C, segments)
-            scratch = torch.empty((nscr,), dtype=torch.uint8, device=grad.device)
-            with _lib.timed("roi_pool_backward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1, plan=plan.plan,
-                                                      segments=segments)):
-                _lib.check(L.wssdl_roi_pool_backward_compact_split(
-                    _lib.ptr(grad), _lib.ptr(arg8), _lib.ptr(rois), R, N, H, W, C,
-                    int(pooled_height), int(pooled_width), float(spatial_scale), mode, _lib.ptr(out),
-                    _lib.ptr(plan.workspace), plan.nbytes, plan.plan, segments, _lib.ptr(scratch), nscr,
-                    _lib.stream()), "wssdl_roi_pool_backward_compact_split")
-        return out
+    if segments is _PLAN_SEGMENTS:
+        segments = getattr(plan, "segments", 1)
+    if plan is None or (plan.owner < 0 and plan.plan < 0):
+        plan, segments = BackwardPlan(None, 0, -1), 1          # no lists: the kernel that filters the RoIs itself
+    export, form_args, scratch_bytes, form_meta = _backward_form(g, plan, int(segments))
     with torch.cuda.device(grad.device):
-        with _lib.timed("roi_pool_backward", dict(N=N, H=H, W=W, C=C, R=R, argmax_bytes=1, plan=plan.plan)):
-            _lib.check(L.wssdl_roi_pool_backward_compact(
-                _lib.ptr(grad), _lib.ptr(arg8), _lib.ptr(rois), R, N, H, W, C,
-                int(pooled_height), int(pooled_width), float(spatial_scale), mode, _lib.ptr(out),
-                _lib.ptr(plan.workspace), plan.nbytes, plan.plan, _lib.stream()),
-                "wssdl_roi_pool_backward_compact")
+        scratch_args = ()
+        if scratch_bytes is not None:
+            nscr = scratch_bytes()
+            scratch = torch.empty((nscr,), dtype=torch.uint8, device=grad.device)
+            scratch_args = (_lib.ptr(scratch), nscr)
+        _run("roi_pool_backward", g.meta(argmax_bytes=1, **form_meta), export, _lib.ptr(grad), _lib.ptr(arg8), _lib.ptr(rois),
+             g.R, g.N, g.H, g.W, g.C, g.ph, g.pw, g.scale, g.mode, _lib.ptr(out), _lib.ptr(plan.workspace), plan.nbytes,
+             *(form_args + scratch_args))
     return out
 
 
 def expand_argmax(arg8, rois, shape, pooled_height, pooled_width, spatial_scale, rounding=None):
     """1-byte codes -> the reference's i32 argmax (flat NHWC index inside the image, -1 empty)."""
-    N, H, W, C = shape
-    mode = _ROUNDING[cfg.ROI_POOL_ROUNDING if rounding is None else rounding]
+    g = _Geom(shape, rois, pooled_height, pooled_width, spatial_scale, rounding)
     out = torch.empty(tuple(arg8.shape), dtype=torch.int32, device=arg8.device)
     with torch.cuda.device(arg8.device):
         _lib.check(_lib.lib().wssdl_roi_argmax_expand(
-            _lib.ptr(arg8), _lib.ptr(rois), rois.shape[0], H, W, C, int(pooled_height),
-            int(pooled_width), float(spatial_scale), mode, _lib.ptr(out), _lib.stream()),
+            _lib.ptr(arg8), _lib.ptr(rois), g.R, g.H, g.W, g.C, g.ph, g.pw, g.scale, g.mode, _lib.ptr(out), _lib.stream()),
             "wssdl_roi_argmax_expand")
     return out
 
@@ -536,7 +531,7 @@ class RoiPoolFunction(torch.autograd.Function):
         shape, ph, pw, scale, rounding = ctx.geom
         if ctx.compact:
             bottom_diff = roi_pool_grad_compact(shape, rois, arg, grad_top.contiguous(), ph, pw, scale,
-                                                rounding, plan=ctx.plan, segments=getattr(ctx.plan, "segments", 1))
+                                                rounding, plan=ctx.plan)
         else:
             bottom_diff = roi_pool_grad(torch.empty(shape, device="meta"), rois, arg,
                                         grad_top.contiguous(), ph, pw, scale)
