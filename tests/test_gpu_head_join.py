@@ -165,3 +165,44 @@ def test_head_fused_joins_equal_unfused_route(torch_cuda, depth, mode, monkeypat
     for (k, ba), (_, bb) in zip(a.named_buffers(), b.named_buffers()):
         assert torch.equal(ba, bb), k
     assert list(a.state_dict().keys()) == list(b.state_dict().keys())
+
+
+def test_head_joins_without_autograd_in_training_mode(torch_cuda, monkeypatch):
+    """Training mode under torch.no_grad(): the head still takes the join kernels (its eligibility has no autograd
+    term, unlike the trunk's), while block 1's entry Function, which exists for its backward, is not taken.  Output
+    and every buffer equal the unfused route's bit for bit."""
+    torch = torch_cuda
+    from wssdl_bus_amd.networks import _plumbing, roi_head
+    R = 37
+    monkeypatch.setattr(_plumbing, "TAPS_MIN_ROIS", 1)        # the position-major route at any R
+    for s in ("WSSDL_HEAD_DENSE_3X3", "WSSDL_HEAD_UNFUSED_ENTRY"):
+        monkeypatch.delenv(s, raising=False)
+    torch.manual_seed(50)
+    a = roi_head.ResNetHeadNHWC(50).cuda()
+    with torch.no_grad():
+        for m in a.modules():
+            if isinstance(m, roi_head.RowBatchNorm):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.uniform_(-0.2, 0.2)
+                m.running_mean.uniform_(-0.1, 0.1)
+                m.running_var.uniform_(0.5, 2.0)
+    b = copy.deepcopy(a)
+    before = {k: v.clone() for k, v in a.named_buffers()}
+    assert a.training and b.training
+    g = torch.Generator(device="cuda").manual_seed(R)
+    x = torch.relu(torch.randn((R, 7, 7, 1024), device="cuda", generator=g))
+    assert a._tap_plans(x) is not None
+
+    calls = {"join": [], "entry": []}
+    for key, fn in (("join", roi_head._JoinFn), ("entry", roi_head._EntryNormFn)):
+        real = fn.apply
+        monkeypatch.setattr(fn, "apply", lambda *args, _r=real, _l=calls[key]: (_l.append(1), _r(*args))[1])
+    with torch.no_grad():
+        _, ya = _run_head(torch, a, x, None, False, monkeypatch)
+        assert (len(calls["join"]), len(calls["entry"])) == (3, 0), calls
+        _, yb = _run_head(torch, b, x, None, True, monkeypatch)
+    assert (len(calls["join"]), len(calls["entry"])) == (3, 0), calls
+    assert not ya.requires_grad and torch.equal(ya, yb)
+    for (k, ba), (_, bb) in zip(a.named_buffers(), b.named_buffers()):
+        assert torch.equal(ba, bb), k
+    assert all(not torch.equal(v, before[k]) for k, v in a.named_buffers()), "a norm did not track its statistics"

@@ -1,7 +1,10 @@
-"""ctypes binding of ``libwssdl_plumbing_hip.so``: fused row batch-norm (+ReLU) kernels for the
-per-RoI head (``csrc/plumbing/rowbn.hip``).  Plumbing around the hot path, not the drop-in C
-ABI; when the library has not been built the head falls back to stock PyTorch ops (slower,
-same maths) and says so once."""
+"""ctypes binding of ``libwssdl_plumbing_hip.so``: the fused row batch-norm (+ReLU) and residual-join kernels
+(``csrc/plumbing/rowbn.hip``), the 3x3 patch kernels (``im2col.hip``) and the class-packed 3x3 convolutions
+(``taps.hip``) of the two networks.  Plumbing around the hot path, not the drop-in C ABI; when the library has not
+been built the networks fall back to stock PyTorch ops (slower, same maths) and say so once.  Imports no sibling
+module: networks/rownorm.py, backbones.py and roi_head.py build on it, in that order.  Every export goes through
+`_call`; the `*_usable` predicates, `fused_running_stats`, `running_of`, TAPS_MIN_ROIS and TAP_GEMM_GROUPED are
+looked up as attributes of this module at call time (tests patch them)."""
 import ctypes
 import os
 import warnings
@@ -66,6 +69,31 @@ def lib():
     return _lib
 
 
+# The A/B switches of the two networks: environment variables, set to anything non-empty, that take one fused route
+# out for a measurement or a test.  Read at call time (switch), never cached: tests set them mid-process.
+SWITCHES = {
+    "WSSDL_DISABLE_FUSED_BN": "no row batch-norm kernel at all: stock PyTorch ops (usable)",
+    "WSSDL_BN_TORCH_RUNNING_STATS": "running statistics by torch's lerp_, not the finish kernels (fused_running_stats)",
+    "WSSDL_HEAD_UNFUSED_ENTRY": "block 1's entry: torch's scatter and add, then the plain backward (entry_usable)",
+    "WSSDL_HEAD_UNFUSED_JOIN": "the head's residual joins: separate norms and a torch add (join_usable)",
+    "WSSDL_TRUNK_UNFUSED_JOIN": "the trunk's residual joins: separate layers (backbones._join)",
+    "WSSDL_DISABLE_FUSED_IM2COL": "3x3 patches by pad / unfold, not the patch kernels (im2col_usable)",
+    "WSSDL_HEAD_DENSE_3X3": "the head's 3x3 convolutions on the dense patch route (taps_usable)",
+}
+
+
+def switch(name):
+    assert name in SWITCHES, name
+    return bool(os.environ.get(name))
+
+
+def _same_pad(size, k, s):
+    """TF 'SAME' padding along one axis: (before, after)."""
+    out = -(-size // s)
+    total = max((out - 1) * s + k - size, 0)
+    return total // 2, total - total // 2
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
@@ -74,18 +102,36 @@ def _pn(t):
     return _p(t) if t is not None else None
 
 
-def _check(rc, name):
-    if rc:
-        raise RuntimeError("%s failed (%d)" % (name, rc))
-
-
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _call(name, dev, *args, tail=()):
+    """One export on `dev` and its current stream (the argument after `args`; `tail` follows it); raises on rc != 0."""
+    with torch.cuda.device(dev):
+        rc = getattr(lib(), name)(*args, _stream(), *tail)
+    if rc:
+        raise RuntimeError("%s failed (%d)" % (name, rc))
+
+
+def _mask_args(mask, M):
+    """(mask, n_rois, rows per RoI) as the exports take them, (None, 0, 1) without a mask."""
+    if mask is None:
+        return None, 0, 1
+    n_rois = mask.shape[0]
+    assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
+    return _p(mask), n_rois, M // n_rois
+
+
+def _workspace(x, join=False):
+    """The scratch bytes a forward or backward over the [M, C] tensor x needs (`join`: of the join kernels)."""
+    sizer = lib().wsplumb_rowbn_join_workspace_bytes if join else lib().wsplumb_rowbn_workspace_bytes
+    return torch.empty((sizer(x.shape[0], x.shape[1]),), dtype=torch.uint8, device=x.device)
+
+
 def usable(x):
     """True when the fused kernels can take this [M, C] tensor."""
-    if os.environ.get("WSSDL_DISABLE_FUSED_BN"):           # A/B switch for measurements
+    if switch("WSSDL_DISABLE_FUSED_BN"):
         return False
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
         return False
@@ -95,8 +141,8 @@ def usable(x):
 
 def fused_running_stats():
     """True when the forward finish kernel updates the layers' running statistics (rowbn.hip, struct Running);
-    WSSDL_BN_TORCH_RUNNING_STATS=1 (A/B switch) leaves them to torch's lerp_ as before."""
-    return not os.environ.get("WSSDL_BN_TORCH_RUNNING_STATS")
+    else torch's lerp_ does (rownorm.track)."""
+    return not switch("WSSDL_BN_TORCH_RUNNING_STATS")
 
 
 def running_of(bn):
@@ -117,100 +163,73 @@ def _run_args(running):
     return _p(rm), _p(rv), float(mom), _pn(nbt)
 
 
-def _workspace(L, M, C, dev):
-    n = L.wsplumb_rowbn_workspace_bytes(M, C)
-    return torch.empty((n,), dtype=torch.uint8, device=dev), n
-
-
 def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False, *, running=None):
     """mask: [n_rois] f32 on x's device (0 = dead RoI), x = [n_rois * per, C] with row r belonging to RoI
     r // per, or r % n_rois when pos_major; returns (y, stats, count) where count is None without a mask,
     else a [1] tensor holding the number of live rows.  running: the layer's buffers to update in the same
     kernels (running_of), or None."""
-    L = lib()
     M, C = x.shape
-    dev = x.device
     y = torch.empty_like(x)
-    stats = torch.empty((5, C), dtype=torch.float32, device=dev)   # mean, var, rstd, scale, shift
-    count, n_rois = None, 0
-    if mask is not None:
-        n_rois = mask.shape[0]
-        assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
-        count = torch.empty((1,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, n = _workspace(L, M, C, dev)
-        _check(L.wsplumb_rowbn_forward(_p(x), M, C, _p(weight), _p(bias), float(eps), int(relu), _pn(mask), n_rois,
-                                       M // n_rois if n_rois else 1, int(bool(pos_major) and n_rois > 0), _p(y),
-                                       _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _pn(count),
-                                       _p(ws), n, _stream(), *_run_args(running)), "wsplumb_rowbn_forward")
+    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)   # mean, var, rstd, scale, shift
+    count = torch.empty((1,), dtype=torch.float32, device=x.device) if mask is not None else None
+    ws = _workspace(x)
+    _call("wsplumb_rowbn_forward", x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), int(relu),
+          *_mask_args(mask, M), int(bool(pos_major) and mask is not None), _p(y), *[_p(stats[i]) for i in range(5)],
+          _pn(count), _p(ws), ws.numel(), tail=_run_args(running))
     return y, stats, count
 
 
 def rowbn_apply(x, scale, shift, relu):
-    L = lib()
     M, C = x.shape
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = L.wsplumb_rowbn_apply(_p(x), M, C, _p(scale), _p(shift), int(relu), _p(y), _stream())
-    _check(rc, "wsplumb_rowbn_apply")
+    _call("wsplumb_rowbn_apply", x.device, _p(x), M, C, _p(scale), _p(shift), int(relu), _p(y))
     return y
 
 
-def _backward_outputs(L, x):
-    """dx, dwb [2, C] = (dweight, dbias), the coefficient scratch and the workspace (tensor, bytes) of a backward call"""
-    M, C = x.shape
-    dwb = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    coef = torch.empty((3, C), dtype=torch.float32, device=x.device)
-    return torch.empty_like(x), dwb, coef, _workspace(L, M, C, x.device)
+def _backward_outputs(x):
+    """dx, dwb [2, C] = (dweight, dbias) and the coefficient scratch of a backward call"""
+    dwb = torch.empty((2, x.shape[1]), dtype=torch.float32, device=x.device)
+    coef = torch.empty((3, x.shape[1]), dtype=torch.float32, device=x.device)
+    return torch.empty_like(x), dwb, coef
 
 
 def rowbn_backward(x, dy, weight, stats, relu, mask=None, pos_major=False):
-    L = lib()
     M, C = x.shape
-    n_rois = mask.shape[0] if mask is not None else 0
-    with torch.cuda.device(x.device):
-        dx, dwb, coef, (ws, n) = _backward_outputs(L, x)
-        _check(L.wsplumb_rowbn_backward(_p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]), _p(stats[3]),
-                                        _p(stats[4]), int(relu), _pn(mask), n_rois, M // n_rois if n_rois else 1,
-                                        int(bool(pos_major) and n_rois > 0), _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef),
-                                        _p(ws), n, _stream()), "wsplumb_rowbn_backward")
+    dx, dwb, coef = _backward_outputs(x)
+    ws = _workspace(x)
+    _call("wsplumb_rowbn_backward", x.device, _p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]),
+          _p(stats[3]), _p(stats[4]), int(relu), *_mask_args(mask, M), int(bool(pos_major) and mask is not None),
+          _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), ws.numel())
     return dx, dwb[0], dwb[1]
 
 
 def entry_usable(x):
     """True when block 1's pre-activation norm may take its output's gradient in two parts (rowbn_backward_entry)
     for this roi-major [M, C] tensor."""
-    if os.environ.get("WSSDL_HEAD_UNFUSED_ENTRY"):         # A/B switch: torch's scatter and add, then the plain backward
-        return False
-    return usable(x) and x.shape[0] < 2 ** 31
+    return not switch("WSSDL_HEAD_UNFUSED_ENTRY") and usable(x) and x.shape[0] < 2 ** 31
 
 
 def rowbn_backward_entry(x, dy, dys, possel, n_slots, weight, stats, mask=None):
     """rowbn_backward(relu=True) of roi-major rows x [R * per, C] whose output gradient is dy [R * per, C] plus, at the
     positions p with possel[p] = slot >= 0 (int32 [per] on the device), the position-major dys [n_slots * R, C]:
     bit-identical to the plain backward on dy + scatter(dys), without forming that sum in memory."""
-    L = lib()
     M, C = x.shape
-    dev = x.device
     per = possel.shape[0]
     n_rois = M // per
     assert M == n_rois * per and dy.shape == x.shape and dys.shape == (n_slots * n_rois, C)
     assert dy.is_contiguous() and dys.is_contiguous() and possel.dtype == torch.int32 and possel.is_contiguous()
-    assert mask is None or (mask.shape[0] == n_rois and mask.dtype == torch.float32 and mask.is_contiguous())
-    with torch.cuda.device(dev):
-        dx, dwb, coef, (ws, n) = _backward_outputs(L, x)
-        _check(L.wsplumb_rowbn_backward_entry(_p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight), _p(stats[0]),
-                                              _p(stats[2]), _p(stats[3]), _p(stats[4]), _pn(mask), n_rois, per, _p(dx),
-                                              _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), n, _stream()),
-               "wsplumb_rowbn_backward_entry")
+    assert mask is None or mask.shape[0] == n_rois
+    dx, dwb, coef = _backward_outputs(x)
+    ws = _workspace(x)
+    _call("wsplumb_rowbn_backward_entry", x.device, _p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight),
+          _p(stats[0]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _mask_args(mask, M)[0], n_rois, per, _p(dx),
+          _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), ws.numel())
     return dx, dwb[0], dwb[1]
 
 
 def join_usable(x):
     """True when the residual-join kernels may take this position-major [M, C] tensor."""
-    if os.environ.get("WSSDL_HEAD_UNFUSED_JOIN"):          # A/B switch: separate norms and a torch add
-        return False
-    return usable(x)
+    return not switch("WSSDL_HEAD_UNFUSED_JOIN") and usable(x)
 
 
 def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
@@ -218,34 +237,24 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
     position-major rows, each bn a (weight, bias, eps) triple, mask as in rowbn_forward(pos_major=True).
     Returns (out, y, stats3, stats_s, stats_n, count or None), stats_s unwritten without bns; bit-identical to the
     separate calls.  running: None, or the running_of() of bn3, bns (None without it) and bnn."""
-    L = lib()
     M, C = x3.shape
     dev = x3.device
     assert other.shape == x3.shape and other.is_contiguous() and other.dtype == torch.float32
     out, y = torch.empty_like(x3), torch.empty_like(x3)
     stats = torch.empty((3, 5, C), dtype=torch.float32, device=dev)
-    count, n_rois = None, 0
-    if mask is not None:
-        n_rois = mask.shape[0]
-        assert M % n_rois == 0 and mask.dtype == torch.float32 and mask.is_contiguous()
-        count = torch.empty((1,), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.float32, device=dev) if mask is not None else None
     ws_, bs_, es_ = bns if bns is not None else (None, None, 0.0)
-    run_ptrs = run_mom = run_nbt = None
+    run = (None, None, None)
     if running is not None:
         a = [_run_args(r) for r in running]
         val = lambda q: q.value if q is not None else None
-        run_ptrs = (_vp * 6)(*[val(q) for r in a for q in r[:2]])
-        run_mom = (_f * 3)(*[r[2] for r in a])
-        run_nbt = (_vp * 3)(*[val(r[3]) for r in a])
-    with torch.cuda.device(dev):
-        n = L.wsplumb_rowbn_join_workspace_bytes(M, C)
-        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-        rc = L.wsplumb_rowbn_join_forward(_p(x3), _p(other), M, C, _p(bn3[0]), _p(bn3[1]), float(bn3[2]), _pn(ws_),
-                                          _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]), _pn(mask), n_rois,
-                                          M // n_rois if n_rois else 1, _p(out), _p(y), _p(stats[0]),
-                                          _p(stats[1]) if bns is not None else None, _p(stats[2]), _pn(count), _p(ws), n,
-                                          _stream(), run_ptrs, run_mom, run_nbt)
-    _check(rc, "wsplumb_rowbn_join_forward")
+        run = ((_vp * 6)(*[val(q) for r in a for q in r[:2]]), (_f * 3)(*[r[2] for r in a]),
+               (_vp * 3)(*[val(r[3]) for r in a]))
+    ws = _workspace(x3, join=True)
+    _call("wsplumb_rowbn_join_forward", dev, _p(x3), _p(other), M, C, _p(bn3[0]), _p(bn3[1]), float(bn3[2]), _pn(ws_),
+          _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]), *_mask_args(mask, M), _p(out), _p(y),
+          _p(stats[0]), _p(stats[1]) if bns is not None else None, _p(stats[2]), _pn(count), _p(ws), ws.numel(),
+          tail=run)
     return out, y, stats[0], stats[1], stats[2], count
 
 
@@ -253,32 +262,23 @@ def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, sta
     """Gradients of rowbn_join_forward: dy for y, dres (or None) for out; xs / ws_ / stats_s None in the identity
     form.  Returns (g, dx3, dxs or None, dwb_n, dwb3, dwb_s or None), the dwb [2, C] = (dweight, dbias); g is the
     gradient of `other` in the identity form."""
-    L = lib()
     M, C = x3.shape
-    dev = x3.device
     dual = xs is not None
     g, dx3 = torch.empty_like(x3), torch.empty_like(x3)
     dxs = torch.empty_like(x3) if dual else None
-    dwb = torch.empty((3, 2, C), dtype=torch.float32, device=dev)
-    coef = torch.empty((9, C), dtype=torch.float32, device=dev)
-    n_rois = mask.shape[0] if mask is not None else 0
-    with torch.cuda.device(dev):
-        n = L.wsplumb_rowbn_join_workspace_bytes(M, C)
-        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-        rc = L.wsplumb_rowbn_join_backward(_p(out), _p(dy), _pn(dres), _p(x3), _pn(xs), M, C, _p(wn), _p(stats_n), _p(w3),
-                                           _p(stats3), _pn(ws_), _pn(stats_s), _pn(mask), n_rois,
-                                           M // n_rois if n_rois else 1, _p(g), _p(dx3), _pn(dxs), _p(dwb[0]), _p(dwb[1]),
-                                           _p(dwb[2]) if dual else None, _p(coef), _p(ws), n, _stream())
-    _check(rc, "wsplumb_rowbn_join_backward")
+    dwb = torch.empty((3, 2, C), dtype=torch.float32, device=x3.device)
+    coef = torch.empty((9, C), dtype=torch.float32, device=x3.device)
+    ws = _workspace(x3, join=True)
+    _call("wsplumb_rowbn_join_backward", x3.device, _p(out), _p(dy), _pn(dres), _p(x3), _pn(xs), M, C, _p(wn),
+          _p(stats_n), _p(w3), _p(stats3), _pn(ws_), _pn(stats_s), *_mask_args(mask, M), _p(g), _p(dx3), _pn(dxs),
+          _p(dwb[0]), _p(dwb[1]), _p(dwb[2]) if dual else None, _p(coef), _p(ws), ws.numel())
     return g, dx3, dxs, dwb[0], dwb[1], dwb[2] if dual else None
 
 
 def im2col_usable(x):
     """True when the 3x3 patch kernels can take this [R, h, w, C] tensor."""
-    if os.environ.get("WSSDL_DISABLE_FUSED_IM2COL"):       # A/B switch for measurements
-        return False
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
-            and x.shape[3] % 4 == 0 and x.shape[0] > 0 and lib() is not None)
+    return (not switch("WSSDL_DISABLE_FUSED_IM2COL") and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous() and x.shape[3] % 4 == 0 and x.shape[0] > 0 and lib() is not None)
 
 
 class Im2Col3x3Fn(torch.autograd.Function):
@@ -286,26 +286,18 @@ class Im2Col3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, stride, oh, ow, pt, pl):
-        L = lib()
         r, h, w, c = x.shape
         cols = torch.empty((r * oh * ow, 9 * c), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = L.wsplumb_im2col3x3(_p(x), r, h, w, c, oh, ow, stride, pt, pl, _p(cols), _stream())
-        if rc:
-            raise RuntimeError("wsplumb_im2col3x3 failed (%d)" % rc)
+        _call("wsplumb_im2col3x3", x.device, _p(x), r, h, w, c, oh, ow, stride, pt, pl, _p(cols))
         ctx.geom = (r, h, w, c, oh, ow, stride, pt, pl)
         return cols
 
     @staticmethod
     def backward(ctx, dcols):
-        L = lib()
-        r, h, w, c, oh, ow, stride, pt, pl = ctx.geom
+        r, h, w, c = ctx.geom[:4]
         dcols = dcols.contiguous()
         dx = torch.empty((r, h, w, c), dtype=torch.float32, device=dcols.device)
-        with torch.cuda.device(dcols.device):
-            rc = L.wsplumb_col2im3x3(_p(dcols), r, h, w, c, oh, ow, stride, pt, pl, _p(dx), _stream())
-        if rc:
-            raise RuntimeError("wsplumb_col2im3x3 failed (%d)" % rc)
+        _call("wsplumb_col2im3x3", dcols.device, _p(dcols), *ctx.geom, _p(dx))
         return dx, None, None, None, None, None
 
 
@@ -335,7 +327,6 @@ class TapPlan:
     """
 
     def __init__(self, h, w, s):
-        from .backbones import _same_pad
         self.h, self.w, self.s = h, w, s
         self.pt, self.pl = _same_pad(h, 3, s)[0], _same_pad(w, 3, s)[0]
         self.oh, self.ow = -(-h // s), -(-w // s)
@@ -435,21 +426,14 @@ def tap_plan(h, w, s):
 
 def taps_usable(x):
     """True when the head may run its 3x3 convolutions on the class-packed route (x: [R, h, w, C])."""
-    if os.environ.get("WSSDL_HEAD_DENSE_3X3"):            # A/B switch: the dense patch route
-        return False
-    return im2col_usable(x) and x.shape[0] >= TAPS_MIN_ROIS
-
-
-def _tap_call(name, *args):
-    _check(getattr(lib(), name)(*args, _stream()), name)
+    return not switch("WSSDL_HEAD_DENSE_3X3") and im2col_usable(x) and x.shape[0] >= TAPS_MIN_ROIS
 
 
 def tap_gather(x, plan, in_pm, R):
     """class-packed patches (plan.units * R * C floats) of x: roi-major [R, h, w, C] or position-major."""
     C = x.shape[-1]
     cols = torch.empty((plan.units * R * C,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _tap_call("wsplumb_tap_gather", _p(x), R, C, _p(plan.device_table(x.device)), plan.hnum, int(in_pm), _p(cols))
+    _call("wsplumb_tap_gather", x.device, _p(x), R, C, _p(plan.device_table(x.device)), plan.hnum, int(in_pm), _p(cols))
     return cols
 
 
@@ -457,9 +441,8 @@ def tap_col2im(dcols, plan, in_pm, R, C):
     """adjoint of tap_gather: dx roi-major [R, h, w, C], or position-major [h*w*R, C] with in_pm."""
     shape = (plan.h * plan.w * R, C) if in_pm else (R, plan.h, plan.w, C)
     dx = torch.empty(shape, dtype=torch.float32, device=dcols.device)
-    with torch.cuda.device(dcols.device):
-        _tap_call("wsplumb_tap_col2im", _p(dcols), R, C, _p(plan.device_table(dcols.device)), plan.hnum, int(in_pm),
-                  _p(dx))
+    _call("wsplumb_tap_col2im", dcols.device, _p(dcols), R, C, _p(plan.device_table(dcols.device)), plan.hnum,
+          int(in_pm), _p(dx))
     return dx
 
 
@@ -467,17 +450,16 @@ def tap_weight_gather(weight, plan):
     """[c_o, 9*C] -> class-packed (plan.wunits * c_o * C floats): class k is [c_o, ntaps_k * C]."""
     CO, C = weight.shape[0], weight.shape[1] // 9
     wp = torch.empty((plan.wunits * CO * C,), dtype=torch.float32, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _tap_call("wsplumb_tap_weight_gather", _p(weight), CO, C, _p(plan.device_table(weight.device)), plan.hnum,
-                  _p(wp))
+    _call("wsplumb_tap_weight_gather", weight.device, _p(weight), CO, C, _p(plan.device_table(weight.device)),
+          plan.hnum, _p(wp))
     return wp
 
 
 def tap_weight_scatter(dwp, plan, CO, C):
     """adjoint of tap_weight_gather: [c_o, 9*C], each column the class contributions summed in class order."""
     dw = torch.empty((CO, 9 * C), dtype=torch.float32, device=dwp.device)
-    with torch.cuda.device(dwp.device):
-        _tap_call("wsplumb_tap_weight_scatter", _p(dwp), CO, C, _p(plan.device_table(dwp.device)), plan.hnum, _p(dw))
+    _call("wsplumb_tap_weight_scatter", dwp.device, _p(dwp), CO, C, _p(plan.device_table(dwp.device)), plan.hnum,
+          _p(dw))
     return dw
 
 

@@ -4,14 +4,15 @@ the detection hot path lives in the HIP library).
 Reference: code/lib/networks/network.py:100-172 (conv / conv_int), :417-545 (ResNet blocks,
 layer_group, normalization), Resnet_train_bus.py:55-63,91-101, VGGnet_train_bus.py:43-101.
 Tensors are NCHW-shaped in channels_last memory format, so ``x.permute(0, 2, 3, 1)`` is the
-contiguous NHWC view the hot-path ops take, with no copy.
+contiguous NHWC view the hot-path ops take, with no copy.  The block wiring (_preact, _init_block,
+_walk) also serves the per-RoI head's NHWC blocks (roi_head.py); the norms run on rownorm.py.
 """
-import math
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _plumbing, rownorm
+from ._plumbing import _same_pad
 
 
 class BatchNormAct2d(nn.BatchNorm2d):
@@ -21,38 +22,20 @@ class BatchNormAct2d(nn.BatchNorm2d):
     anywhere else it is the stock module followed by F.relu."""
 
     def forward(self, x, relu=False):
-        if self.training and x.dim() == 4 and x.is_cuda and self.track_running_stats:
-            rows = x.permute(0, 2, 3, 1)
-            if rows.is_contiguous():
-                from . import _plumbing
-                from .roi_head import _FusedRowBatchNormFn
-                n, h, w, c = rows.shape
-                r2 = rows.reshape(-1, c)
-                if _plumbing.usable(r2):
-                    # the forward kernels update the running statistics themselves (run is not None)
-                    run = _plumbing.running_of(self)
-                    y, mean, var, _ = _FusedRowBatchNormFn.apply(r2, self.weight, self.bias, self.eps, bool(relu),
-                                                                 None, False, run)
-                    if run is None:
-                        self._track(mean, var, r2.shape[0])
-                    return y.view(n, h, w, c).permute(0, 3, 1, 2)
+        if self.training and x.is_cuda and self.track_running_stats:
+            r2 = _rows(x)
+            if r2 is not None and _plumbing.usable(r2):
+                run, done = rownorm.running((self,), None, r2.shape[0])
+                y, mean, var, n = rownorm._FusedRowBatchNormFn.apply(r2, self.weight, self.bias, self.eps, bool(relu),
+                                                                     None, False, run)
+                done(((mean, var),), n)
+                return _nchw(y, x)
         y = super().forward(x)
         return F.relu(y) if relu else y
 
-    def _track(self, mean, var, m):
-        """running statistics from one batch's mean / biased variance over m rows, with torch ops."""
-        with torch.no_grad():
-            mom = self.momentum if self.momentum is not None else 0.1
-            self.running_mean.lerp_(mean, mom)
-            self.running_var.lerp_(var * (m / max(m - 1, 1)), mom)
-            self.num_batches_tracked += 1
 
-
-def _same_pad(size, k, s):
-    """TF 'SAME' padding along one axis: (before, after)."""
-    out = -(-size // s)
-    total = max((out - 1) * s + k - size, 0)
-    return total // 2, total - total // 2
+def _bn(c):
+    return BatchNormAct2d(c, eps=1e-3, momentum=0.01)
 
 
 class Conv(nn.Module):
@@ -66,7 +49,7 @@ class Conv(nn.Module):
         nn.init.trunc_normal_(self.conv.weight, std=0.01, a=-0.02, b=0.02)     # :110
         if self.conv.bias is not None:
             nn.init.zeros_(self.conv.bias)
-        self.bn = BatchNormAct2d(c_o, eps=1e-3, momentum=0.01) if norm == "BN" else None
+        self.bn = _bn(c_o) if norm == "BN" else None
 
     def forward(self, x, act=True):
         """act=False: the convolution's raw output (its norm is applied by the block's join, _join)."""
@@ -91,99 +74,92 @@ def _rows(x):
     return r.reshape(-1, r.shape[3]) if r.is_contiguous() else None
 
 
+def _nchw(rows, like):
+    """_rows back: the NCHW-shaped channels_last view of the row matrix of a tensor shaped like `like`."""
+    n, c, h, w = like.shape
+    return rows.view(n, h, w, c).permute(0, 3, 1, 2)
+
+
 def _join(last, x, short, ori, nxt):
     """The end of a trunk block: last(x) + shortcut, `last` the block's final Conv (norm, no ReLU), the shortcut
     `ori` itself or short(ori); then, when `nxt` is given, relu(nxt(out)) with the norm that follows the block.
-    Returns (out, relu(nxt(out))) from the residual-join kernels of csrc/plumbing/rowbn.hip (roi_head._JoinFn on
-    the [N*H*W, C] row views, no mask) when every norm involved is a training-mode BatchNormAct2d with running
-    statistics on a CUDA f32 channels_last tensor the kernels take and autograd is recording; else (out, None)
-    from the separate layers (also with WSSDL_TRUNK_UNFUSED_JOIN=1)."""
+    Returns (out, relu(nxt(out))) from the residual-join kernels (rownorm.join_rows on the [N*H*W, C] row views, no
+    mask) under rownorm.join_norms' conditions when, besides, every norm is a BatchNormAct2d with running statistics,
+    both sides are CUDA f32 channels_last tensors of one shape that the kernels take, and autograd is recording; else
+    (out, None) from the separate layers (also with WSSDL_TRUNK_UNFUSED_JOIN=1)."""
     x3 = last(x, act=False)
     xs = short(ori, act=False) if short is not None else ori
-    bns = [last.bn, nxt] + ([short.bn] if short is not None else [])
-    if (nxt is not None and not last.relu and torch.is_grad_enabled()
-            and not os.environ.get("WSSDL_TRUNK_UNFUSED_JOIN")
-            and all(isinstance(b, BatchNormAct2d) and b.training and b.track_running_stats for b in bns)
+    bns = rownorm.join_norms(last, short, nxt)
+    if (bns is not None and torch.is_grad_enabled() and not _plumbing.switch("WSSDL_TRUNK_UNFUSED_JOIN")
+            and all(isinstance(b, BatchNormAct2d) and b.track_running_stats for b in bns if b is not None)
             and xs.shape == x3.shape):
         r3, rs = _rows(x3), _rows(xs)
-        from . import _plumbing
         if r3 is not None and rs is not None and _plumbing.usable(r3) and _plumbing.usable(rs):
-            from .roi_head import _JoinFn
-            b3, bs = last.bn, short.bn if short is not None else None
-            run = None
-            if _plumbing.fused_running_stats():
-                run = (_plumbing.running_of(b3), _plumbing.running_of(bs) if bs is not None else None,
-                       _plumbing.running_of(nxt))
-            out, y, st3, sts, stn, _ = _JoinFn.apply(
-                r3, rs, b3.weight, b3.bias, bs.weight if bs is not None else None,
-                bs.bias if bs is not None else None, nxt.weight, nxt.bias, b3.eps, bs.eps if bs is not None else 0.0,
-                nxt.eps, None, run)
-            if run is None:
-                m = r3.shape[0]
-                b3._track(st3[0], st3[1], m)
-                if bs is not None:
-                    bs._track(sts[0], sts[1], m)
-                nxt._track(stn[0], stn[1], m)
-            n, c, h, w = x3.shape
-            return out.view(n, h, w, c).permute(0, 3, 1, 2), y.view(n, h, w, c).permute(0, 3, 1, 2)
+            out, y = rownorm.join_rows(*bns, r3, rs, None)
+            return _nchw(out, x3), _nchw(y, x3)
     return last._act(x3) + (short._act(xs) if short is not None else xs), None
 
 
-def _pre_act(blk, x, pre):
-    """A block's pre-activation: given by the previous block's join (pre), or computed here."""
-    if pre is not None:
-        return pre
-    return blk.pre_bn(x, relu=True) if blk.pre_bn is not None else F.relu(x)
+def _norm_relu(bn, x):
+    """relu(bn(x)), bn a BatchNormAct2d or None."""
+    return bn(x, relu=True) if bn is not None else F.relu(x)
 
 
-class Bottleneck(nn.Module):
-    """network.py:475-491: 1x1 -> 3x3 (stride here) -> 1x1(x4), pre-activation variants."""
-    expansion = 4
+def _preact(blk, x, pre, norm_relu):
+    """What a block's residual branch and its shortcut take (network.py:424-457), as (branch input, shortcut input).
+    'no_preact': both the block's input x.  Otherwise the branch takes y = relu(pre_bn(x)) -- `pre` when the previous
+    block's join computed it, else norm_relu(blk.pre_bn, x) -- and the shortcut y too ('both_preact') or the raw x
+    ('default')."""
+    if blk.preact == "no_preact":
+        return x, x
+    y = pre if pre is not None else norm_relu(blk.pre_bn, x)
+    return y, (y if blk.preact == "both_preact" else x)
+
+
+def _init_block(blk, conv, bn, c_i, c_o, s, preact, norm):
+    """The layers of a residual block of either layout (`conv`, `bn`: its convolution and norm classes) from
+    blk.chain, the (kernel, carries the stride) pairs of conv1, conv2, ...: pre_bn (None without pre-activation norm),
+    the chain c_i -> c_o -> ... -> c_o * expansion with no ReLU on its last member, and the projection shortcut
+    `short` (None when the channel counts agree)."""
+    blk.preact, blk.stride = preact, s
+    blk.pre_bn = bn(c_i) if (preact != "no_preact" and norm == "BN") else None
+    c_out, c = c_o * blk.expansion, c_i
+    for i, (k, strided) in enumerate(blk.chain, 1):
+        last = i == len(blk.chain)
+        setattr(blk, "conv%d" % i, conv(c, c_out if last else c_o, k, s if strided else 1, norm, relu=not last))
+        c = c_o
+    blk.short = conv(c_i, c_out, 1, s, norm, relu=False) if c_i != c_out else None
+
+
+def _convs(blk):
+    return [getattr(blk, "conv%d" % i) for i in range(1, len(blk.chain) + 1)]
+
+
+class _Block(nn.Module):
+    """A trunk-layout residual block (NCHW-shaped channels_last tensors); the subclasses name their chain."""
 
     def __init__(self, c_i, c_o, s, preact, norm):
         super().__init__()
-        self.preact = preact
-        if preact != "no_preact":
-            self.pre_bn = BatchNormAct2d(c_i, eps=1e-3, momentum=0.01) if norm == "BN" else None
-        self.conv1 = Conv(c_i, c_o, 1, 1, norm)
-        self.conv2 = Conv(c_o, c_o, 3, s, norm)
-        self.conv3 = Conv(c_o, c_o * 4, 1, 1, norm, relu=False)
-        self.short = Conv(c_i, c_o * 4, 1, s, norm, relu=False) if c_i != c_o * 4 else None
+        _init_block(self, Conv, _bn, c_i, c_o, s, preact, norm)
 
     def forward(self, x, pre=None, nxt=None):
         """pre: this block's pre-activation when the previous block's join computed it; nxt: the norm (+ReLU)
         that follows this block.  Returns (the block's output, nxt's output or None): _join."""
-        ori = x
-        if self.preact != "no_preact":
-            y = _pre_act(self, x, pre)
-            if self.preact == "both_preact":
-                ori = y
-            x = y
-        return _join(self.conv3, self.conv2(self.conv1(x)), self.short, ori, nxt)
+        x, ori = _preact(self, x, pre, _norm_relu)
+        *body, last = _convs(self)
+        for conv in body:
+            x = conv(x)
+        return _join(last, x, self.short, ori, nxt)
 
 
-class BasicBlock(nn.Module):
+class Bottleneck(_Block):
+    """network.py:475-491: 1x1 -> 3x3 (stride here) -> 1x1(x4), pre-activation variants."""
+    expansion, chain = 4, ((1, False), (3, True), (1, False))
+
+
+class BasicBlock(_Block):
     """network.py:457-473: 3x3 (stride here) -> 3x3."""
-    expansion = 1
-
-    def __init__(self, c_i, c_o, s, preact, norm):
-        super().__init__()
-        self.preact = preact
-        if preact != "no_preact":
-            self.pre_bn = BatchNormAct2d(c_i, eps=1e-3, momentum=0.01) if norm == "BN" else None
-        self.conv1 = Conv(c_i, c_o, 3, s, norm)
-        self.conv2 = Conv(c_o, c_o, 3, 1, norm, relu=False)
-        self.short = Conv(c_i, c_o, 1, s, norm, relu=False) if c_i != c_o else None
-
-    def forward(self, x, pre=None, nxt=None):
-        """Bottleneck.forward for the basic block."""
-        ori = x
-        if self.preact != "no_preact":
-            y = _pre_act(self, x, pre)
-            if self.preact == "both_preact":
-                ori = y
-            x = y
-        return _join(self.conv2, self.conv1(x), self.short, ori, nxt)
+    expansion, chain = 1, ((3, True), (3, False))
 
 
 def layer_group(block, c_i, c_o, count, s, norm, first=False):
@@ -194,19 +170,17 @@ def layer_group(block, c_i, c_o, count, s, norm, first=False):
     return nn.Sequential(*blocks)
 
 
-def _walk(blocks, x, final, join=True):
-    """The blocks in order, each told (with `join`) the norm that follows it -- the next block's pre-activation
-    norm, or `final` after the last -- so that its join can apply it; returns final's output (with its ReLU)."""
+def _walk(blocks, x, final, norm_relu, step=nn.Module.__call__, join=True):
+    """The blocks in order through step(blk, x, pre, nxt) -> (x, pre), by default the block's forward, each told (with `join`) the norm that follows it
+    -- the next block's pre-activation norm, or `final` after the last -- so that its join can apply it, and handed
+    the pre-activation the previous join computed; returns relu(final(x)), from the last join or norm_relu."""
     pre = None
     for i, blk in enumerate(blocks):
         nxt = None
         if join:
-            nxt = final if i + 1 == len(blocks) else \
-                (getattr(blocks[i + 1], "pre_bn", None) if blocks[i + 1].preact != "no_preact" else None)
-        x, pre = blk(x, pre, nxt)
-    if pre is None:
-        pre = final(x, relu=True) if final is not None else F.relu(x)
-    return pre
+            nxt = final if i + 1 == len(blocks) else blocks[i + 1].pre_bn
+        x, pre = step(blk, x, pre, nxt)
+    return pre if pre is not None else norm_relu(final, x)
 
 
 RESNET_DEFS = {18: ([2, 2, 2, 2], BasicBlock), 34: ([3, 4, 6, 3], BasicBlock),
@@ -224,13 +198,13 @@ class ResNetTrunk(nn.Module):
         self.group0 = layer_group(block, 64, 64, defs[0], 1, norm, first=True)
         self.group1 = layer_group(block, 64 * e, 128, defs[1], 2, norm)
         self.group2 = layer_group(block, 128 * e, 256, defs[2], 2, norm)
-        self.norm = BatchNormAct2d(256 * e, eps=1e-3, momentum=0.01) if norm == "BN" else None
+        self.norm = _bn(256 * e) if norm == "BN" else None
         self.out_channels = 256 * e
 
     def forward(self, x):
         x = self.conv0(x)
         x = F.max_pool2d(x, 3, 2)                         # 'VALID'
-        return _walk(list(self.group0) + list(self.group1) + list(self.group2), x, self.norm)
+        return _walk(list(self.group0) + list(self.group1) + list(self.group2), x, self.norm, _norm_relu)
 
 
 class ResNetHead(nn.Module):
@@ -241,11 +215,11 @@ class ResNetHead(nn.Module):
         defs, block = RESNET_DEFS[depth]
         e = block.expansion
         self.group3 = layer_group(block, 256 * e, 512, defs[3], 2, norm)
-        self.norm = BatchNormAct2d(512 * e, eps=1e-3, momentum=0.01) if norm == "BN" else None
+        self.norm = _bn(512 * e) if norm == "BN" else None
         self.out_features = 512 * e
 
     def forward(self, x):
-        return _walk(list(self.group3), x, self.norm, join=False).mean(dim=(2, 3))
+        return _walk(list(self.group3), x, self.norm, _norm_relu, join=False).mean(dim=(2, 3))
 
 
 class VGGTrunk(nn.Module):

@@ -10,224 +10,17 @@ normalisation is batch-norm over rows.  GEMMs (rocBLAS/hipBLASLt) are shape-agno
 Plumbing, not the product: stock PyTorch ops, except that batch-norm (+ReLU) runs on the
 fused kernels of csrc/plumbing/rowbn.hip when that library is built (the activations are
 [R*h*w, C] with up to ~4e5 rows: separate elementwise passes over them were a third of the
-step).
+step).  The norm layers, their autograd Functions and the live-row mask live in rownorm.py, the
+block wiring shared with the trunk in backbones.py; both are re-exported here under their names.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _plumbing
-from .backbones import RESNET_DEFS, _same_pad
-
-
-class _RowBatchNormFn(torch.autograd.Function):
-    """Training-mode batch norm over the rows of [M, C] built from column reductions
-    (`var_mean`, `sum`) and fused elementwise ops (stock PyTorch; used on the CPU and when the
-    plumbing library is not built).  PyTorch's native channels-last batch-norm kernels take
-    12 ms forward+backward on a [136k, 2048] f32 tensor on MI355X; this form about 2.5 ms."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps):
-        var, mean = torch.var_mean(x, dim=0, unbiased=False)
-        rstd = torch.rsqrt(var + eps)
-        scale = rstd * weight
-        y = torch.addcmul(bias - mean * scale, x, scale)
-        ctx.save_for_backward(x, mean, rstd, weight)
-        ctx.mark_non_differentiable(mean, var)
-        return y, mean, var
-
-    @staticmethod
-    def backward(ctx, dy, _dmean, _dvar):
-        x, mean, rstd, weight = ctx.saved_tensors
-        m = x.shape[0]
-        sum_dy = dy.sum(0)
-        sum_dy_x = (dy * x).sum(0)
-        sum_dy_xhat = (sum_dy_x - mean * sum_dy) * rstd
-        # dx = w*rstd * (dy - mean(dy) - xhat * mean(dy*xhat)),  xhat = (x - mean) * rstd
-        a = weight * rstd
-        k1 = a * rstd * sum_dy_xhat / m                  # multiplies (x - mean)
-        k0 = a * sum_dy / m - k1 * mean                  # constant per column: a*mean(dy) - k1*mean
-        dx = torch.addcmul(-k0, dy, a)
-        dx.addcmul_(x, -k1)
-        return dx, sum_dy_xhat, sum_dy, None
-
-
-def _side_outputs(ctx, count, placeholder, *side):
-    """Shared end of the fused Functions' forwards: the statistics and the live-row count they return next to the
-    activations carry no gradient.  Without a mask the count is a placeholder view of `placeholder` (unused: no extra
-    launch).  Returns the count to hand out."""
-    if count is None:
-        count = placeholder[0, :1]
-    ctx.mark_non_differentiable(*side, count)
-    ctx.set_materialize_grads(False)                   # no zero-filled gradients for the side outputs
-    return count
-
-
-class _FusedRowBatchNormFn(torch.autograd.Function):
-    """The same layer (optionally with its ReLU) on the fused HIP kernels of
-    csrc/plumbing/rowbn.hip: 3 passes over the tensor forward, 5 backward, instead of 5 + 14
-    with separate elementwise ops; the ReLU mask is recomputed from x in the backward.  `running`
-    (_plumbing.running_of: the layer's buffers, not autograd inputs) are updated by the forward kernels."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps, relu, roi_mask=None, pos_major=False, running=None):
-        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask, pos_major, running=running)
-        ctx.save_for_backward(x, weight, stats, roi_mask)
-        ctx.relu, ctx.pos_major = relu, pos_major
-        mean, var = stats[0], stats[1]
-        return y, mean, var, _side_outputs(ctx, count, stats, mean, var)
-
-    @staticmethod
-    def backward(ctx, dy, _dmean, _dvar, _dcount):
-        x, weight, stats, roi_mask = ctx.saved_tensors
-        if dy is None:
-            dy = torch.zeros_like(x)
-        dx, dw, db = _plumbing.rowbn_backward(x, dy.contiguous(), weight, stats, ctx.relu, roi_mask, ctx.pos_major)
-        return dx, dw, db, None, None, None, None, None
-
-
-class _JoinFn(torch.autograd.Function):
-    """The end of a block on the position-major route in one Function: out = bn3(x3) + other, where other is the
-    identity shortcut or (with the shortcut norm's weight / bias) bn_s(xs), then y = relu(bn_n(out)) with the next
-    block's pre-activation norm or the head's final norm.  The join kernels of csrc/plumbing/rowbn.hip apply
-    bn3 (and bn_s), add and take bn_n's statistics in one pass over the tensors, and in the backward form
-    g = bn_n's dx + the residual gradient together with the sums bn3's (bn_s's) backward takes over it; results
-    are bit-identical to the separate layers and torch's adds.  Returns out, y, the three [5, C] statistic
-    blocks (stats_s is not written in the identity form) and the live-row count."""
-
-    @staticmethod
-    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask, running=None):
-        dual = ws is not None
-        out, y, st3, sts, stn, count = _plumbing.rowbn_join_forward(
-            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask, running=running)
-        ctx.dual = dual
-        ctx.save_for_backward(x3, other if dual else None, out, w3, ws, wn, st3, sts, stn, roi_mask)
-        return out, y, st3, sts, stn, _side_outputs(ctx, count, stn, st3, sts, stn)
-
-    @staticmethod
-    def backward(ctx, dres, dy, *_):
-        x3, xs, out, w3, ws, wn, st3, sts, stn, roi_mask = ctx.saved_tensors
-        if dy is None:
-            dy = torch.zeros_like(out)
-        g, dx3, dxs, dwbn, dwb3, dwbs = _plumbing.rowbn_join_backward(
-            out, dy.contiguous(), dres.contiguous() if dres is not None else None, x3, xs, wn, stn, w3, st3, ws, sts,
-            roi_mask)
-        if ctx.dual:
-            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None, None
-        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None, None
-
-
-class _EntryNormFn(torch.autograd.Function):
-    """Block 1's pre-activation norm + ReLU on the position-major route, with both consumers of its output y in
-    one Function: returns y (roi-major rows, for conv1) and the position-major rows of the positions the
-    projection shortcut samples (_pm_rows).  The backward takes the two gradients as they arrive and forms
-    their sum inside the norm's two backward passes (rowbn.hip, EntryGrad): no zero-fill, index_add, strided
-    add or contiguous copy of a [R, 49, C] tensor.  Bit-identical to the separate layers."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps, roi_mask, plan, s, hw, running=None):
-        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, True, roi_mask, False, running=running)
-        h, w = hw
-        r = x.shape[0] // (h * w)
-        ys = _pm_rows(y.view(r, h, w, -1), plan, s)
-        ctx.save_for_backward(x, weight, stats, roi_mask)
-        ctx.geom = (plan, s, h, w)
-        mean, var = stats[0], stats[1]
-        return y, ys, mean, var, _side_outputs(ctx, count, stats, mean, var)
-
-    @staticmethod
-    def backward(ctx, dy, dys, *_):
-        x, weight, stats, roi_mask = ctx.saved_tensors
-        plan, s, h, w = ctx.geom
-        if dy is None:
-            dy = torch.zeros_like(x)
-        if dys is None:
-            dys = x.new_zeros((len(plan.slots) * (x.shape[0] // (h * w)), x.shape[1]))
-        dx, dw, db = _plumbing.rowbn_backward_entry(x, dy.contiguous(), dys.contiguous(),
-                                                    plan.subsample_slots(h, w, s, x.device), len(plan.slots), weight,
-                                                    stats, roi_mask)
-        return dx, dw, db, None, None, None, None, None, None
-
-
-# The head can see RoI rows that are not live: the padding rows of the fixed-shape blob
-# (cfg.PADDED_ROIS) and those of a supervised image that ran short of candidates under the device
-# sampler (cfg.SAMPLING_RNG = 'device': the layer keeps its fixed S*128 rows, batch index -1).
-# The networks set this mask ([R] f32, 1 = live) around the head call; batch statistics are
-# taken over the live rows only and dead rows are zeroed after every normalisation, so that the
-# live rows come out as if the blob had been compacted.  On the GPU this is the masked form of the
-# fused kernels (csrc/plumbing/rowbn.hip: dead rows are not even read); elsewhere plain PyTorch ops.
-# No host sync either way.
-_ROI_MASK = None
-
-
-def set_roi_mask(mask):
-    global _ROI_MASK
-    _ROI_MASK = mask
-
-
-def _masked_row_batch_norm(x, weight, bias, eps, relu, roi_mask, pos_major=False):
-    M = x.shape[0]
-    per = M // roi_mask.shape[0]
-    m = (roi_mask.repeat(per) if pos_major else roi_mask.repeat_interleave(per)).unsqueeze(1)
-    n = (roi_mask.sum() * per).clamp_min(1.0)
-    mean = (x * m).sum(0) / n
-    d = (x - mean) * m
-    var = (d * d).sum(0) / n
-    y = d * (torch.rsqrt(var + eps) * weight) + bias
-    if relu:
-        y = F.relu(y)
-    return y * m, mean.detach(), var.detach(), n
-
-
-class RowBatchNorm(nn.Module):
-    """BatchNorm over rows ([M, C] input) with the usual running statistics; `relu=True`
-    applies the ReLU that follows it in the network inside the same kernels.  Rows are roi-major
-    (row r belongs to RoI r // (M / R)) or, with `pos_major=True`, position-major (RoI r % R): only
-    the live-row mask cares."""
-
-    def __init__(self, num_features, eps=1e-3, momentum=0.01):
-        super().__init__()
-        self.eps, self.momentum = eps, momentum
-        self.weight = nn.Parameter(torch.ones(num_features))
-        self.bias = nn.Parameter(torch.zeros(num_features))
-        self.register_buffer("running_mean", torch.zeros(num_features))
-        self.register_buffer("running_var", torch.ones(num_features))
-
-    def forward(self, x, relu=False, pos_major=False):
-        fused = _plumbing.usable(x)
-        if not self.training:
-            scale = self.weight * torch.rsqrt(self.running_var + self.eps)
-            shift = self.bias - self.running_mean * scale
-            if fused and not torch.is_grad_enabled():
-                return _plumbing.rowbn_apply(x, scale.contiguous(), shift.contiguous(), relu)
-            y = torch.addcmul(shift, x, scale)
-            return F.relu(y) if relu else y
-        # on the fused route the forward kernels update the running statistics themselves (run is not None)
-        run = _plumbing.running_of(self) if fused else None
-        mask = _ROI_MASK
-        if fused and (mask is None or x.shape[0] % mask.shape[0] == 0):
-            y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), mask,
-                                                         bool(pos_major) and mask is not None, run)
-            if run is not None:
-                return y
-            n = n[0] if mask is not None else x.shape[0]
-        elif mask is not None:
-            y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, mask, pos_major)
-        else:
-            y, mean, var = _RowBatchNormFn.apply(x, self.weight, self.bias, self.eps)
-            if relu:
-                y = F.relu(y)
-            n = x.shape[0]
-        self._track(mean, var, n)
-        return y
-
-    def _track(self, mean, var, n):
-        """running statistics from one batch's mean / biased variance over n rows (n: an int, or the live-row
-        count as a 0-d tensor)."""
-        with torch.no_grad():
-            unbias = n / (n - 1).clamp_min(1.0) if torch.is_tensor(n) else n / max(n - 1, 1)
-            self.running_mean.lerp_(mean, self.momentum)
-            self.running_var.lerp_(var * unbias, self.momentum)
+from . import _plumbing, rownorm
+from .backbones import RESNET_DEFS, _convs, _init_block, _preact, _same_pad, _walk, layer_group
+from .rownorm import (RowBatchNorm, _EntryNormFn, _FusedRowBatchNormFn, _JoinFn, _RowBatchNormFn,  # noqa: F401
+                      _pm_rows, set_roi_mask)
 
 
 class ConvNHWC(nn.Module):
@@ -245,19 +38,16 @@ class ConvNHWC(nn.Module):
     def forward(self, x):
         r, h, w, c = x.shape
         k, s = self.k, self.s
+        (pt, pb), (pl, pr) = _same_pad(h, k, s), _same_pad(w, k, s)
         if k == 1:
             if s > 1:
                 x = x[:, ::s, ::s, :]
             oh, ow = x.shape[1], x.shape[2]
             rows = x.reshape(-1, c)
         elif k == 3 and _plumbing.im2col_usable(x):
-            pt, pb = _same_pad(h, k, s)
-            pl, pr = _same_pad(w, k, s)
             oh, ow = -(-h // s), -(-w // s)
             rows = _plumbing.Im2Col3x3Fn.apply(x, s, oh, ow, pt, pl)
         else:
-            pt, pb = _same_pad(h, k, s)
-            pl, pr = _same_pad(w, k, s)
             xp = F.pad(x, (0, 0, pl, pr, pt, pb))
             p = xp.unfold(1, k, s).unfold(2, k, s)            # [R, oh, ow, C, kh, kw]
             oh, ow = p.shape[1], p.shape[2]
@@ -284,157 +74,90 @@ class ConvNHWC(nn.Module):
         return self._act(y, pos_major=True) if act else y
 
 
-def _pm_rows(x, plan, s):
-    """roi-major [R, h, w, C] -> position-major [slots * R, C]: the inputs x[:, y*s, x*s] of the slots."""
+def _norm_relu(bn, x):
+    """relu(bn(x)), bn a RowBatchNorm or None, x a roi-major [R, h, w, C] map or position-major rows."""
+    if bn is None:
+        return F.relu(x)
+    if x.dim() == 2:
+        return bn(x, relu=True, pos_major=True)
     r, h, w, c = x.shape
-    idx = plan.subsample_index(w, s, x.device)
-    return x.view(r, h * w, c).transpose(0, 1).index_select(0, idx).reshape(-1, c)
+    return bn(x.reshape(-1, c), relu=True).view(r, h, w, c)
 
 
-def _bn_rows(bn, x, relu=False):
-    r, h, w, c = x.shape
-    return bn(x.reshape(-1, c), relu=relu).view(r, h, w, c)
-
-
-class BottleneckNHWC(nn.Module):
-    expansion = 4
+class _BlockNHWC(nn.Module):
+    """A residual block of the head on NHWC tensors; the subclasses name their chain."""
 
     def __init__(self, c_i, c_o, s, preact, norm):
         super().__init__()
-        self.preact = preact
-        self.pre_bn = RowBatchNorm(c_i) if (preact != "no_preact" and norm == "BN") else None
-        self.conv1 = ConvNHWC(c_i, c_o, 1, 1, norm)
-        self.conv2 = ConvNHWC(c_o, c_o, 3, s, norm)
-        self.conv3 = ConvNHWC(c_o, c_o * 4, 1, 1, norm, relu=False)
-        self.short = ConvNHWC(c_i, c_o * 4, 1, s, norm, relu=False) if c_i != c_o * 4 else None
+        _init_block(self, ConvNHWC, RowBatchNorm, c_i, c_o, s, preact, norm)
 
     def forward(self, x):
-        ori = x
-        if self.preact != "no_preact":
-            y = _bn_rows(self.pre_bn, x, relu=True) if self.pre_bn is not None else F.relu(x)
-            if self.preact == "both_preact":
-                ori = y
-            x = y
-        x = self.conv3(self.conv2(self.conv1(x)))
+        x, ori = _preact(self, x, None, _norm_relu)
+        for conv in _convs(self):
+            x = conv(x)
         return x + (self.short(ori) if self.short is not None else ori)
 
     def forward_pm(self, x, plans, R, pre=None, nxt=None):
         """forward on the position-major route: x roi-major [R, 7, 7, C] (first block) or position-major rows;
         plans: {stride: TapPlan}; pre: this block's pre-activation when the previous block's join computed it;
         nxt: the norm (+ReLU) that follows this block.  Returns (position-major rows, nxt's output or None)."""
-        pm = x.dim() == 2
-        ori = x
-        s = self.conv2.s
-        plan = plans[s]
+        s = self.stride
         if self._entry_fused(x, pre):
-            x, ori = _entry_pre_act(self.pre_bn, x, plan, s)   # ori: the shortcut's rows, already position-major
-        elif self.preact != "no_preact":
-            y = pre if pre is not None else _pre_act(self.pre_bn, x, pm)
-            if self.preact == "both_preact":
-                ori = y
-            x = y
-        if not pm:
-            x = self.conv1(x)                                   # 1x1 on the roi-major 7x7 map
+            x, ori = _entry_pre_act(self.pre_bn, x, plans[s], s)   # ori: the shortcut's rows, already position-major
         else:
-            x = self.conv1.forward_pm(x, plan, R)
-        x = self.conv3.forward_pm(self.conv2.forward_pm(x, plan, R), plan, R, act=False)
-        return _join_pm(self.conv3, x, self.short, ori, plan, s, R, nxt)
-
+            x, ori = _preact(self, x, pre, _norm_relu)
+        *body, last = _convs(self)
+        for conv in body:
+            # a 1x1 ahead of the strided convolution keeps a roi-major map roi-major (the bottleneck's conv1 on 7x7)
+            x = conv(x) if (conv.k == 1 and x.dim() == 4) else conv.forward_pm(x, plans[conv.s], R)
+        x = last.forward_pm(x, plans[last.s], R, act=False)
+        return _join_pm(last, x, self.short, ori, plans[s], s, R, nxt)
 
     def _entry_fused(self, x, pre):
         """True when this is block 1 of the position-major route in the form _EntryNormFn covers: a roi-major
-        input, a training-mode pre-activation norm whose output feeds both conv1 and a projection shortcut."""
-        bn, mask = self.pre_bn, _ROI_MASK
-        if x.dim() != 4 or pre is not None or self.preact != "both_preact" or self.short is None or bn is None:
+        input, a training-mode pre-activation norm whose output feeds both a 1x1 conv1 (the bottleneck's; the basic
+        block's 3x3 conv1 was never routed through it) and a projection shortcut."""
+        bn = self.pre_bn
+        if (x.dim() != 4 or pre is not None or self.preact != "both_preact" or self.short is None or bn is None
+                or self.conv1.k != 1):
             return False
         rows = x.reshape(-1, x.shape[3])
         return (bn.training and torch.is_grad_enabled() and _plumbing.entry_usable(rows)
-                and (mask is None or rows.shape[0] % mask.shape[0] == 0))
+                and rownorm.live_mask(rows.shape[0])[1])
 
 
-class BasicBlockNHWC(nn.Module):
-    expansion = 1
+class BottleneckNHWC(_BlockNHWC):
+    expansion, chain = 4, ((1, False), (3, True), (1, False))
 
-    def __init__(self, c_i, c_o, s, preact, norm):
-        super().__init__()
-        self.preact = preact
-        self.pre_bn = RowBatchNorm(c_i) if (preact != "no_preact" and norm == "BN") else None
-        self.conv1 = ConvNHWC(c_i, c_o, 3, s, norm)
-        self.conv2 = ConvNHWC(c_o, c_o, 3, 1, norm, relu=False)
-        self.short = ConvNHWC(c_i, c_o, 1, s, norm, relu=False) if c_i != c_o else None
 
-    def forward(self, x):
-        ori = x
-        if self.preact != "no_preact":
-            y = _bn_rows(self.pre_bn, x, relu=True) if self.pre_bn is not None else F.relu(x)
-            if self.preact == "both_preact":
-                ori = y
-            x = y
-        x = self.conv2(self.conv1(x))
-        return x + (self.short(ori) if self.short is not None else ori)
-
-    def forward_pm(self, x, plans, R, pre=None, nxt=None):
-        """BottleneckNHWC.forward_pm for the basic block."""
-        pm = x.dim() == 2
-        ori = x
-        if self.preact != "no_preact":
-            y = pre if pre is not None else _pre_act(self.pre_bn, x, pm)
-            if self.preact == "both_preact":
-                ori = y
-            x = y
-        s = self.conv1.s
-        plan = plans[s]
-        x = self.conv2.forward_pm(self.conv1.forward_pm(x, plan, R), plans[1], R, act=False)
-        return _join_pm(self.conv2, x, self.short, ori, plan, s, R, nxt)
+class BasicBlockNHWC(_BlockNHWC):
+    expansion, chain = 1, ((3, True), (3, False))
 
 
 def _join_pm(last, x3, short, ori, plan, s, R, nxt):
     """The end of a block (stride s) on the position-major route: act(x3) + shortcut, x3 the raw output of the
-    block's last convolution `last`.  Returns (out, relu(nxt(out))) from the join kernels (_JoinFn) when `nxt` is given and
-    every norm involved is a training-mode RowBatchNorm on a tensor the kernels take; else (out, None) from the
-    separate layers (also with WSSDL_HEAD_UNFUSED_JOIN=1)."""
+    block's last convolution `last`.  Returns (out, relu(nxt(out))) from the join kernels (rownorm.join_rows) under
+    rownorm.join_norms' conditions when, besides, the kernels take x3 and the live-row mask fits its rows -- with or
+    without autograd; else (out, None) from the separate layers (also with WSSDL_HEAD_UNFUSED_JOIN=1)."""
     if short is not None:
         xs = short.forward_pm(ori, plan, R, act=False)
     else:
         xs = ori if ori.dim() == 2 else _pm_rows(ori, plan, s)
-    bns = [last.bn, nxt] + ([short.bn] if short is not None else [])
-    mask = _ROI_MASK
-    if (nxt is None or any(b is None or not b.training for b in bns) or last.relu or not _plumbing.join_usable(x3)
-            or (mask is not None and x3.shape[0] % mask.shape[0] != 0)):
+    bns = rownorm.join_norms(last, short, nxt)
+    mask, fits = rownorm.live_mask(x3.shape[0])
+    if bns is None or not _plumbing.join_usable(x3) or not fits:
         return last._act(x3, pos_major=True) + (short._act(xs, pos_major=True) if short is not None else xs), None
-    b3, bs = last.bn, short.bn if short is not None else None
-    run = None
-    if _plumbing.fused_running_stats():
-        run = (_plumbing.running_of(b3), _plumbing.running_of(bs) if bs is not None else None, _plumbing.running_of(nxt))
-    out, y, st3, sts, stn, n = _JoinFn.apply(
-        x3, xs.contiguous(), b3.weight, b3.bias, bs.weight if bs is not None else None,
-        bs.bias if bs is not None else None, nxt.weight, nxt.bias, b3.eps, bs.eps if bs is not None else 0.0, nxt.eps,
-        mask, run)
-    if run is not None:                                 # the join's finish kernels updated the running statistics
-        return out, y
-    n = n[0] if mask is not None else x3.shape[0]
-    b3._track(st3[0], st3[1], n)
-    if bs is not None:
-        bs._track(sts[0], sts[1], n)
-    nxt._track(stn[0], stn[1], n)
-    return out, y
+    return rownorm.join_rows(*bns, x3, xs.contiguous(), mask)
 
 
 def _entry_pre_act(bn, x, plan, s):
     """Block 1's pre-activation through _EntryNormFn: (y roi-major [R, h, w, C], the shortcut's position-major rows)."""
     r, h, w, c = x.shape
-    run = _plumbing.running_of(bn)
-    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, _ROI_MASK, plan, s, (h, w),
-                                             run)
-    if run is None:
-        bn._track(mean, var, n[0] if _ROI_MASK is not None else r * h * w)
+    mask, _ = rownorm.live_mask(r * h * w)
+    run, done = rownorm.running((bn,), mask, r * h * w)
+    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, mask, plan, s, (h, w), run)
+    done(((mean, var),), n)
     return y.view(r, h, w, c), ys
-
-
-def _pre_act(bn, x, pm):
-    if not pm:
-        return _bn_rows(bn, x, relu=True) if bn is not None else F.relu(x)
-    return bn(x, relu=True, pos_major=True) if bn is not None else F.relu(x)
 
 
 class ResNetHeadNHWC(nn.Module):
@@ -445,10 +168,7 @@ class ResNetHeadNHWC(nn.Module):
         defs, block = RESNET_DEFS[depth]
         blk = BottleneckNHWC if block.expansion == 4 else BasicBlockNHWC
         e = blk.expansion
-        blocks = [blk(256 * e, 512, 2, "both_preact", norm)]
-        for _ in range(1, defs[3]):
-            blocks.append(blk(512 * e, 512, 1, "default", norm))
-        self.group3 = nn.Sequential(*blocks)
+        self.group3 = layer_group(blk, 256 * e, 512, defs[3], 2, norm)
         self.norm = RowBatchNorm(512 * e) if norm == "BN" else None
         self.out_features = 512 * e
 
@@ -456,9 +176,7 @@ class ResNetHeadNHWC(nn.Module):
         plans = self._tap_plans(x)
         if plans is not None:
             return self._forward_pm(x, plans)
-        x = self.group3(x)
-        x = _bn_rows(self.norm, x, relu=True) if self.norm is not None else F.relu(x)
-        return x.mean(dim=(1, 2))
+        return _norm_relu(self.norm, self.group3(x)).mean(dim=(1, 2))
 
     @staticmethod
     def _tap_plans(x):
@@ -479,12 +197,6 @@ class ResNetHeadNHWC(nn.Module):
         corners by _plumbing.TapPlan): each 3x3 class GEMM writes its own contiguous slab; batch norm,
         1x1 convolutions and residual adds do not care about row order, the final mean reduces over slots."""
         R = x.shape[0]
-        blocks, pre = list(self.group3), None
-        for i, blk in enumerate(blocks):
-            # the norm (+ReLU) after this block: the next block's pre-activation, or the final norm
-            nxt = self.norm if i + 1 == len(blocks) else \
-                (blocks[i + 1].pre_bn if blocks[i + 1].preact != "no_preact" else None)
-            x, pre = blk.forward_pm(x, plans, R, pre, nxt)
-        if pre is None:
-            pre = self.norm(x, relu=True, pos_major=True) if self.norm is not None else F.relu(x)
-        return pre.view(-1, R, pre.shape[1]).mean(dim=0)
+        y = _walk(list(self.group3), x, self.norm, _norm_relu,
+                  lambda blk, x, pre, nxt: blk.forward_pm(x, plans, R, pre, nxt))
+        return y.view(-1, R, y.shape[1]).mean(dim=0)

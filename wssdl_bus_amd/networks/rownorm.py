@@ -1,0 +1,277 @@
+"""Batch norm over the rows of an [M, C] matrix, the one form both networks normalise in: the trunk's [N, H, W, C]
+maps are [N*H*W, C] row views (backbones.BatchNormAct2d), the per-RoI head's activations are rows already
+(RowBatchNorm, roi-major or position-major).  Here live the autograd Functions over the kernels of
+csrc/plumbing/rowbn.hip (single norm, block-1 entry norm, residual join) with their stock-PyTorch stand-ins, the
+live-row mask of the head, the one running-statistics update (`track`, `running`) and the one residual join over row
+matrices (`join_norms`, `join_rows`).  Imports only _plumbing; backbones.py and roi_head.py import from here.
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _plumbing
+
+
+class _RowBatchNormFn(torch.autograd.Function):
+    """Training-mode batch norm over the rows of [M, C] built from column reductions
+    (`var_mean`, `sum`) and fused elementwise ops (stock PyTorch; used on the CPU and when the
+    plumbing library is not built).  PyTorch's native channels-last batch-norm kernels take
+    12 ms forward+backward on a [136k, 2048] f32 tensor on MI355X; this form about 2.5 ms."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        var, mean = torch.var_mean(x, dim=0, unbiased=False)
+        rstd = torch.rsqrt(var + eps)
+        scale = rstd * weight
+        y = torch.addcmul(bias - mean * scale, x, scale)
+        ctx.save_for_backward(x, mean, rstd, weight)
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, _dmean, _dvar):
+        x, mean, rstd, weight = ctx.saved_tensors
+        m = x.shape[0]
+        sum_dy = dy.sum(0)
+        sum_dy_x = (dy * x).sum(0)
+        sum_dy_xhat = (sum_dy_x - mean * sum_dy) * rstd
+        # dx = w*rstd * (dy - mean(dy) - xhat * mean(dy*xhat)),  xhat = (x - mean) * rstd
+        a = weight * rstd
+        k1 = a * rstd * sum_dy_xhat / m                  # multiplies (x - mean)
+        k0 = a * sum_dy / m - k1 * mean                  # constant per column: a*mean(dy) - k1*mean
+        dx = torch.addcmul(-k0, dy, a)
+        dx.addcmul_(x, -k1)
+        return dx, sum_dy_xhat, sum_dy, None
+
+
+def _side_outputs(ctx, count, placeholder, *side):
+    """Shared end of the fused Functions' forwards: the statistics and the live-row count they return next to the
+    activations carry no gradient.  Without a mask the count is a placeholder view of `placeholder` (unused: no extra
+    launch).  Returns the count to hand out."""
+    if count is None:
+        count = placeholder[0, :1]
+    ctx.mark_non_differentiable(*side, count)
+    ctx.set_materialize_grads(False)                   # no zero-filled gradients for the side outputs
+    return count
+
+
+def _grad(dy, like):
+    """An output's gradient as the kernels take it: contiguous, zeros when autograd has none for it."""
+    return dy.contiguous() if dy is not None else torch.zeros_like(like)
+
+
+class _FusedRowBatchNormFn(torch.autograd.Function):
+    """The same layer (optionally with its ReLU) on the fused HIP kernels of
+    csrc/plumbing/rowbn.hip: 3 passes over the tensor forward, 5 backward, instead of 5 + 14
+    with separate elementwise ops; the ReLU mask is recomputed from x in the backward.  `running`
+    (_plumbing.running_of: the layer's buffers, not autograd inputs) are updated by the forward kernels."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, relu, roi_mask=None, pos_major=False, running=None):
+        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, relu, roi_mask, pos_major, running=running)
+        ctx.save_for_backward(x, weight, stats, roi_mask)
+        ctx.relu, ctx.pos_major = relu, pos_major
+        mean, var = stats[0], stats[1]
+        return y, mean, var, _side_outputs(ctx, count, stats, mean, var)
+
+    @staticmethod
+    def backward(ctx, dy, _dmean, _dvar, _dcount):
+        x, weight, stats, roi_mask = ctx.saved_tensors
+        dx, dw, db = _plumbing.rowbn_backward(x, _grad(dy, x), weight, stats, ctx.relu, roi_mask, ctx.pos_major)
+        return dx, dw, db, None, None, None, None, None
+
+
+class _JoinFn(torch.autograd.Function):
+    """The end of a residual block in one Function: out = bn3(x3) + other, where other is the
+    identity shortcut or (with the shortcut norm's weight / bias) bn_s(xs), then y = relu(bn_n(out)) with the next
+    block's pre-activation norm or the network's final norm.  The join kernels of csrc/plumbing/rowbn.hip apply
+    bn3 (and bn_s), add and take bn_n's statistics in one pass over the tensors, and in the backward form
+    g = bn_n's dx + the residual gradient together with the sums bn3's (bn_s's) backward takes over it; results
+    are bit-identical to the separate layers and torch's adds.  Returns out, y, the three [5, C] statistic
+    blocks (stats_s is not written in the identity form) and the live-row count."""
+
+    @staticmethod
+    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask, running=None):
+        dual = ws is not None
+        out, y, st3, sts, stn, count = _plumbing.rowbn_join_forward(
+            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask, running=running)
+        ctx.dual = dual
+        ctx.save_for_backward(x3, other if dual else None, out, w3, ws, wn, st3, sts, stn, roi_mask)
+        return out, y, st3, sts, stn, _side_outputs(ctx, count, stn, st3, sts, stn)
+
+    @staticmethod
+    def backward(ctx, dres, dy, *_):
+        x3, xs, out, w3, ws, wn, st3, sts, stn, roi_mask = ctx.saved_tensors
+        g, dx3, dxs, dwbn, dwb3, dwbs = _plumbing.rowbn_join_backward(
+            out, _grad(dy, out), dres.contiguous() if dres is not None else None, x3, xs, wn, stn, w3, st3, ws, sts,
+            roi_mask)
+        if ctx.dual:
+            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None, None
+        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None, None
+
+
+def _pm_rows(x, plan, s):
+    """roi-major [R, h, w, C] -> position-major [slots * R, C]: the inputs x[:, y*s, x*s] of the slots."""
+    r, h, w, c = x.shape
+    idx = plan.subsample_index(w, s, x.device)
+    return x.view(r, h * w, c).transpose(0, 1).index_select(0, idx).reshape(-1, c)
+
+
+class _EntryNormFn(torch.autograd.Function):
+    """Block 1's pre-activation norm + ReLU on the position-major route, with both consumers of its output y in
+    one Function: returns y (roi-major rows, for conv1) and the position-major rows of the positions the
+    projection shortcut samples (_pm_rows).  The backward takes the two gradients as they arrive and forms
+    their sum inside the norm's two backward passes (rowbn.hip, EntryGrad): no zero-fill, index_add, strided
+    add or contiguous copy of a [R, 49, C] tensor.  Bit-identical to the separate layers."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, roi_mask, plan, s, hw, running=None):
+        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, True, roi_mask, False, running=running)
+        h, w = hw
+        r = x.shape[0] // (h * w)
+        ys = _pm_rows(y.view(r, h, w, -1), plan, s)
+        ctx.save_for_backward(x, weight, stats, roi_mask)
+        ctx.geom = (plan, s, h, w)
+        mean, var = stats[0], stats[1]
+        return y, ys, mean, var, _side_outputs(ctx, count, stats, mean, var)
+
+    @staticmethod
+    def backward(ctx, dy, dys, *_):
+        x, weight, stats, roi_mask = ctx.saved_tensors
+        plan, s, h, w = ctx.geom
+        if dys is None:
+            dys = x.new_zeros((len(plan.slots) * (x.shape[0] // (h * w)), x.shape[1]))
+        dx, dw, db = _plumbing.rowbn_backward_entry(x, _grad(dy, x), dys.contiguous(),
+                                                    plan.subsample_slots(h, w, s, x.device), len(plan.slots), weight,
+                                                    stats, roi_mask)
+        return dx, dw, db, None, None, None, None, None, None
+
+
+# The head can see RoI rows that are not live: the padding rows of the fixed-shape blob
+# (cfg.PADDED_ROIS) and those of a supervised image that ran short of candidates under the device
+# sampler (cfg.SAMPLING_RNG = 'device': the layer keeps its fixed S*128 rows, batch index -1).
+# The networks set this mask ([R] f32, 1 = live) around the head call; batch statistics are
+# taken over the live rows only and dead rows are zeroed after every normalisation, so that the
+# live rows come out as if the blob had been compacted.  On the GPU this is the masked form of the
+# fused kernels (csrc/plumbing/rowbn.hip: dead rows are not even read); elsewhere plain PyTorch ops.
+# No host sync either way.
+_ROI_MASK = None
+
+
+def set_roi_mask(mask):
+    global _ROI_MASK
+    _ROI_MASK = mask
+
+
+def live_mask(rows):
+    """(the live-row mask or None, whether a matrix of `rows` rows can take it: none set, or its RoI count divides
+    them)."""
+    return _ROI_MASK, _ROI_MASK is None or rows % _ROI_MASK.shape[0] == 0
+
+
+def _masked_row_batch_norm(x, weight, bias, eps, relu, roi_mask, pos_major=False):
+    M = x.shape[0]
+    per = M // roi_mask.shape[0]
+    m = (roi_mask.repeat(per) if pos_major else roi_mask.repeat_interleave(per)).unsqueeze(1)
+    n = (roi_mask.sum() * per).clamp_min(1.0)
+    mean = (x * m).sum(0) / n
+    d = (x - mean) * m
+    var = (d * d).sum(0) / n
+    y = d * (torch.rsqrt(var + eps) * weight) + bias
+    if relu:
+        y = F.relu(y)
+    return y * m, mean.detach(), var.detach(), n
+
+
+def track(bn, mean, var, n):
+    """The running statistics of a norm module (RowBatchNorm or an nn.BatchNorm2d) from one batch's mean / biased
+    variance over n rows, with torch ops; n: an int, or the live-row count as a 0-d / 1-element tensor."""
+    with torch.no_grad():
+        mom = bn.momentum if bn.momentum is not None else 0.1
+        unbias = n / (n - 1).clamp_min(1.0) if torch.is_tensor(n) else n / max(n - 1, 1)
+        bn.running_mean.lerp_(mean, mom)
+        bn.running_var.lerp_(var * unbias, mom)
+        if getattr(bn, "num_batches_tracked", None) is not None:
+            bn.num_batches_tracked += 1
+
+
+def running(bns, mask, rows):
+    """Who updates the running statistics of the norms `bns` (None entries: norms the call does not have) around one
+    fused forward over `rows` rows: returns (run, done).  `run` is the Function's `running` argument -- the norms'
+    _plumbing.running_of(), bare for a single norm -- when the finish kernels update the buffers, else None; then
+    done(stats, count), called after the Function with one (mean, var, ...) per norm and the live-row count it
+    returned, does it with torch ops (track)."""
+    run = None
+    if _plumbing.fused_running_stats():
+        run = tuple(_plumbing.running_of(b) if b is not None else None for b in bns)
+        run = run[0] if len(bns) == 1 else run
+
+    def done(stats, count):
+        if run is None:
+            n = count[0] if mask is not None else rows
+            for b, st in zip(bns, stats):
+                if b is not None:
+                    track(b, st[0], st[1], n)
+    return run, done
+
+
+def join_norms(last, short, nxt):
+    """The norms (bn3, bn_s or None, bn_n) of a residual block's end when the join kernels can stand for them: `nxt`
+    (the norm that follows the block) is given, `last` (the block's final convolution) applies no ReLU, and every
+    norm exists and is in training mode.  Else None.  These conditions both networks share; each adds its own."""
+    bns = (last.bn, nxt) + ((short.bn,) if short is not None else ())
+    if nxt is None or last.relu or any(b is None or not b.training for b in bns):
+        return None
+    return last.bn, short.bn if short is not None else None, nxt
+
+
+def join_rows(b3, bs, nxt, r3, rs, mask):
+    """out = b3(r3) + (bs(rs) if bs is not None else rs), y = relu(nxt(out)) over [M, C] row matrices through _JoinFn,
+    running statistics included; returns (out, y)."""
+    ws, bias_s, eps_s = (bs.weight, bs.bias, bs.eps) if bs is not None else (None, None, 0.0)
+    run, done = running((b3, bs, nxt), mask, r3.shape[0])
+    out, y, st3, sts, stn, n = _JoinFn.apply(r3, rs, b3.weight, b3.bias, ws, bias_s, nxt.weight, nxt.bias, b3.eps,
+                                             eps_s, nxt.eps, mask, run)
+    done((st3, sts, stn), n)
+    return out, y
+
+
+class RowBatchNorm(nn.Module):
+    """BatchNorm over rows ([M, C] input) with the usual running statistics; `relu=True`
+    applies the ReLU that follows it in the network inside the same kernels.  Rows are roi-major
+    (row r belongs to RoI r // (M / R)) or, with `pos_major=True`, position-major (RoI r % R): only
+    the live-row mask cares."""
+
+    def __init__(self, num_features, eps=1e-3, momentum=0.01):
+        super().__init__()
+        self.eps, self.momentum = eps, momentum
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+
+    def forward(self, x, relu=False, pos_major=False):
+        fused = _plumbing.usable(x)
+        if not self.training:
+            scale = self.weight * torch.rsqrt(self.running_var + self.eps)
+            shift = self.bias - self.running_mean * scale
+            if fused and not torch.is_grad_enabled():
+                return _plumbing.rowbn_apply(x, scale.contiguous(), shift.contiguous(), relu)
+            y = torch.addcmul(shift, x, scale)
+            return F.relu(y) if relu else y
+        mask, fits = live_mask(x.shape[0])
+        if fused and fits:
+            run, done = running((self,), mask, x.shape[0])
+            y, mean, var, n = _FusedRowBatchNormFn.apply(x, self.weight, self.bias, self.eps, bool(relu), mask,
+                                                         bool(pos_major) and mask is not None, run)
+            done(((mean, var),), n)
+            return y
+        if mask is not None:
+            y, mean, var, n = _masked_row_batch_norm(x, self.weight, self.bias, self.eps, relu, mask, pos_major)
+        else:
+            y, mean, var = _RowBatchNormFn.apply(x, self.weight, self.bias, self.eps)
+            if relu:
+                y = F.relu(y)
+            n = x.shape[0]
+        track(self, mean, var, n)
+        return y
