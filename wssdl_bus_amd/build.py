@@ -110,15 +110,16 @@ def build(force=False, verbose=True):
 # of the per-RoI head).  Not part of the drop-in C ABI, so it does not share its header.
 PLUMB_OUT = os.path.join(HERE, "libwssdl_plumbing_hip.so")
 PLUMB_SOURCES = [os.path.join("plumbing", "rowbn.hip"), os.path.join("plumbing", "im2col.hip"),
-                 os.path.join("plumbing", "taps.hip")]
+                 os.path.join("plumbing", "taps.hip"), os.path.join("plumbing", "l2decay.hip")]
+PLUMB_HEADERS = [os.path.join("plumbing", "bn_math.hip.h")]
 PLUMB_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-fvisibility=hidden",
                "-Wall"]
 
 
 def build_plumbing(force=False, verbose=True):
     srcs = [os.path.join(CSRC, s) for s in PLUMB_SOURCES]
-    if not force and os.path.exists(PLUMB_OUT) and \
-            all(os.path.getmtime(f) <= os.path.getmtime(PLUMB_OUT) for f in srcs + [os.path.abspath(__file__)]):
+    deps = srcs + [os.path.join(CSRC, h) for h in PLUMB_HEADERS] + [os.path.abspath(__file__)]
+    if not force and os.path.exists(PLUMB_OUT) and all(os.path.getmtime(f) <= os.path.getmtime(PLUMB_OUT) for f in deps):
         return PLUMB_OUT
     tmp = "%s.%d.tmp" % (PLUMB_OUT, os.getpid())
     cmd = [hipcc()] + PLUMB_FLAGS + srcs + ["-o", tmp]

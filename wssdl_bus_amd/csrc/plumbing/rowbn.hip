@@ -22,6 +22,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "bn_math.hip.h"
+
 #define PLUMB_API extern "C" __attribute__((visibility("default")))
 
 namespace {
@@ -39,11 +41,8 @@ __device__ __forceinline__ unsigned mask_roi(long long r, int div) {
 }
 
 // ---- arithmetic shared by every kernel of this file (the join kernels below must round as these do) ----
-// The fused multiply-adds are written out: left to the compiler's contraction, the same expression came out
-// fused in one kernel and as separate multiplies and subtractions in another (even lane by lane within one
-// kernel), and a join must round exactly as the layers it replaces.
-// y = x*scale + shift
-__device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return __builtin_fmaf(x, sc, sh); }
+// The fused multiply-adds are written out (why: bn_math.hip.h, which holds y = x*scale + shift, bn_affine, for this
+// file and the patch gather of taps.hip).
 // dx = a*u - k0 - k1*x (coefficients of rowbn_bwd_finish_kernel)
 __device__ __forceinline__ float bn_dx(float ka, float u, float k0, float k1, float x) {
     return __builtin_fmaf(-k1, x, __builtin_fmaf(ka, u, -k0));
@@ -797,6 +796,24 @@ PLUMB_API int wsplumb_rowbn_forward(const float *x, long long M, int C, const fl
     launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
                       Running{running_mean, running_var, momentum, num_batches_tracked});
     launch_apply_fwd(g, x, scale, shift, relu != 0, y);
+    return launched();
+}
+
+// wsplumb_rowbn_forward without its apply pass: the statistics (and the running statistics) of the layer, for a
+// consumer that applies scale / shift itself while it reads x (the patch gather of taps.hip).  Same arguments minus
+// relu and y, same values.
+PLUMB_API int wsplumb_rowbn_stats(const float *x, long long M, int C, const float *weight, const float *bias, float eps,
+                                  const float *mask, int n_rois, int per, int pos_major, float *mean, float *var,
+                                  float *rstd, float *scale, float *shift, float *count, void *workspace,
+                                  size_t workspace_bytes, void *stream, float *running_mean, float *running_var,
+                                  float momentum, long long *num_batches_tracked) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, !mask || count, workspace, workspace_bytes, 1,
+                  stream))
+        return 1;
+    launch_sums(g, x, g.p0);
+    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
+                      Running{running_mean, running_var, momentum, num_batches_tracked});
     return launched();
 }
 

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bn_math.hip.h"
+
 #define PLUMB_API extern "C" __attribute__((visibility("default")))
 
 namespace {
@@ -67,9 +69,16 @@ constexpr unsigned GATHER_CHUNK = 32, COL2IM_CHUNK = 16;    // RoIs per workgrou
 
 // blockIdx.y = unit q of the packed patch matrix (class k, position p of the class, tap tl of the class),
 // blockIdx.x = RoI chunk.  32-bit index math (total4 < 2^31, checked by the entry point).
+// NORM: x is the raw output of the convolution in front (the bottleneck's conv1) and the copy applies that layer's
+// norm and ReLU on the way, relu(x * scale + shift) with the arithmetic of rowbn_apply_fwd_kernel (bn_math.hip.h);
+// the RoIs with mask[roi] == 0 (mask may be null) are not loaded and give zeros, as the layer writes them.  The
+// thread's scale / shift float4 is loaded once per column pass.
+template <bool NORM>
 __global__ __launch_bounds__(256) void tap_gather_kernel(const float *__restrict__ x, const int *__restrict__ T,
                                                         int in_pm, unsigned R, unsigned C4,
-                                                        float *__restrict__ cols) {
+                                                        float *__restrict__ cols, const float *__restrict__ scale,
+                                                        const float *__restrict__ shift,
+                                                        const float *__restrict__ mask) {
     const int H = T[TAB_H], W = T[TAB_W], OW = T[TAB_OW], S = T[TAB_S], PT = T[TAB_PT], PL = T[TAB_PL];
     const unsigned q = blockIdx.y;
     const int *cl = cls_of(T, find_class<C_CUM>(T, q));
@@ -89,15 +98,30 @@ __global__ __launch_bounds__(256) void tap_gather_kernel(const float *__restrict
     const RoiWalk w(R, C4, GATHER_CHUNK);
     const float4v zero4 = {0.f, 0.f, 0.f, 0.f};
     for (unsigned c4 = w.lc; c4 < C4; c4 += w.L) {
+        float4v sc = zero4, sh = zero4;
+        if (NORM) {
+            sc = reinterpret_cast<const float4v *>(scale)[c4];
+            sh = reinterpret_cast<const float4v *>(shift)[c4];
+        }
+        // the (roi, c4) element: a copy, or the layer's output for a live RoI
+        auto fetch = [&](unsigned roi) -> float4v {
+            if (!NORM) return inside ? src[roi * sstride + c4] : zero4;
+            if (!inside || (mask && mask[roi] == 0.0f)) return zero4;
+            const float4v a = src[roi * sstride + c4];
+            float4v o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = bn_affine_relu(a[j], sc[j], sh[j]);
+            return o;
+        };
         unsigned roi = w.roi0 + w.lr;
         for (; roi + 3u * w.RS < w.roi1; roi += 4u * w.RS) {          // four rows in flight
             float4v v[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = inside ? src[(roi + k * w.RS) * sstride + c4] : zero4;
+            for (int k = 0; k < 4; ++k) v[k] = fetch(roi + k * w.RS);
 #pragma unroll
             for (int k = 0; k < 4; ++k) dst[(roi + k * w.RS) * dstride + c4] = v[k];
         }
-        for (; roi < w.roi1; roi += w.RS) dst[roi * dstride + c4] = inside ? src[roi * sstride + c4] : zero4;
+        for (; roi < w.roi1; roi += w.RS) dst[roi * dstride + c4] = fetch(roi);
     }
 }
 
@@ -206,17 +230,38 @@ inline bool dims_ok(long long R, int C, long long total4) {
 // int32 count of a class table
 PLUMB_API int wsplumb_tap_table_ints() { return TAB_INTS; }
 
-// cols (class-packed, TAB_UNITS * R * C floats) <- x.  tab: device copy of the class table; hnum: host copy
-// (the shape checks read it).  Returns 0 on success, 1 on a bad shape, 2 when the indices exceed 32 bits.
-PLUMB_API int wsplumb_tap_gather(const float *x, long long R, int C, const int *tab, const int *hnum, int in_pm,
-                                 float *cols, void *stream) {
+namespace {
+
+// the shape checks and the launch of both gather exports
+template <bool NORM>
+int gather_impl(const float *x, long long R, int C, const int *tab, const int *hnum, int in_pm, float *cols,
+                const float *scale, const float *shift, const float *mask, void *stream) {
     const long long total4 = (long long)hnum[TAB_UNITS] * R * (C / 4);
     if (R < 1 || C < 4 || (C & 3)) return 1;
     if (!dims_ok(R, C, total4) || (long long)hnum[TAB_H] * hnum[TAB_W] * R * (C / 4) > 0x7fffffffLL) return 2;
     if (hnum[TAB_UNITS] < 1 || hnum[TAB_UNITS] > 65535) return 1;
-    hipLaunchKernelGGL(tap_gather_kernel, dim3(roi_chunks(R, GATHER_CHUNK), hnum[TAB_UNITS]), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, tab, in_pm, (unsigned)R, (unsigned)(C / 4), cols);
+    hipLaunchKernelGGL(tap_gather_kernel<NORM>, dim3(roi_chunks(R, GATHER_CHUNK), hnum[TAB_UNITS]), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, tab, in_pm, (unsigned)R, (unsigned)(C / 4), cols, scale, shift,
+                       mask);
     return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+}  // namespace
+
+// cols (class-packed, TAB_UNITS * R * C floats) <- x.  tab: device copy of the class table; hnum: host copy
+// (the shape checks read it).  Returns 0 on success, 1 on a bad shape, 2 when the indices exceed 32 bits.
+PLUMB_API int wsplumb_tap_gather(const float *x, long long R, int C, const int *tab, const int *hnum, int in_pm,
+                                 float *cols, void *stream) {
+    return gather_impl<false>(x, R, C, tab, hnum, in_pm, cols, nullptr, nullptr, nullptr, stream);
+}
+
+// cols <- relu(x * scale + shift), zeros for the RoIs with mask[roi] == 0: the gather of the output of a row batch
+// norm + ReLU over x given that layer's scale / shift [C] (wsplumb_rowbn_stats); mask [R] f32 or null.
+PLUMB_API int wsplumb_tap_gather_norm(const float *x, long long R, int C, const int *tab, const int *hnum, int in_pm,
+                                      const float *scale, const float *shift, const float *mask, float *cols,
+                                      void *stream) {
+    if (!scale || !shift) return 1;
+    return gather_impl<true>(x, R, C, tab, hnum, in_pm, cols, scale, shift, mask, stream);
 }
 
 // dx (roi-major [R, H, W, C] or position-major) <- class-packed dcols

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from ..mil import core as mil_core
+from ..networks import _plumbing
 from ..roi_pooling_layer import roi_pooling_op
 from .config import cfg
 
@@ -108,7 +109,12 @@ def l2_weight_decay(params):
     """train_bus.py:268-270: sum(l2_loss(w)) * WEIGHT_DECAY over '*weights' variables."""
     if not params:
         return 0.0
-    return torch.stack([(p * p).sum() for p in params]).sum() * (0.5 * cfg.TRAIN.WEIGHT_DECAY)
+    k = 0.5 * cfg.TRAIN.WEIGHT_DECAY
+    if _plumbing.l2decay_usable(params):
+        # every parameter in one device op (csrc/plumbing/l2decay.hip): same gradients bit for bit, the value an
+        # f64 sum rounded once
+        return _plumbing.l2_decay(params, k)
+    return torch.stack([(p * p).sum() for p in params]).sum() * k
 
 
 def supervised_loss(layers, params, n_sup=None):

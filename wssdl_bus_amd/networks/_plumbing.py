@@ -1,6 +1,6 @@
 """ctypes binding of ``libwssdl_plumbing_hip.so``: the fused row batch-norm (+ReLU) and residual-join kernels
 (``csrc/plumbing/rowbn.hip``), the 3x3 patch kernels (``im2col.hip``) and the class-packed 3x3 convolutions
-(``taps.hip``) of the two networks.  Plumbing around the hot path, not the drop-in C ABI; when the library has not
+(``taps.hip``) of the two networks, and the one-launch L2 weight decay of the training step (``l2decay.hip``).  Plumbing around the hot path, not the drop-in C ABI; when the library has not
 been built the networks fall back to stock PyTorch ops (slower, same maths) and say so once.  Imports no sibling
 module: networks/rownorm.py, backbones.py and roi_head.py build on it, in that order.  Every export goes through
 `_call`; the `*_usable` predicates, `fused_running_stats`, `running_of`, TAPS_MIN_ROIS and TAP_GEMM_GROUPED are
@@ -37,6 +37,8 @@ def lib():
         L.wsplumb_rowbn_forward.restype = _i
         L.wsplumb_rowbn_forward.argtypes = ([_vp, _ll, _i, _vp, _vp, _f, _i, _vp, _i, _i, _i] + [_vp] * 8 + [_sz, _vp]
                                             + _RUN)
+        L.wsplumb_rowbn_stats.restype = _i
+        L.wsplumb_rowbn_stats.argtypes = [_vp, _ll, _i, _vp, _vp, _f, _vp, _i, _i, _i] + [_vp] * 7 + [_sz, _vp] + _RUN
         L.wsplumb_rowbn_apply.restype = _i
         L.wsplumb_rowbn_apply.argtypes = [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp]
         L.wsplumb_rowbn_backward.restype = _i
@@ -57,6 +59,8 @@ def lib():
             f = getattr(L, name)
             f.restype = _i
             f.argtypes = [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp]
+        L.wsplumb_tap_gather_norm.restype = _i
+        L.wsplumb_tap_gather_norm.argtypes = [_vp, _ll, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]
         for name in ("wsplumb_tap_weight_gather", "wsplumb_tap_weight_scatter"):
             f = getattr(L, name)
             f.restype = _i
@@ -65,6 +69,12 @@ def lib():
             f = getattr(L, name)
             f.restype = _i
             f.argtypes = [_vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]
+        L.wsplumb_l2decay_chunk.restype = _i
+        L.wsplumb_l2decay_chunk.argtypes = []
+        L.wsplumb_l2decay_forward.restype = _i
+        L.wsplumb_l2decay_forward.argtypes = [_vp, _i, _vp, _f, _vp, _vp]
+        L.wsplumb_l2decay_backward.restype = _i
+        L.wsplumb_l2decay_backward.argtypes = [_vp, _i, _vp, _f, _vp, _vp]
         _lib = L
     return _lib
 
@@ -78,7 +88,10 @@ SWITCHES = {
     "WSSDL_HEAD_UNFUSED_JOIN": "the head's residual joins: separate norms and a torch add (join_usable)",
     "WSSDL_TRUNK_UNFUSED_JOIN": "the trunk's residual joins: separate layers (backbones._join)",
     "WSSDL_DISABLE_FUSED_IM2COL": "3x3 patches by pad / unfold, not the patch kernels (im2col_usable)",
+    "WSSDL_HEAD_UNFUSED_TAPNORM": "a bottleneck's conv1 norm as its own layer in front of the 3x3 patch gather "
+                                  "(tapnorm_usable)",
     "WSSDL_HEAD_DENSE_3X3": "the head's 3x3 convolutions on the dense patch route (taps_usable)",
+    "WSSDL_TORCH_L2_DECAY": "the L2 weight decay by torch's per-parameter multiply / sum chain (l2decay_usable)",
 }
 
 
@@ -177,6 +190,19 @@ def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False, *, run
           *_mask_args(mask, M), int(bool(pos_major) and mask is not None), _p(y), *[_p(stats[i]) for i in range(5)],
           _pn(count), _p(ws), ws.numel(), tail=_run_args(running))
     return y, stats, count
+
+
+def rowbn_stats(x, weight, bias, eps, mask=None, pos_major=False, *, running=None):
+    """rowbn_forward without its apply pass: (stats, count), the layer's output left to a consumer that applies
+    stats[3] / stats[4] (scale / shift) while it reads x (tap_gather_norm)."""
+    M, C = x.shape
+    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)
+    count = torch.empty((1,), dtype=torch.float32, device=x.device) if mask is not None else None
+    ws = _workspace(x)
+    _call("wsplumb_rowbn_stats", x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), *_mask_args(mask, M),
+          int(bool(pos_major) and mask is not None), *[_p(stats[i]) for i in range(5)], _pn(count), _p(ws), ws.numel(),
+          tail=_run_args(running))
+    return stats, count
 
 
 def rowbn_apply(x, scale, shift, relu):
@@ -437,6 +463,25 @@ def tap_gather(x, plan, in_pm, R):
     return cols
 
 
+def tapnorm_usable(x):
+    """True when the patch gather may apply the norm + ReLU of the [M, C] rows x it reads (tap_gather_norm)."""
+    return not switch("WSSDL_HEAD_UNFUSED_TAPNORM") and usable(x)
+
+
+def tap_gather_norm(x, plan, in_pm, R, scale, shift, mask=None):
+    """tap_gather(relu(x * scale + shift) with the rows of the RoIs mask marks dead zeroed) without that tensor:
+    x the rows [h*w*R, C] of a row batch norm's input (roi-major or position-major), scale / shift its stats[3] /
+    stats[4], mask [R] f32 or None."""
+    C = x.shape[-1]
+    assert x.numel() == plan.h * plan.w * R * C and x.is_contiguous() and (not in_pm or plan.h == plan.oh)
+    assert scale.shape == (C,) and shift.shape == (C,) and scale.is_contiguous() and shift.is_contiguous()
+    assert mask is None or (mask.shape == (R,) and mask.dtype == torch.float32 and mask.is_contiguous())
+    cols = torch.empty((plan.units * R * C,), dtype=torch.float32, device=x.device)
+    _call("wsplumb_tap_gather_norm", x.device, _p(x), R, C, _p(plan.device_table(x.device)), plan.hnum, int(in_pm),
+          _p(scale), _p(shift), _pn(mask), _p(cols))
+    return cols
+
+
 def tap_col2im(dcols, plan, in_pm, R, C):
     """adjoint of tap_gather: dx roi-major [R, h, w, C], or position-major [h*w*R, C] with in_pm."""
     shape = (plan.h * plan.w * R, C) if in_pm else (R, plan.h, plan.w, C)
@@ -472,70 +517,202 @@ def _gemm_groups(plan, fn):
                 fn(k0, n, npos, ntaps, slice(j, j + 1))
 
 
+def tap_gemms_forward(cols, weight, bias, plan, R):
+    """The class GEMMs of a 3x3 convolution over the class-packed patches `cols`: (position-major output
+    [oh*ow*R, c_o], the class-packed weight)."""
+    C, CO = weight.shape[1] // 9, weight.shape[0]
+    wp = tap_weight_gather(weight.contiguous(), plan)
+    out = torch.empty((plan.oh * plan.ow * R, CO), dtype=torch.float32, device=cols.device)
+
+    def gemm(k0, n, npos, ntaps, j):
+        a = cols[plan.cum[k0] * R * C:(plan.cum[k0] + n * npos * ntaps) * R * C].view(n, npos * R, ntaps * C)
+        b = wp[plan.wcum[k0] * CO * C:(plan.wcum[k0] + n * ntaps) * CO * C].view(n, CO, ntaps * C)
+        o = out[plan.slot_base[k0] * R:(plan.slot_base[k0] + n * npos) * R].view(n, npos * R, CO)
+        if j.stop - j.start == 1:
+            torch.mm(a[j.start], b[j.start].t(), out=o[j.start])
+        else:
+            torch.bmm(a, b.transpose(1, 2), out=o)
+
+    _gemm_groups(plan, gemm)
+    if bias is not None:
+        out.add_(bias)
+    return out, wp
+
+
+def tap_gemms_backward(dy, cols, wp, plan, R, C, CO, need_x, need_w):
+    """Gradients of tap_gemms_forward: (the input's in the layout of tap_col2im's result or None, the weight's
+    [c_o, 9*C] or None)."""
+    dcols = torch.empty_like(cols) if need_x else None
+    dwp = torch.empty_like(wp) if need_w else None
+
+    def gemm(k0, n, npos, ntaps, j):
+        g = dy[plan.slot_base[k0] * R:(plan.slot_base[k0] + n * npos) * R].view(n, npos * R, CO)
+        cs = slice(plan.cum[k0] * R * C, (plan.cum[k0] + n * npos * ntaps) * R * C)
+        ws = slice(plan.wcum[k0] * CO * C, (plan.wcum[k0] + n * ntaps) * CO * C)
+        one = j.stop - j.start == 1
+        if need_x:
+            b = wp[ws].view(n, CO, ntaps * C)
+            o = dcols[cs].view(n, npos * R, ntaps * C)
+            if one:
+                torch.mm(g[j.start], b[j.start], out=o[j.start])
+            else:
+                torch.bmm(g, b, out=o)
+        if need_w:
+            a = cols[cs].view(n, npos * R, ntaps * C)
+            o = dwp[ws].view(n, CO, ntaps * C)
+            if one:
+                torch.mm(g[j.start].t(), a[j.start], out=o[j.start])
+            else:
+                torch.bmm(g.transpose(1, 2), a, out=o)
+
+    _gemm_groups(plan, gemm)
+    return dcols, tap_weight_scatter(dwp, plan, CO, C) if need_w else None
+
+
 class TapConv3x3Fn(torch.autograd.Function):
     """3x3 TF-'SAME' convolution over the valid taps only (TapPlan): x is roi-major [R, h, w, C] or, with
     in_pm, position-major [h*w*R, C] in the plan's slot order; weight [c_o, 9*C] (kh, kw, c); returns the
     position-major [oh*ow*R, c_o] output.  One GEMM per class group (torch's hipBLASLt); patches, weights
-    and their gradients move between the dense and the class-packed layouts in taps.hip."""
+    and their gradients move between the dense and the class-packed layouts in taps.hip.
+
+    With norm_w / norm_b (a row batch norm's weight and bias; eps, roi_mask and running as rowbn_forward takes them)
+    x is instead the RAW rows [h*w*R, C] in front of that norm + ReLU -- a bottleneck's conv1 output -- and the
+    convolution runs over relu(bn(x)): the forward takes the norm's statistics (two of the layer's three kernels,
+    running statistics included) and the patch gather applies scale, shift and ReLU while it copies
+    (tap_gather_norm), so the layer's output is never written, read back or kept for the backward.  The backward is
+    the two layers': the class GEMMs, the patches' adjoint, then rowbn_backward on (x, that gradient).  Returns
+    (out, mean, var, live-row count) then; bit-identical to the separate layers."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, plan, in_pm, R):
+    def forward(ctx, x, weight, bias, plan, in_pm, R, norm_w=None, norm_b=None, eps=0.0, roi_mask=None, running=None):
         C, CO = weight.shape[1] // 9, weight.shape[0]
         x = x.contiguous()
         assert x.shape[-1] == C and x.numel() == plan.h * plan.w * R * C and (not in_pm or plan.h == plan.oh)
-        cols = tap_gather(x, plan, in_pm, R)
-        wp = tap_weight_gather(weight.contiguous(), plan)
-        out = torch.empty((plan.oh * plan.ow * R, CO), dtype=torch.float32, device=x.device)
+        normed = norm_w is not None
+        if normed:
+            x = x.view(-1, C)
+            stats, count = rowbn_stats(x, norm_w, norm_b, eps, roi_mask, in_pm, running=running)
+            cols = tap_gather_norm(x, plan, in_pm, R, stats[3], stats[4], roi_mask)
+        else:
+            cols = tap_gather(x, plan, in_pm, R)
+        out, wp = tap_gemms_forward(cols, weight, bias, plan, R)
+        ctx.geom = (plan, bool(in_pm), R, C, CO, bias is not None, normed)
+        if not normed:
+            ctx.save_for_backward(cols, wp)
+            return out
+        ctx.save_for_backward(cols, wp, x, norm_w, stats, roi_mask)
+        mean, var = stats[0], stats[1]
+        if count is None:
+            count = stats[0, :1]                           # placeholder without a mask (unused: no extra launch)
+        ctx.mark_non_differentiable(mean, var, count)
+        ctx.set_materialize_grads(False)                   # no zero-filled gradients for the side outputs
+        return out, mean, var, count
 
-        def gemm(k0, n, npos, ntaps, j):
-            a = cols[plan.cum[k0] * R * C:(plan.cum[k0] + n * npos * ntaps) * R * C].view(n, npos * R, ntaps * C)
-            b = wp[plan.wcum[k0] * CO * C:(plan.wcum[k0] + n * ntaps) * CO * C].view(n, CO, ntaps * C)
-            o = out[plan.slot_base[k0] * R:(plan.slot_base[k0] + n * npos) * R].view(n, npos * R, CO)
-            if j.stop - j.start == 1:
-                torch.mm(a[j.start], b[j.start].t(), out=o[j.start])
-            else:
-                torch.bmm(a, b.transpose(1, 2), out=o)
+    @staticmethod
+    def backward(ctx, dy, *_):
+        cols, wp = ctx.saved_tensors[:2]
+        plan, in_pm, R, C, CO, has_bias, normed = ctx.geom
+        dy = dy.contiguous() if dy is not None else cols.new_zeros((plan.oh * plan.ow * R, CO))
+        need_x = ctx.needs_input_grad[0] or (normed and (ctx.needs_input_grad[6] or ctx.needs_input_grad[7]))
+        dcols, dw = tap_gemms_backward(dy, cols, wp, plan, R, C, CO, need_x, ctx.needs_input_grad[1])
+        dx = tap_col2im(dcols, plan, in_pm, R, C) if need_x else None
+        db = dwn = dbn = None
+        if has_bias and ctx.needs_input_grad[2]:
+            db = dy.sum(0)
+        if normed and need_x:
+            x, norm_w, stats, roi_mask = ctx.saved_tensors[2:]
+            dx, dwn, dbn = rowbn_backward(x, dx.view(x.shape), norm_w, stats, True, roi_mask, in_pm)
+        return dx, dw, db, None, None, None, dwn, dbn, None, None, None
 
-        _gemm_groups(plan, gemm)
-        if bias is not None:
-            out.add_(bias)
-        ctx.save_for_backward(cols, wp)
-        ctx.geom = (plan, bool(in_pm), R, C, CO, bias is not None)
+# ---- L2 weight decay over all the decayed parameters as one device op (csrc/plumbing/l2decay.hip) ----
+_L2_CHUNK = 4096                    # floats per chunk: keep in sync with CHUNK of l2decay.hip
+_L2_ALIGN = 4                       # every parameter starts on a float4 of the flat gradient buffer
+
+
+def _storage_dense(p):
+    """True when p's elements fill numel() consecutive floats of its storage in some order of its dimensions
+    (contiguous, channels_last, any permutation of a contiguous tensor)."""
+    expect = 1
+    for stride, size in sorted((st, sz) for sz, st in zip(p.shape, p.stride()) if sz != 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return p.numel() > 0
+
+
+def l2decay_usable(params):
+    """True when l2_decay takes this parameter list: every one a dense f32 tensor on the same GPU."""
+    if switch("WSSDL_TORCH_L2_DECAY") or not params:
+        return False
+    dev = params[0].device
+    if not all(p.is_cuda and p.device == dev and p.dtype == torch.float32 and _storage_dense(p) for p in params):
+        return False
+    return lib() is not None
+
+
+class _L2Table:
+    """Device table of l2decay.hip for one parameter list: row i = (address of chunk i's first float, its element
+    offset in the flat gradient buffer, its length), the parameters walked in storage order; `offsets` are the
+    parameters' own offsets in the flat buffer, `total` its length."""
+
+    def __init__(self, params):
+        rows, self.offsets, off = [], [], 0
+        for p in params:
+            self.offsets.append(off)
+            n, base = p.numel(), p.data_ptr()
+            for first in range(0, n, _L2_CHUNK):
+                rows.append((base + 4 * first, off + first, min(_L2_CHUNK, n - first)))
+            off += -(-n // _L2_ALIGN) * _L2_ALIGN
+        self.total, self.n_chunks = off, len(rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(params[0].device)
+
+
+_L2_TABLES = {}                     # device -> (key, _L2Table): the last parameter list seen on it
+L2_TABLE_BUILDS = [0]               # tables built so far (tests read it)
+
+
+def _l2_table(params):
+    """The table of `params`, cached while they stay where they are (the optimiser updates them in place, so a
+    training run builds it once); anything else -- another list, a re-allocated parameter -- rebuilds it."""
+    key = tuple((p.data_ptr(), tuple(p.shape), p.stride()) for p in params)
+    dev = params[0].device
+    hit = _L2_TABLES.get(dev)
+    if hit is None or hit[0] != key:
+        assert lib().wsplumb_l2decay_chunk() == _L2_CHUNK
+        hit = _L2_TABLES[dev] = (key, _L2Table(params))
+        L2_TABLE_BUILDS[0] += 1
+    return hit[1]
+
+
+class _L2DecayFn(torch.autograd.Function):
+    """f32(sum over every parameter of sum(p * p)) * k as two launches; the backward writes every parameter's
+    gradient 2 * p * (gout * k) into one flat buffer with one launch and returns views of it that have the
+    parameters' own strides.  The gradients are bit-identical to those of torch's chain
+    stack([(p * p).sum() ...]).sum() * k; the value is the f64 sum rounded once (torch sums in f32)."""
+
+    @staticmethod
+    def forward(ctx, k, *params):
+        tab = _l2_table(params)
+        dev = params[0].device
+        partial = torch.empty((tab.n_chunks,), dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        _call("wsplumb_l2decay_forward", dev, _p(tab.table), tab.n_chunks, _p(partial), float(k), _p(out))
+        ctx.save_for_backward(*params)
+        ctx.k = float(k)
         return out
 
     @staticmethod
-    def backward(ctx, dy):
-        cols, wp = ctx.saved_tensors
-        plan, in_pm, R, C, CO, has_bias = ctx.geom
-        dy = dy.contiguous()
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dcols = torch.empty_like(cols) if need_x else None
-        dwp = torch.empty_like(wp) if need_w else None
+    def backward(ctx, gout):
+        params = ctx.saved_tensors
+        tab = _l2_table(params)
+        dev = params[0].device
+        gout = gout.to(torch.float32).contiguous()
+        flat = torch.empty((tab.total,), dtype=torch.float32, device=dev)
+        _call("wsplumb_l2decay_backward", dev, _p(tab.table), tab.n_chunks, _p(gout), ctx.k, _p(flat))
+        return (None,) + tuple(flat.as_strided(p.shape, p.stride(), off) if need else None
+                               for p, off, need in zip(params, tab.offsets, ctx.needs_input_grad[1:]))
 
-        def gemm(k0, n, npos, ntaps, j):
-            g = dy[plan.slot_base[k0] * R:(plan.slot_base[k0] + n * npos) * R].view(n, npos * R, CO)
-            cs = slice(plan.cum[k0] * R * C, (plan.cum[k0] + n * npos * ntaps) * R * C)
-            ws = slice(plan.wcum[k0] * CO * C, (plan.wcum[k0] + n * ntaps) * CO * C)
-            one = j.stop - j.start == 1
-            if need_x:
-                b = wp[ws].view(n, CO, ntaps * C)
-                o = dcols[cs].view(n, npos * R, ntaps * C)
-                if one:
-                    torch.mm(g[j.start], b[j.start], out=o[j.start])
-                else:
-                    torch.bmm(g, b, out=o)
-            if need_w:
-                a = cols[cs].view(n, npos * R, ntaps * C)
-                o = dwp[ws].view(n, CO, ntaps * C)
-                if one:
-                    torch.mm(g[j.start].t(), a[j.start], out=o[j.start])
-                else:
-                    torch.bmm(g.transpose(1, 2), a, out=o)
 
-        _gemm_groups(plan, gemm)
-        dx = tap_col2im(dcols, plan, in_pm, R, C) if need_x else None
-        dw = tap_weight_scatter(dwp, plan, CO, C) if need_w else None
-        db = None
-        if has_bias and ctx.needs_input_grad[2]:
-            db = dy.sum(0)
-        return dx, dw, db, None, None, None
+def l2_decay(params, k):
+    """sum(sum(p * p) for p in params) * k as a 0-dim f32 tensor on the parameters' device (l2decay_usable)."""
+    return _L2DecayFn.apply(float(k), *params)

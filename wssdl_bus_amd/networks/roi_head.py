@@ -74,6 +74,17 @@ class ConvNHWC(nn.Module):
         return self._act(y, pos_major=True) if act else y
 
 
+def _norm_tap_conv(c1, c2, rows, plan, in_pm, R, mask):
+    """c2 (3x3, raw output) over relu(c1.bn(rows)) with the norm inside the patch gather (TapConv3x3Fn's norm form),
+    c1.bn's running statistics included."""
+    bn = c1.bn
+    run, done = rownorm.running((bn,), mask, rows.shape[0])
+    y, mean, var, n = _plumbing.TapConv3x3Fn.apply(rows, c2.weight, None, plan, in_pm, R, bn.weight, bn.bias, bn.eps,
+                                                   mask, run)
+    done(((mean, var),), n)
+    return y
+
+
 def _norm_relu(bn, x):
     """relu(bn(x)), bn a RowBatchNorm or None, x a roi-major [R, h, w, C] map or position-major rows."""
     if bn is None:
@@ -107,11 +118,39 @@ class _BlockNHWC(nn.Module):
         else:
             x, ori = _preact(self, x, pre, _norm_relu)
         *body, last = _convs(self)
+        if self._tapnorm_fused(body, x):
+            x, body = self._conv12_pm(body[0], body[1], x, plans[body[1].s], R), ()
         for conv in body:
             # a 1x1 ahead of the strided convolution keeps a roi-major map roi-major (the bottleneck's conv1 on 7x7)
             x = conv(x) if (conv.k == 1 and x.dim() == 4) else conv.forward_pm(x, plans[conv.s], R)
         x = last.forward_pm(x, plans[last.s], R, act=False)
         return _join_pm(last, x, self.short, ori, plans[s], s, R, nxt)
+
+    @staticmethod
+    def _tapnorm_fused(body, x):
+        """True when the body is a bottleneck's conv1 -> conv2 pair in the form TapConv3x3Fn's norm form covers: a 1x1 at
+        stride 1 with a training-mode norm and a ReLU, then a 3x3 without a bias, on the GPU, and the switch
+        WSSDL_HEAD_UNFUSED_TAPNORM not set."""
+        if len(body) != 2 or _plumbing.switch("WSSDL_HEAD_UNFUSED_TAPNORM"):
+            return False
+        c1, c2 = body
+        return (c1.k == 1 and c1.s == 1 and c1.relu and c1.bn is not None and c1.bn.training and c2.k == 3
+                and c2.bias is None and x.is_cuda and _plumbing.lib() is not None)
+
+    @staticmethod
+    def _conv12_pm(c1, c2, x, plan, R):
+        """conv1 -> conv2 with their norms: conv1's norm inside conv2's patch gather when the kernels take conv1's
+        raw rows and the live-row mask is one entry per RoI, else the separate layers."""
+        in_pm = x.dim() == 2
+        rows = F.linear(x if in_pm else x.reshape(-1, x.shape[3]), c1.weight, c1.bias)
+        mask, fits = rownorm.live_mask(rows.shape[0])
+        if _plumbing.tapnorm_usable(rows) and fits and (mask is None or mask.shape[0] == R):
+            y = _norm_tap_conv(c1, c2, rows, plan, in_pm, R, mask)
+        else:
+            y1 = c1._act(rows, pos_major=in_pm)
+            y = _plumbing.TapConv3x3Fn.apply(y1 if in_pm else y1.view(R, plan.h, plan.w, -1), c2.weight, c2.bias, plan,
+                                             in_pm, R)
+        return c2._act(y, pos_major=True)
 
     def _entry_fused(self, x, pre):
         """True when this is block 1 of the position-major route in the form _EntryNormFn covers: a roi-major
