@@ -2,7 +2,9 @@
 `rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline`
 (tools/step_breakdown.sh): the window between the last five roi_pool_bwd launches = 4 steps.
 
-    python tools/step_kernel_classes.py DIR [TAG] [TOPN]
+    python tools/step_kernel_classes.py DIR [TAG] [TOPN] [SUBSTRING ...]
+
+Each SUBSTRING adds a COUNT line: calls, ms per step and mean us per launch of the kernels whose name contains it.
 """
 import csv
 import glob
@@ -52,6 +54,11 @@ def main():
     for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0]):
         if "rowbn_" in k or "CUDAFunctor_add" in k:
             print("KERNEL " + fmt % (v[0] / steps, v[1] / steps, v[0] / v[1] * 1e3, k[:120]))
+    for sub in sys.argv[4:]:
+        ms = sum(v[0] for k, v in agg.items() if sub in k)
+        n = sum(v[1] for k, v in agg.items() if sub in k)
+        print("COUNT %-60s calls/step=%6.1f ms/step=%7.3f avg_us=%8.1f" % (sub[:60], n / steps, ms / steps,
+                                                                           ms / n * 1e3 if n else 0.0))
 
 
 if __name__ == "__main__":

@@ -90,19 +90,31 @@ __device__ __forceinline__ void store4(float *__restrict__ p, long long r, int C
 // with dy conv1's gradient, dys the shortcut's position-major gradient and possel[p] the shortcut's slot of
 // position p (-1: not sampled).  The ENTRY variants of the two backward kernels form it in registers.  The
 // "+ 0" is kept: the separate ops scatter dys into a zero tensor first, which turns a -0 into +0.
+//
+// ---- the head's exit gradient (networks/roi_head.py: the last _JoinFn in its exit form) ----
+// The head's output is the mean over the slots of its final norm's position-major output y, so the gradient of y at
+// row r is dfeat[r % R] * (1 / n_slots): DY_EXIT forms it in registers from dfeat [R, C] (passed as dy) instead of
+// reading a [n_slots * R, C] expansion of it.  Same values, so whatever a kernel computes from them is the same.
+enum DySrc { DY_PLAIN, DY_ENTRY, DY_EXIT };
+
 struct EntryGrad {
-    const float *dys;       // [n_slots * R, C]
-    const int *possel;      // [per]
-    int per, R;
+    const float *dys;       // DY_ENTRY: [n_slots * R, C]
+    const int *possel;      // DY_ENTRY: [per]
+    int per, R;             // R also DY_EXIT
+    float inv;              // DY_EXIT: slot_mean_scale(n_slots)
 };
 
-template <bool ENTRY>
+template <DySrc SRC>
 __device__ __forceinline__ float4v load_dy(const float *__restrict__ dy, const EntryGrad &e, long long r, int C, int c4,
                                            bool on = true) {
     const float4v zero4 = {0, 0, 0, 0};
     if (!on) return zero4;
+    if (SRC == DY_EXIT) {
+        const unsigned roi = (unsigned)r % (unsigned)e.R;
+        return reinterpret_cast<const float4v *>(dy + (size_t)roi * C)[c4] * e.inv;
+    }
     const float4v g = reinterpret_cast<const float4v *>(dy + (size_t)r * C)[c4];
-    if (!ENTRY) return g;
+    if (SRC == DY_PLAIN) return g;
     const unsigned roi = (unsigned)r / (unsigned)e.per, p = (unsigned)r - roi * (unsigned)e.per;
     const int slot = e.possel[p];
     float4v d = zero4;
@@ -211,8 +223,9 @@ __device__ __forceinline__ void slab_walk(const Slab &b, int C, const float *__r
 // Partial column sums of one row slab.
 // MODE 0: s = sum x,  q = sum x*x
 // MODE 1: s = sum g,  q = sum g*x   with g = dy, masked by (x*scale + shift > 0) when RELU
-// ENTRY: dy is block 1's entry gradient (EntryGrad; MODE 1, roi-major rows, M < 2^31)
-template <int MODE, bool RELU, bool ENTRY>
+// SRC: where dy comes from (MODE 1, M < 2^31 unless DY_PLAIN): block 1's entry gradient (roi-major rows) or the
+// head's exit gradient (position-major rows)
+template <int MODE, bool RELU, DySrc SRC>
 struct PartialCols {
     static constexpr bool VISITS_DEAD = false, TWO_Q = false;
     const float *x, *dy, *scale, *shift;
@@ -230,7 +243,7 @@ struct PartialCols {
     }
     __device__ __forceinline__ Row load(long long r, int c4, bool live) const {
         Row w = {load4(x, r, C, c4, live), {0, 0, 0, 0}};
-        if (MODE == 1) w.g = load_dy<ENTRY>(dy, eg, r, C, c4, live);
+        if (MODE == 1) w.g = load_dy<SRC>(dy, eg, r, C, c4, live);
         return w;
     }
     __device__ __forceinline__ Term finish(const Row &w, long long, int, bool) const {
@@ -245,29 +258,45 @@ struct PartialCols {
     }
 };
 
-template <int MODE, bool RELU, int MASK, bool ENTRY = false>
+template <int MODE, bool RELU, int MASK, DySrc SRC = DY_PLAIN>
 __global__ __launch_bounds__(BLOCK) void rowbn_partial_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ scale,
     const float *__restrict__ shift, long long M, int C, long long rows_per_block,
     double *__restrict__ partial, const float *__restrict__ mask, int per, EntryGrad eg = EntryGrad()) {
     __shared__ double red[BLOCK][8];
     const Slab b(M, C, rows_per_block);
-    PartialCols<MODE, RELU, ENTRY> f = {x, dy, scale, shift, C, eg};
+    PartialCols<MODE, RELU, SRC> f = {x, dy, scale, shift, C, eg};
     slab_walk<MASK>(b, C, mask, per, f, red, partial + (size_t)blockIdx.x * 2 * C);
 }
 
 // Sum of the per-workgroup partials of 16 columns, in a fixed order: 64 row groups of 16 lanes
 // each add every 64th partial (in order), then lane-wise the 64 group sums are added in order.
-constexpr int FIN_COLS = 16, FIN_GROUPS = 64;
+// A thread owns the partials b = grp, grp + 64, ...: at most FIN_DEPTH of them.  All of its loads are issued before
+// the first addition (a load per step and a wait for it made the kernel a chain of FIN_DEPTH trips to memory); the
+// additions are those of the plain loop, in its order, from 0.0: a step past nblocks loads nothing and adds nothing.
+constexpr int FIN_COLS = 16, FIN_GROUPS = 64, FIN_DEPTH = MAX_PARTIAL_BLOCKS / FIN_GROUPS, WAVE = 64;
+static_assert(MAX_PARTIAL_BLOCKS == FIN_DEPTH * FIN_GROUPS && FIN_DEPTH == 16, "a finish thread owns at most 16 partials");
+static_assert((FIN_COLS * FIN_GROUPS) % WAVE == 0 && FIN_COLS * FIN_GROUPS / WAVE <= WAVE, "live_rows: one LDS step");
 
 __device__ __forceinline__ void finish_reduce(const double *__restrict__ partial, int nblocks, int C,
                                               int c, int grp, double (*red)[FIN_COLS][2], double &s,
                                               double &q) {
+    double ps[FIN_DEPTH], pq[FIN_DEPTH];
+#pragma unroll
+    for (int k = FIN_DEPTH - 1; k >= 0; --k) {      // issue order only (last step first: the compiler keeps the first
+        const int b = grp + k * FIN_GROUPS;         // addition next to the load of step 0, so that load goes out last)
+        ps[k] = pq[k] = 0.0;
+        if (c < C && b < nblocks) {
+            ps[k] = partial[(size_t)b * 2 * C + c];
+            pq[k] = partial[(size_t)b * 2 * C + C + c];
+        }
+    }
     double ss = 0.0, qq = 0.0;
-    if (c < C)
-        for (int b = grp; b < nblocks; b += FIN_GROUPS) {
-            ss += partial[(size_t)b * 2 * C + c];
-            qq += partial[(size_t)b * 2 * C + C + c];
+#pragma unroll
+    for (int k = 0; k < FIN_DEPTH; ++k)
+        if (c < C && grp + k * FIN_GROUPS < nblocks) {
+            ss += ps[k];
+            qq += pq[k];
         }
     red[grp][threadIdx.x % FIN_COLS][0] = ss;
     red[grp][threadIdx.x % FIN_COLS][1] = qq;
@@ -282,19 +311,36 @@ __device__ __forceinline__ void finish_reduce(const double *__restrict__ partial
 }
 
 // rows the statistics are taken over: M, or per * (number of live RoIs) with a mask (at least 1).
-// Every thread of the workgroup returns the same value; the sum runs in a fixed order.
+// Every thread of the workgroup returns the same value.  The live RoIs are counted as integers (a sum of 0 / 1
+// values, exact in any order; n_rois < 2^31): LIVE_LOADS mask loads in flight per thread, a shuffle reduction within each
+// wave, one LDS step across the waves, and one conversion to f64.
 __device__ __forceinline__ double live_rows(const float *__restrict__ mask, int n_rois, int per, long long M,
                                             double *scratch /* [FIN_COLS * FIN_GROUPS] LDS */) {
     if (!mask) return (double)M;
-    double c = 0.0;
-    for (int i = threadIdx.x; i < n_rois; i += FIN_COLS * FIN_GROUPS) c += mask[i] != 0.0f ? 1.0 : 0.0;
+    constexpr int T = FIN_COLS * FIN_GROUPS, NW = T / WAVE, LIVE_LOADS = 8;
+    int n = 0;
+    const unsigned last = (unsigned)n_rois - 1;     // a step past the end re-reads the last entry and does not count
+    for (unsigned i0 = threadIdx.x; i0 <= last; i0 += LIVE_LOADS * T) {     // unsigned: n_rois + LIVE_LOADS * T < 2^32
+        float m[LIVE_LOADS];
+#pragma unroll
+        for (int k = 0; k < LIVE_LOADS; ++k) {
+            const unsigned i = i0 + k * T;
+            m[k] = mask[i <= last ? i : last];
+        }
+#pragma unroll
+        for (int k = 0; k < LIVE_LOADS; ++k) n += (i0 + k * T <= last && m[k] != 0.0f) ? 1 : 0;
+    }
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1) n += __shfl_xor(n, d, WAVE);
+    int *cnt = reinterpret_cast<int *>(scratch);
     __syncthreads();
-    scratch[threadIdx.x] = c;
+    if (threadIdx.x % WAVE == 0) cnt[threadIdx.x / WAVE] = n;
     __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < FIN_COLS * FIN_GROUPS; ++i) t += scratch[i];
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) total += cnt[w];
     __syncthreads();
-    t *= (double)per;
+    const double t = (double)total * (double)per;
     return t < 1.0 ? 1.0 : t;
 }
 
@@ -336,8 +382,10 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel
     double s, q;
     finish_reduce(partial, nblocks, C, c, grp, red, s, q);
     if (grp != 0 || c >= C) return;
+    // The fused multiply-adds are written out, as the compiler's contraction always formed them (the host restates
+    // these lines: tests/test_gpu_rowbn_finish.py): v = fma(-mu, mu, q / n), shift = fmaf(-scale, mean, bias).
     const double mu = s / Mn;
-    double v = q / Mn - mu * mu;
+    double v = __builtin_fma(-mu, mu, q / Mn);
     if (v < 0.0) v = 0.0;
     const float rs = (float)(1.0 / sqrt(v + (double)eps));
     const float scl = rs * weight[c];
@@ -345,7 +393,7 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel
     var[c] = (float)v;
     rstd[c] = rs;
     scale[c] = scl;
-    shift[c] = bias[c] - (float)mu * scl;
+    shift[c] = __builtin_fmaf(-scl, (float)mu, bias[c]);
     const double mom = (double)run.momentum;
     if (run.mean) run.mean[c] = running_update(run.mean[c], (float)mu, 1.0, mom);
     if (run.var) run.var[c] = running_update(run.var[c], (float)v, Mn / (Mn - 1.0 > 1.0 ? Mn - 1.0 : 1.0), mom);
@@ -364,11 +412,12 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_kernel
     double sg, sgx;
     finish_reduce(partial, nblocks, C, c, grp, red, sg, sgx);
     if (grp != 0 || c >= C) return;
+    // fused multiply-adds written out as in the forward finish: fma(-mu, sg, sgx) and k0 = fma(-k1, mu, a * sg / n)
     const double mu = mean[c], rs = rstd[c], w = weight[c];
-    const double sum_g_xhat = (sgx - mu * sg) * rs;
+    const double sum_g_xhat = __builtin_fma(-mu, sg, sgx) * rs;
     const double a = w * rs;
     const double k1 = a * rs * sum_g_xhat / Mn;
-    const double k0 = a * sg / Mn - k1 * mu;
+    const double k0 = __builtin_fma(-k1, mu, a * sg / Mn);
     dweight[c] = (float)sum_g_xhat;
     dbias[c] = (float)sg;
     coef[c] = (float)a;
@@ -376,16 +425,34 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_kernel
     coef[2 * C + c] = (float)k1;
 }
 
-template <bool RELU, int MASK>
+// Block 1's entry (networks/roi_head.py, _EntryNormFn): besides y (roi-major rows, `per` positions per RoI), the
+// forward apply pass writes the rows of the positions the projection shortcut samples a second time, position-major:
+// ys[possel[p] * R + roi] = y[roi * per + p] where possel[p] >= 0 (the table of EntryGrad).  A copy of the float4 it
+// has just stored, zeros for a dead RoI.
+struct EntryRows {
+    float *ys;              // [n_slots * R, C]
+    const int *possel;      // [per]
+    int per, R;
+};
+
+template <bool RELU, int MASK, bool ENTRY = false>
 __global__ __launch_bounds__(BLOCK) void rowbn_apply_fwd_kernel(
     const float *__restrict__ x, const float *__restrict__ scale, const float *__restrict__ shift,
-    long long total4, int C4, float *__restrict__ y, const float *__restrict__ mask, int per) {
+    long long total4, int C4, float *__restrict__ y, const float *__restrict__ mask, int per,
+    EntryRows er = EntryRows()) {
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total4;
          i += (long long)gridDim.x * BLOCK) {
         const int c4 = (int)(i % C4);
+        float4v *ys4 = nullptr;     // where this row goes in ys, if anywhere
+        if (ENTRY) {
+            const unsigned r = (unsigned)(i / C4), roi = r / (unsigned)er.per, p = r - roi * (unsigned)er.per;
+            const int slot = er.possel[p];
+            if (slot >= 0) ys4 = reinterpret_cast<float4v *>(er.ys) + ((size_t)slot * er.R + roi) * C4 + c4;
+        }
         if (MASK && mask[mask_roi<MASK>(i / C4, per)] == 0.0f) {
             const float4v zero4 = {0, 0, 0, 0};
             reinterpret_cast<float4v *>(y)[i] = zero4;
+            if (ENTRY && ys4) *ys4 = zero4;
             continue;
         }
         const float4v a = reinterpret_cast<const float4v *>(x)[i];
@@ -399,6 +466,53 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_fwd_kernel(
             o[j] = v;
         }
         reinterpret_cast<float4v *>(y)[i] = o;
+        if (ENTRY && ys4) *ys4 = o;
+    }
+}
+
+// The head's exit: feat[roi] = the mean over the slots (bn_math.hip.h: slot order, chunks of 16, a balanced tree per
+// chunk) of the position-major rows x[slot * R + roi] -- with NORM of relu(x*scale + shift), the final norm's output
+// as rowbn_apply_fwd_kernel<true> would write it, which is then never written.  A dead RoI's row of feat is zero and
+// nothing of it is read.  One thread per (roi, float4 column), 16 loads in flight.  MASK is 0 or 2.
+template <bool NORM, int MASK>
+__global__ __launch_bounds__(BLOCK) void rowbn_slot_mean_kernel(
+    const float *__restrict__ x, const float *__restrict__ scale, const float *__restrict__ shift, int n_slots, int R,
+    int C4, float *__restrict__ feat, const float *__restrict__ mask) {
+    const long long total4 = (long long)R * C4;
+    const float inv = slot_mean_scale(n_slots);
+    const float4v zero4 = {0, 0, 0, 0};
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total4;
+         i += (long long)gridDim.x * BLOCK) {
+        const int c4 = (int)(i % C4);
+        const long long roi = i / C4;
+        float4v acc = zero4;
+        if (!(MASK && mask[roi] == 0.0f)) {
+            float4v sc = zero4, sh = zero4;
+            if (NORM) {
+                sc = reinterpret_cast<const float4v *>(scale)[c4];
+                sh = reinterpret_cast<const float4v *>(shift)[c4];
+            }
+            for (int s0 = 0; s0 < n_slots; s0 += SLOT_CHUNK) {
+                float4v v[SLOT_CHUNK];
+                // a place past the last slot re-reads the last slot's row (no branch per load) and is set to +0
+#pragma unroll
+                for (int k = 0; k < SLOT_CHUNK; ++k) {
+                    const int slot = s0 + k < n_slots ? s0 + k : n_slots - 1;
+                    v[k] = reinterpret_cast<const float4v *>(x)[((size_t)slot * R + roi) * C4 + c4];
+                }
+#pragma unroll
+                for (int k = 0; k < SLOT_CHUNK; ++k)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float t = NORM ? bn_affine_relu(v[k][j], sc[j], sh[j]) : v[k][j];
+                        v[k][j] = s0 + k < n_slots ? t : 0.0f;
+                    }
+                const float4v cs = slot_chunk_sum(v);
+                acc = s0 == 0 ? cs : acc + cs;
+            }
+            acc = acc * inv;
+        }
+        reinterpret_cast<float4v *>(feat)[i] = acc;
     }
 }
 
@@ -417,7 +531,7 @@ __global__ __launch_bounds__(BLOCK) void rowbn_apply_bwd_kernel(
             continue;
         }
         const float4v a = reinterpret_cast<const float4v *>(x)[i];
-        const float4v g = ENTRY ? load_dy<true>(dy, eg, i / C4, C, c4) : reinterpret_cast<const float4v *>(dy)[i];
+        const float4v g = ENTRY ? load_dy<DY_ENTRY>(dy, eg, i / C4, C, c4) : reinterpret_cast<const float4v *>(dy)[i];
         const float4v ka = reinterpret_cast<const float4v *>(coef)[c4];
         const float4v k0 = reinterpret_cast<const float4v *>(coef + C)[c4];
         const float4v k1 = reinterpret_cast<const float4v *>(coef + 2 * C)[c4];
@@ -524,12 +638,14 @@ __global__ __launch_bounds__(BLOCK) void rowbn_join_fwd_kernel(
 // coefficients in coef, u = dy masked by the recomputed ReLU of xo*scn + shn; zero on dead rows) plus, with
 // RES, the gradient arriving over the residual path -- and the partials bn3's backward takes over it:
 // partial3 = (sum g, sum g*x3) and, with DUAL, partials = (sum g, sum g*xs), live rows only.
-template <bool DUAL, bool RES>
+// SRC = DY_EXIT: dy is the head's exit gradient, formed from dfeat (the last join of the head; it has no dres).
+template <bool DUAL, bool RES, DySrc SRC>
 struct JoinBwdCols {
     static constexpr bool VISITS_DEAD = true, TWO_Q = DUAL;
     const float *xo, *dy, *scn, *shn, *coef, *dres, *x3, *xs;
     float *g;
     int C;
+    EntryGrad eg;
     float4v sc, sh, ka, k0, k1;
     struct Row {
         float4v x, d, e, a, b;
@@ -542,8 +658,10 @@ struct JoinBwdCols {
         k1 = reinterpret_cast<const float4v *>(coef + 2 * C)[c4];
     }
     __device__ __forceinline__ Row load(long long r, int c4, bool live) const {
-        return {load4(xo, r, C, c4, live), load4(dy, r, C, c4, live), load4(dres, r, C, c4, RES),
-                load4(x3, r, C, c4, live), load4(xs, r, C, c4, DUAL && live)};
+        const float4v a = load4(xo, r, C, c4, live);
+        const float4v d = SRC == DY_PLAIN ? load4(dy, r, C, c4, live) : load_dy<SRC>(dy, eg, r, C, c4, live);
+        return {a, d, load4(dres, r, C, c4, RES), load4(x3, r, C, c4, live),
+                load4(xs, r, C, c4, DUAL && live)};
     }
     __device__ __forceinline__ Term finish(const Row &w, long long r, int c4, bool live) const {
         float4v o;
@@ -559,16 +677,16 @@ struct JoinBwdCols {
     }
 };
 
-template <bool DUAL, bool RES, int MASK>
+template <bool DUAL, bool RES, int MASK, DySrc SRC = DY_PLAIN>
 __global__ __launch_bounds__(BLOCK) void rowbn_join_bwd_kernel(
     const float *__restrict__ xo, const float *__restrict__ dy, const float *__restrict__ scn,
     const float *__restrict__ shn, const float *__restrict__ coef, const float *__restrict__ dres,
     const float *__restrict__ x3, const float *__restrict__ xs, long long M, int C, long long rows_per_block,
     float *__restrict__ g, double *__restrict__ partial3, double *__restrict__ partials,
-    const float *__restrict__ mask, int div) {
+    const float *__restrict__ mask, int div, EntryGrad eg = EntryGrad()) {
     __shared__ double red[BLOCK][8];
     const Slab b(M, C, rows_per_block);
-    JoinBwdCols<DUAL, RES> f = {xo, dy, scn, shn, coef, dres, x3, xs, g, C};
+    JoinBwdCols<DUAL, RES, SRC> f = {xo, dy, scn, shn, coef, dres, x3, xs, g, C, eg};
     slab_walk<MASK>(b, C, mask, div, f, red, partial3 + (size_t)blockIdx.x * 2 * C,
                     DUAL ? partials + (size_t)blockIdx.x * 2 * C : nullptr);
 }
@@ -696,13 +814,19 @@ inline void launch_sums(const Geom &g, const float *x, double *partial) {
     });
 }
 
-// column sums of g and g*x (MODE 1), dy given in two parts with eg
+// column sums of g and g*x (MODE 1); with eg, dy is given in the two parts of the entry gradient or, with `exit`, as
+// the head's dfeat (relu in both)
 inline void launch_grad_sums(const Geom &g, const float *x, const float *dy, const float *scale, const float *shift,
-                             bool relu, const EntryGrad *eg, double *partial) {
-    if (eg)
+                             bool relu, const EntryGrad *eg, double *partial, bool exit = false) {
+    if (eg && exit)
+        pick<0, 2>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_partial_kernel<1, true, MASK, DY_EXIT>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, dy,
+                               scale, shift, g.M, g.C, g.rpb, partial, g.mask, g.div, *eg);
+        });
+    else if (eg)
         pick<0, 1>(g.mode, [&](auto MASK) {
-            hipLaunchKernelGGL((rowbn_partial_kernel<1, true, MASK, true>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, dy, scale,
-                               shift, g.M, g.C, g.rpb, partial, g.mask, g.div, *eg);
+            hipLaunchKernelGGL((rowbn_partial_kernel<1, true, MASK, DY_ENTRY>), dim3(g.nb), dim3(BLOCK), 0, g.st, x, dy,
+                               scale, shift, g.M, g.C, g.rpb, partial, g.mask, g.div, *eg);
         });
     else
         pick<false, true>(relu, [&](auto RELU) {
@@ -735,7 +859,16 @@ inline void launch_bwd_finish(const Geom &g, const double *partial, const float 
                        g.st, partial, g.nb, g.C, g.M, weight, mean, rstd, dweight, dbias, coef, g.mask, g.n_rois, g.per);
 }
 
-inline void launch_apply_fwd(const Geom &g, const float *x, const float *scale, const float *shift, bool relu, float *y) {
+// er: block 1's entry form (relu, roi-major rows): the sampled rows go to er->ys as well
+inline void launch_apply_fwd(const Geom &g, const float *x, const float *scale, const float *shift, bool relu, float *y,
+                             const EntryRows *er = nullptr) {
+    if (er) {
+        pick<0, 1>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_apply_fwd_kernel<true, MASK, true>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st,
+                               x, scale, shift, g.total4, g.C / 4, y, g.mask, g.div, *er);
+        });
+        return;
+    }
     pick<false, true>(relu, [&](auto RELU) {
         pick<0, 1, 2>(g.mode, [&](auto MASK) {
             hipLaunchKernelGGL((rowbn_apply_fwd_kernel<RELU, MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x,
@@ -758,6 +891,18 @@ inline void launch_apply_bwd(const Geom &g, const float *x, const float *dy, con
                                    x, dy, scale, shift, coef, g.total4, g.C / 4, dx, g.mask, g.div);
             });
         });
+}
+
+// feat [R, C] = the mean over the slots of x [n_slots * R, C], of relu(x*scale + shift) when scale is given; mask [R]
+// or null
+inline void launch_slot_mean(hipStream_t st, const float *x, const float *scale, const float *shift, int n_slots, int R,
+                             int C, const float *mask, float *feat) {
+    pick<false, true>(scale != nullptr, [&](auto NORM) {
+        pick<false, true>(mask != nullptr, [&](auto MASKED) {
+            hipLaunchKernelGGL((rowbn_slot_mean_kernel<NORM, MASKED ? 2 : 0>), dim3(apply_grid((long long)R * (C / 4))),
+                               dim3(BLOCK), 0, st, x, scale, shift, n_slots, R, C / 4, feat, mask);
+        });
+    });
 }
 
 inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
@@ -817,6 +962,37 @@ PLUMB_API int wsplumb_rowbn_stats(const float *x, long long M, int C, const floa
     return launched();
 }
 
+// wsplumb_rowbn_forward with ReLU for block 1's pre-activation norm (roi-major rows, n_rois groups of `per`; mask may
+// be null): besides y it writes ys [n_slots * n_rois, C], the position-major rows of the positions the projection
+// shortcut samples -- ys[possel[p] * n_rois + roi] = y[roi * per + p] for the p with possel[p] >= 0, possel [per]
+// (device) being the table of wsplumb_rowbn_backward_entry, every slot 0 .. n_slots - 1 named by exactly one position.
+// ys is a copy made in the apply pass, bit-identical to selecting the rows from y.
+PLUMB_API int wsplumb_rowbn_forward_entry(const float *x, long long M, int C, const float *weight, const float *bias,
+                                          float eps, const float *mask, int n_rois, int per, const int *possel,
+                                          int n_slots, float *y, float *ys, float *mean, float *var, float *rstd,
+                                          float *scale, float *shift, float *count, void *workspace,
+                                          size_t workspace_bytes, void *stream, float *running_mean,
+                                          float *running_var, float momentum, long long *num_batches_tracked) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, false, true,
+                  (!mask || count) && ys && possel && n_slots >= 1 && n_slots <= per, workspace, workspace_bytes, 1, stream))
+        return 1;
+    launch_sums(g, x, g.p0);
+    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
+                      Running{running_mean, running_var, momentum, num_batches_tracked});
+    const EntryRows er = {ys, possel, per, n_rois};
+    launch_apply_fwd(g, x, scale, shift, true, y, &er);
+    return launched();
+}
+
+// feat [R, C] = the mean over the slots of the position-major rows x [n_slots * R, C] (row slot * R + roi), in the one
+// order of bn_math.hip.h that the exit form of wsplumb_rowbn_join_forward uses as well.
+PLUMB_API int wsplumb_slot_mean(const float *x, int n_slots, int R, int C, float *feat, void *stream) {
+    if (n_slots < 1 || R < 1 || C < 4 || (C & 3) || (long long)n_slots * R > 0x7fffffffLL) return 1;
+    launch_slot_mean(static_cast<hipStream_t>(stream), x, nullptr, nullptr, n_slots, R, C, nullptr, feat);
+    return launched();
+}
+
 // y = act(x*scale + shift) with given per-column scale / shift (inference statistics)
 PLUMB_API int wsplumb_rowbn_apply(const float *x, long long M, int C, const float *scale,
                                   const float *shift, int relu, float *y, void *stream) {
@@ -853,36 +1029,29 @@ PLUMB_API int wsplumb_rowbn_backward_entry(const float *x, const float *dy, cons
     if (make_geom(g, M, C, mask, n_rois, per, false, true, dys && possel && n_slots >= 1 && n_slots <= per, workspace,
                   workspace_bytes, 1, stream))
         return 1;
-    const EntryGrad eg = {dys, possel, per, n_rois};
+    const EntryGrad eg = {dys, possel, per, n_rois, 0.0f};
     return backward_impl(g, x, dy, &eg, weight, mean, rstd, scale, shift, true, dx, dweight, dbias, coef);
 }
 
 // ---- residual joins (position-major rows; mask may be null: every row live) ----
 // Statistic blocks are [5, C] f32: mean, var, rstd, scale, shift (the layout of the Python binding).
 
-// out = bn3(x3) + other, y = relu(bn_n(out)), all in training mode over the live rows:
-//   other is the identity shortcut when weight_s is null, else the input xs of the shortcut's own norm
-//   (out = bn3(x3) + bn_s(xs); stats_s is written only then);
-//   stats3 / stats_s / stats_n [5, C] and count [1] are what wsplumb_rowbn_forward (pos_major) writes for the
-//   three layers (count: once, they share the mask; untouched without a mask);
-//   running [6] / momentum [3] / batches [3] (host arrays, or null): the running_mean, running_var pointers, the
-//   momentum and the num_batches_tracked pointer of bn3, bn_s, bn_n in that order (struct Running), each
-//   updated once, by the finish kernel that writes the layer's statistics.
-// Dead rows: out = other (identity form) or 0, y = 0.  Bit-identical to the three (four) separate calls and
-// the add between them.
-PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, long long M, int C,
-                                         const float *weight3, const float *bias3, float eps3,
-                                         const float *weight_s, const float *bias_s, float eps_s,
-                                         const float *weight_n, const float *bias_n, float eps_n,
-                                         const float *mask, int n_rois, int per, float *out, float *y,
-                                         float *stats3, float *stats_s, float *stats_n, float *count,
-                                         void *workspace, size_t workspace_bytes, void *stream,
-                                         float *const *running, const float *momentum,
-                                         long long *const *batches) {
+namespace {
+
+// exit_slots = 0: y [M, C] is written.  exit_slots = n_slots > 0 (the head's exit): y is feat [M / n_slots, C], the
+// mean over the slots of what y would hold, which is then never written.
+int join_forward_impl(const float *x3, const float *other, long long M, int C, const float *weight3, const float *bias3,
+                      float eps3, const float *weight_s, const float *bias_s, float eps_s, const float *weight_n,
+                      const float *bias_n, float eps_n, const float *mask, int n_rois, int per, float *out, float *y,
+                      float *stats3, float *stats_s, float *stats_n, float *count, void *workspace,
+                      size_t workspace_bytes, void *stream, float *const *running, const float *momentum,
+                      long long *const *batches, int exit_slots) {
     const bool dual = weight_s != nullptr;
     Geom g;
-    if (make_geom(g, M, C, mask, n_rois, per, mask != nullptr, false, (!mask || count) && (!dual || (bias_s && stats_s)),
-                  workspace, workspace_bytes, 2, stream))
+    const bool exit_ok = exit_slots == 0 || (exit_slots > 0 && M % exit_slots == 0 && M <= 0x7fffffffLL &&
+                                             (!mask || (per == exit_slots && (long long)n_rois * per == M)));
+    if (make_geom(g, M, C, mask, n_rois, per, mask != nullptr, false,
+                  exit_ok && (!mask || count) && (!dual || (bias_s && stats_s)), workspace, workspace_bytes, 2, stream))
         return 1;
     Running run[3] = {};
     for (int k = 0; k < 3; ++k) {
@@ -904,9 +1073,112 @@ PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, lo
         });
     });
     launch_fwd_finish(g, g.p0, weight_n, bias_n, eps_n, stats_n, count, run[2]);
-    launch_apply_fwd(g, out, stats_n + 3 * C, stats_n + 4 * C, true, y);
+    if (exit_slots)
+        launch_slot_mean(g.st, out, stats_n + 3 * C, stats_n + 4 * C, exit_slots, (int)(M / exit_slots), C, mask, y);
+    else
+        launch_apply_fwd(g, out, stats_n + 3 * C, stats_n + 4 * C, true, y);
     return launched();
 }
+
+}  // namespace
+
+// out = bn3(x3) + other, y = relu(bn_n(out)), all in training mode over the live rows:
+//   other is the identity shortcut when weight_s is null, else the input xs of the shortcut's own norm
+//   (out = bn3(x3) + bn_s(xs); stats_s is written only then);
+//   stats3 / stats_s / stats_n [5, C] and count [1] are what wsplumb_rowbn_forward (pos_major) writes for the
+//   three layers (count: once, they share the mask; untouched without a mask);
+//   running [6] / momentum [3] / batches [3] (host arrays, or null): the running_mean, running_var pointers, the
+//   momentum and the num_batches_tracked pointer of bn3, bn_s, bn_n in that order (struct Running), each
+//   updated once, by the finish kernel that writes the layer's statistics.
+// Dead rows: out = other (identity form) or 0, y = 0.  Bit-identical to the three (four) separate calls and
+// the add between them.
+PLUMB_API int wsplumb_rowbn_join_forward(const float *x3, const float *other, long long M, int C,
+                                         const float *weight3, const float *bias3, float eps3,
+                                         const float *weight_s, const float *bias_s, float eps_s,
+                                         const float *weight_n, const float *bias_n, float eps_n,
+                                         const float *mask, int n_rois, int per, float *out, float *y,
+                                         float *stats3, float *stats_s, float *stats_n, float *count,
+                                         void *workspace, size_t workspace_bytes, void *stream,
+                                         float *const *running, const float *momentum,
+                                         long long *const *batches) {
+    return join_forward_impl(x3, other, M, C, weight3, bias3, eps3, weight_s, bias_s, eps_s, weight_n, bias_n, eps_n, mask,
+                             n_rois, per, out, y, stats3, stats_s, stats_n, count, workspace, workspace_bytes, stream,
+                             running, momentum, batches, 0);
+}
+
+// The exit form of wsplumb_rowbn_join_forward, for the last join of the head, whose y = relu(bn_n(out)) is only ever
+// averaged over the n_slots positions of each RoI (M = n_slots * R rows, row slot * R + roi; with a mask n_rois = R and
+// per = n_slots): instead of y it writes feat [R, C], feat[roi] = mean over the slots of y[slot * R + roi] in the order
+// of bn_math.hip.h (wsplumb_slot_mean of the y the plain form writes, bit for bit), zero for a dead RoI.  Everything
+// else as the plain form.
+PLUMB_API int wsplumb_rowbn_join_forward_exit(const float *x3, const float *other, long long M, int C,
+                                              const float *weight3, const float *bias3, float eps3,
+                                              const float *weight_s, const float *bias_s, float eps_s,
+                                              const float *weight_n, const float *bias_n, float eps_n,
+                                              const float *mask, int n_rois, int per, float *out, float *feat,
+                                              float *stats3, float *stats_s, float *stats_n, float *count,
+                                              void *workspace, size_t workspace_bytes, void *stream,
+                                              float *const *running, const float *momentum,
+                                              long long *const *batches, int n_slots) {
+    if (n_slots < 1) return 1;
+    return join_forward_impl(x3, other, M, C, weight3, bias3, eps3, weight_s, bias_s, eps_s, weight_n, bias_n, eps_n, mask,
+                             n_rois, per, out, feat, stats3, stats_s, stats_n, count, workspace, workspace_bytes, stream,
+                             running, momentum, batches, n_slots);
+}
+
+namespace {
+
+// exit_slots = n_slots > 0: dy is dfeat [M / n_slots, C] of the forward's exit form, and there is no dres
+int join_backward_impl(const float *out, const float *dy, const float *dres, const float *x3, const float *xs, long long M,
+                       int C, const float *weight_n, const float *stats_n, const float *weight3, const float *stats3,
+                       const float *weight_s, const float *stats_s, const float *mask, int n_rois, int per, float *gout,
+                       float *dx3, float *dxs, float *dwb_n, float *dwb3, float *dwb_s, float *coef, void *workspace,
+                       size_t workspace_bytes, void *stream, int exit_slots) {
+    const bool dual = xs != nullptr;
+    Geom g;
+    const bool exit_ok = exit_slots == 0 || (exit_slots > 0 && !dres && M % exit_slots == 0 && M <= 0x7fffffffLL &&
+                                             (!mask || (per == exit_slots && (long long)n_rois * per == M)));
+    if (make_geom(g, M, C, mask, n_rois, per, mask != nullptr, false,
+                  exit_ok && (!dual || (weight_s && stats_s && dxs && dwb_s)), workspace, workspace_bytes, 2, stream))
+        return 1;
+    float *coef_n = coef, *coef3 = coef + 3 * C, *coefs = coef + 6 * C;
+    const float *scn = stats_n + 3 * C, *shn = stats_n + 4 * C;
+    if (exit_slots) {
+        const EntryGrad eg = {nullptr, nullptr, exit_slots, (int)(M / exit_slots), slot_mean_scale(exit_slots)};
+        launch_grad_sums(g, out, dy, scn, shn, true, &eg, g.p0, true);
+        launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n);
+        pick<false, true>(dual, [&](auto DUAL) {
+            pick<0, 2>(g.mode, [&](auto MASK) {
+                hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, false, MASK, DY_EXIT>), dim3(g.nb), dim3(BLOCK), 0, g.st, out,
+                                   dy, scn, shn, coef_n, nullptr, x3, xs, M, C, g.rpb, gout, g.p0, g.p1, mask, g.div, eg);
+            });
+        });
+    } else {
+        launch_grad_sums(g, out, dy, scn, shn, true, nullptr, g.p0);
+        launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n);
+        pick<false, true>(dual, [&](auto DUAL) {
+            pick<false, true>(dres != nullptr, [&](auto RES) {
+                pick<0, 2>(g.mode, [&](auto MASK) {
+                    hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, RES, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy,
+                                       scn, shn, coef_n, dres, x3, xs, M, C, g.rpb, gout, g.p0, g.p1, mask, g.div);
+                });
+            });
+        });
+    }
+    launch_bwd_finish(g, g.p0, weight3, stats3, stats3 + 2 * C, dwb3, dwb3 + C, coef3);
+    if (dual) {
+        launch_bwd_finish(g, g.p1, weight_s, stats_s, stats_s + 2 * C, dwb_s, dwb_s + C, coefs);
+        pick<0, 2>(g.mode, [&](auto MASK) {
+            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
+                               gout, coef3, coefs, g.total4, C / 4, dx3, dxs, mask, g.div);
+        });
+    } else {
+        launch_apply_bwd(g, x3, gout, nullptr, nullptr, coef3, false, nullptr, dx3);
+    }
+    return launched();
+}
+
+}  // namespace
 
 // gradients of wsplumb_rowbn_join_forward: dy is the gradient of y, dres that of out over the residual path
 // (null: none).  g = dx of bn_n + dres is the gradient of `other` in the identity form; dx3 (and dxs, when
@@ -919,32 +1191,23 @@ PLUMB_API int wsplumb_rowbn_join_backward(const float *out, const float *dy, con
                                           int n_rois, int per, float *gout, float *dx3, float *dxs, float *dwb_n,
                                           float *dwb3, float *dwb_s, float *coef, void *workspace,
                                           size_t workspace_bytes, void *stream) {
-    const bool dual = xs != nullptr;
-    Geom g;
-    if (make_geom(g, M, C, mask, n_rois, per, mask != nullptr, false, !dual || (weight_s && stats_s && dxs && dwb_s),
-                  workspace, workspace_bytes, 2, stream))
-        return 1;
-    float *coef_n = coef, *coef3 = coef + 3 * C, *coefs = coef + 6 * C;
-    const float *scn = stats_n + 3 * C, *shn = stats_n + 4 * C;
-    launch_grad_sums(g, out, dy, scn, shn, true, nullptr, g.p0);
-    launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n);
-    pick<false, true>(dual, [&](auto DUAL) {
-        pick<false, true>(dres != nullptr, [&](auto RES) {
-            pick<0, 2>(g.mode, [&](auto MASK) {
-                hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, RES, MASK>), dim3(g.nb), dim3(BLOCK), 0, g.st, out, dy, scn,
-                                   shn, coef_n, dres, x3, xs, M, C, g.rpb, gout, g.p0, g.p1, mask, g.div);
-            });
-        });
-    });
-    launch_bwd_finish(g, g.p0, weight3, stats3, stats3 + 2 * C, dwb3, dwb3 + C, coef3);
-    if (dual) {
-        launch_bwd_finish(g, g.p1, weight_s, stats_s, stats_s + 2 * C, dwb_s, dwb_s + C, coefs);
-        pick<0, 2>(g.mode, [&](auto MASK) {
-            hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
-                               gout, coef3, coefs, g.total4, C / 4, dx3, dxs, mask, g.div);
-        });
-    } else {
-        launch_apply_bwd(g, x3, gout, nullptr, nullptr, coef3, false, nullptr, dx3);
-    }
-    return launched();
+    return join_backward_impl(out, dy, dres, x3, xs, M, C, weight_n, stats_n, weight3, stats3, weight_s, stats_s, mask,
+                              n_rois, per, gout, dx3, dxs, dwb_n, dwb3, dwb_s, coef, workspace, workspace_bytes, stream, 0);
+}
+
+// gradients of wsplumb_rowbn_join_forward_exit: dfeat [M / n_slots, C] is the gradient of feat; the gradient of the y
+// that was never written, dfeat[r % R] * (1 / n_slots), is formed in registers by the two kernels that read it (DY_EXIT).
+// There is no dres.  Everything else as wsplumb_rowbn_join_backward, and bit-identical to it fed with that gradient
+// expanded to [M, C] (1 / n_slots is exact for a power of two, which makes it torch's mean backward as well).
+PLUMB_API int wsplumb_rowbn_join_backward_exit(const float *out, const float *dfeat, int n_slots, const float *x3,
+                                               const float *xs, long long M, int C, const float *weight_n,
+                                               const float *stats_n, const float *weight3, const float *stats3,
+                                               const float *weight_s, const float *stats_s, const float *mask,
+                                               int n_rois, int per, float *gout, float *dx3, float *dxs, float *dwb_n,
+                                               float *dwb3, float *dwb_s, float *coef, void *workspace,
+                                               size_t workspace_bytes, void *stream) {
+    if (n_slots < 1) return 1;
+    return join_backward_impl(out, dfeat, nullptr, x3, xs, M, C, weight_n, stats_n, weight3, stats3, weight_s, stats_s,
+                              mask, n_rois, per, gout, dx3, dxs, dwb_n, dwb3, dwb_s, coef, workspace, workspace_bytes,
+                              stream, n_slots);
 }

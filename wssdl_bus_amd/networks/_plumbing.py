@@ -46,13 +46,23 @@ def lib():
                                              + [_sz, _vp])
         L.wsplumb_rowbn_backward_entry.restype = _i
         L.wsplumb_rowbn_backward_entry.argtypes = [_vp] * 4 + [_i, _ll, _i] + [_vp] * 6 + [_i, _i] + [_vp] * 5 + [_sz, _vp]
+        L.wsplumb_rowbn_forward_entry.restype = _i
+        L.wsplumb_rowbn_forward_entry.argtypes = ([_vp, _ll, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _i] + [_vp] * 9
+                                                  + [_sz, _vp] + _RUN)
+        L.wsplumb_slot_mean.restype = _i
+        L.wsplumb_slot_mean.argtypes = [_vp, _i, _i, _i, _vp, _vp]
         L.wsplumb_rowbn_join_workspace_bytes.restype = _sz
         L.wsplumb_rowbn_join_workspace_bytes.argtypes = [_ll, _i]
         L.wsplumb_rowbn_join_forward.restype = _i
         L.wsplumb_rowbn_join_forward.argtypes = [_vp, _vp, _ll, _i, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _f, _vp, _i, _i,
                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]
+        L.wsplumb_rowbn_join_forward_exit.restype = _i
+        L.wsplumb_rowbn_join_forward_exit.argtypes = L.wsplumb_rowbn_join_forward.argtypes + [_i]
         L.wsplumb_rowbn_join_backward.restype = _i
         L.wsplumb_rowbn_join_backward.argtypes = [_vp] * 5 + [_ll, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 8 + [_sz, _vp]
+        L.wsplumb_rowbn_join_backward_exit.restype = _i
+        L.wsplumb_rowbn_join_backward_exit.argtypes = ([_vp, _vp, _i, _vp, _vp, _ll, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 8
+                                                       + [_sz, _vp])
         L.wsplumb_tap_table_ints.restype = _i
         L.wsplumb_tap_table_ints.argtypes = []
         for name in ("wsplumb_tap_gather", "wsplumb_tap_col2im"):
@@ -84,7 +94,10 @@ def lib():
 SWITCHES = {
     "WSSDL_DISABLE_FUSED_BN": "no row batch-norm kernel at all: stock PyTorch ops (usable)",
     "WSSDL_BN_TORCH_RUNNING_STATS": "running statistics by torch's lerp_, not the finish kernels (fused_running_stats)",
-    "WSSDL_HEAD_UNFUSED_ENTRY": "block 1's entry: torch's scatter and add, then the plain backward (entry_usable)",
+    "WSSDL_HEAD_UNFUSED_ENTRY": "block 1's entry: torch's index_select forward, scatter and add, then the plain "
+                                "backward (entry_usable)",
+    "WSSDL_HEAD_UNFUSED_EXIT": "the head's exit: the last join writes y, the slot-mean kernel reads it back, the mean's "
+                               "gradient is expanded in memory (exit_usable)",
     "WSSDL_HEAD_UNFUSED_JOIN": "the head's residual joins: separate norms and a torch add (join_usable)",
     "WSSDL_TRUNK_UNFUSED_JOIN": "the trunk's residual joins: separate layers (backbones._join)",
     "WSSDL_DISABLE_FUSED_IM2COL": "3x3 patches by pad / unfold, not the patch kernels (im2col_usable)",
@@ -235,6 +248,27 @@ def entry_usable(x):
     return not switch("WSSDL_HEAD_UNFUSED_ENTRY") and usable(x) and x.shape[0] < 2 ** 31
 
 
+def rowbn_forward_entry(x, weight, bias, eps, possel, n_slots, mask=None, *, running=None):
+    """rowbn_forward(relu=True) of roi-major rows x [R * per, C] that also hands out, position-major, the rows of the
+    positions possel names (int32 [per] on the device: the slot of each position or -1; every slot 0 .. n_slots - 1
+    exactly once): returns (y, ys [n_slots * R, C], stats, count) with ys[possel[p] * R + roi] = y[roi * per + p],
+    written by the apply pass itself."""
+    M, C = x.shape
+    per = possel.shape[0]
+    n_rois = M // per
+    assert M == n_rois * per and possel.dtype == torch.int32 and possel.is_contiguous() and 1 <= n_slots <= per
+    assert mask is None or mask.shape[0] == n_rois
+    y = torch.empty_like(x)
+    ys = torch.empty((n_slots * n_rois, C), dtype=torch.float32, device=x.device)
+    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)
+    count = torch.empty((1,), dtype=torch.float32, device=x.device) if mask is not None else None
+    ws = _workspace(x)
+    _call("wsplumb_rowbn_forward_entry", x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), _mask_args(mask, M)[0],
+          n_rois, per, _p(possel), n_slots, _p(y), _p(ys), *[_p(stats[i]) for i in range(5)], _pn(count), _p(ws),
+          ws.numel(), tail=_run_args(running))
+    return y, ys, stats, count
+
+
 def rowbn_backward_entry(x, dy, dys, possel, n_slots, weight, stats, mask=None):
     """rowbn_backward(relu=True) of roi-major rows x [R * per, C] whose output gradient is dy [R * per, C] plus, at the
     positions p with possel[p] = slot >= 0 (int32 [per] on the device), the position-major dys [n_slots * R, C]:
@@ -258,15 +292,38 @@ def join_usable(x):
     return not switch("WSSDL_HEAD_UNFUSED_JOIN") and usable(x)
 
 
-def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
+def exit_usable(x):
+    """True when the last join of the head may take its exit form for this position-major [M, C] tensor."""
+    return not switch("WSSDL_HEAD_UNFUSED_EXIT") and join_usable(x) and x.shape[0] < 2 ** 31
+
+
+def slot_mean(x, n_slots):
+    """[n_slots * R, C] position-major rows -> [R, C]: the mean over the slots in the one order of the exit kernels
+    (csrc/plumbing/bn_math.hip.h), not torch's."""
+    M, C = x.shape
+    R = M // n_slots
+    assert M == R * n_slots and x.is_contiguous() and x.dtype == torch.float32
+    feat = torch.empty((R, C), dtype=torch.float32, device=x.device)
+    _call("wsplumb_slot_mean", x.device, _p(x), n_slots, R, C, _p(feat))
+    return feat
+
+
+def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None, exit_slots=None):
     """out = bn3(x3) + (bns(other) if bns else other); y = relu(bnn(out)): training-mode row batch norms over
     position-major rows, each bn a (weight, bias, eps) triple, mask as in rowbn_forward(pos_major=True).
     Returns (out, y, stats3, stats_s, stats_n, count or None), stats_s unwritten without bns; bit-identical to the
-    separate calls.  running: None, or the running_of() of bn3, bns (None without it) and bnn."""
+    separate calls.  running: None, or the running_of() of bn3, bns (None without it) and bnn.
+    exit_slots = n_slots (the head's exit): y is never written; in its place comes feat [M / n_slots, C] =
+    slot_mean(y, n_slots), bit for bit."""
     M, C = x3.shape
     dev = x3.device
     assert other.shape == x3.shape and other.is_contiguous() and other.dtype == torch.float32
-    out, y = torch.empty_like(x3), torch.empty_like(x3)
+    out = torch.empty_like(x3)
+    if exit_slots:
+        assert M % exit_slots == 0 and (mask is None or mask.shape[0] * exit_slots == M)
+        y = torch.empty((M // exit_slots, C), dtype=torch.float32, device=dev)
+    else:
+        y = torch.empty_like(x3)
     stats = torch.empty((3, 5, C), dtype=torch.float32, device=dev)
     count = torch.empty((1,), dtype=torch.float32, device=dev) if mask is not None else None
     ws_, bs_, es_ = bns if bns is not None else (None, None, 0.0)
@@ -277,25 +334,30 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None):
         run = ((_vp * 6)(*[val(q) for r in a for q in r[:2]]), (_f * 3)(*[r[2] for r in a]),
                (_vp * 3)(*[val(r[3]) for r in a]))
     ws = _workspace(x3, join=True)
-    _call("wsplumb_rowbn_join_forward", dev, _p(x3), _p(other), M, C, _p(bn3[0]), _p(bn3[1]), float(bn3[2]), _pn(ws_),
-          _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]), *_mask_args(mask, M), _p(out), _p(y),
-          _p(stats[0]), _p(stats[1]) if bns is not None else None, _p(stats[2]), _pn(count), _p(ws), ws.numel(),
-          tail=run)
+    _call("wsplumb_rowbn_join_forward_exit" if exit_slots else "wsplumb_rowbn_join_forward", dev, _p(x3), _p(other), M, C,
+          _p(bn3[0]), _p(bn3[1]), float(bn3[2]), _pn(ws_), _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]),
+          *_mask_args(mask, M), _p(out), _p(y), _p(stats[0]), _p(stats[1]) if bns is not None else None, _p(stats[2]),
+          _pn(count), _p(ws), ws.numel(), tail=run + ((int(exit_slots),) if exit_slots else ()))
     return out, y, stats[0], stats[1], stats[2], count
 
 
-def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, stats_s, mask=None):
+def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, stats_s, mask=None, exit_slots=None):
     """Gradients of rowbn_join_forward: dy for y, dres (or None) for out; xs / ws_ / stats_s None in the identity
     form.  Returns (g, dx3, dxs or None, dwb_n, dwb3, dwb_s or None), the dwb [2, C] = (dweight, dbias); g is the
-    gradient of `other` in the identity form."""
+    gradient of `other` in the identity form.  exit_slots = n_slots: dy is the gradient of feat [M / n_slots, C] and
+    dres must be None; bit-identical to the plain form on (dy * (1 / n_slots)) repeated over the slots."""
     M, C = x3.shape
+    if exit_slots:
+        assert dres is None and dy.shape == (M // exit_slots, C) and dy.is_contiguous()
     dual = xs is not None
     g, dx3 = torch.empty_like(x3), torch.empty_like(x3)
     dxs = torch.empty_like(x3) if dual else None
     dwb = torch.empty((3, 2, C), dtype=torch.float32, device=x3.device)
     coef = torch.empty((9, C), dtype=torch.float32, device=x3.device)
     ws = _workspace(x3, join=True)
-    _call("wsplumb_rowbn_join_backward", x3.device, _p(out), _p(dy), _pn(dres), _p(x3), _pn(xs), M, C, _p(wn),
+    name, third = ("wsplumb_rowbn_join_backward_exit", int(exit_slots)) if exit_slots else \
+        ("wsplumb_rowbn_join_backward", _pn(dres))
+    _call(name, x3.device, _p(out), _p(dy), third, _p(x3), _pn(xs), M, C, _p(wn),
           _p(stats_n), _p(w3), _p(stats3), _pn(ws_), _pn(stats_s), *_mask_args(mask, M), _p(g), _p(dx3), _pn(dxs),
           _p(dwb[0]), _p(dwb[1]), _p(dwb[2]) if dual else None, _p(coef), _p(ws), ws.numel())
     return g, dx3, dxs, dwb[0], dwb[1], dwb[2] if dual else None

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from . import _plumbing, rownorm
 from .backbones import RESNET_DEFS, _convs, _init_block, _preact, _same_pad, _walk, layer_group
 from .rownorm import (RowBatchNorm, _EntryNormFn, _FusedRowBatchNormFn, _JoinFn, _RowBatchNormFn,  # noqa: F401
-                      _pm_rows, set_roi_mask)
+                      _SlotMeanFn, _pm_rows, set_roi_mask)
 
 
 class ConvNHWC(nn.Module):
@@ -108,10 +108,11 @@ class _BlockNHWC(nn.Module):
             x = conv(x)
         return x + (self.short(ori) if self.short is not None else ori)
 
-    def forward_pm(self, x, plans, R, pre=None, nxt=None):
+    def forward_pm(self, x, plans, R, pre=None, nxt=None, exit=None):
         """forward on the position-major route: x roi-major [R, 7, 7, C] (first block) or position-major rows;
         plans: {stride: TapPlan}; pre: this block's pre-activation when the previous block's join computed it;
-        nxt: the norm (+ReLU) that follows this block.  Returns (position-major rows, nxt's output or None)."""
+        nxt: the norm (+ReLU) that follows this block; exit: the head's _Exit when this is its last block and nxt its
+        final norm.  Returns (position-major rows, nxt's output or None) -- _join_pm."""
         s = self.stride
         if self._entry_fused(x, pre):
             x, ori = _entry_pre_act(self.pre_bn, x, plans[s], s)   # ori: the shortcut's rows, already position-major
@@ -124,7 +125,7 @@ class _BlockNHWC(nn.Module):
             # a 1x1 ahead of the strided convolution keeps a roi-major map roi-major (the bottleneck's conv1 on 7x7)
             x = conv(x) if (conv.k == 1 and x.dim() == 4) else conv.forward_pm(x, plans[conv.s], R)
         x = last.forward_pm(x, plans[last.s], R, act=False)
-        return _join_pm(last, x, self.short, ori, plans[s], s, R, nxt)
+        return _join_pm(last, x, self.short, ori, plans[s], s, R, nxt, exit)
 
     @staticmethod
     def _tapnorm_fused(body, x):
@@ -173,11 +174,22 @@ class BasicBlockNHWC(_BlockNHWC):
     expansion, chain = 1, ((3, True), (3, False))
 
 
-def _join_pm(last, x3, short, ori, plan, s, R, nxt):
+class _Exit:
+    """The head's exit as its last block sees it: `n_slots` positions per RoI, and `taken`, set by the block's join
+    when it returned the mean over the slots in place of the final norm's output (_JoinFn's exit form)."""
+
+    def __init__(self, n_slots):
+        self.n_slots, self.taken = n_slots, False
+
+
+def _join_pm(last, x3, short, ori, plan, s, R, nxt, exit=None):
     """The end of a block (stride s) on the position-major route: act(x3) + shortcut, x3 the raw output of the
     block's last convolution `last`.  Returns (out, relu(nxt(out))) from the join kernels (rownorm.join_rows) under
     rownorm.join_norms' conditions when, besides, the kernels take x3 and the live-row mask fits its rows -- with or
-    without autograd; else (out, None) from the separate layers (also with WSSDL_HEAD_UNFUSED_JOIN=1)."""
+    without autograd; else (out, None) from the separate layers (also with WSSDL_HEAD_UNFUSED_JOIN=1).
+    With `exit` (the head's last block, nxt its final norm) the join takes its exit form unless
+    WSSDL_HEAD_UNFUSED_EXIT=1 or the mask is not one entry per RoI: the second result is then the head's output
+    [R, C], the mean of relu(nxt(out)) over the slots, and exit.taken is set."""
     if short is not None:
         xs = short.forward_pm(ori, plan, R, act=False)
     else:
@@ -186,6 +198,9 @@ def _join_pm(last, x3, short, ori, plan, s, R, nxt):
     mask, fits = rownorm.live_mask(x3.shape[0])
     if bns is None or not _plumbing.join_usable(x3) or not fits:
         return last._act(x3, pos_major=True) + (short._act(xs, pos_major=True) if short is not None else xs), None
+    if exit is not None and _plumbing.exit_usable(x3) and (mask is None or mask.shape[0] == R):
+        exit.taken = True
+        return rownorm.join_rows(*bns, x3, xs.contiguous(), mask, exit.n_slots)
     return rownorm.join_rows(*bns, x3, xs.contiguous(), mask)
 
 
@@ -234,8 +249,16 @@ class ResNetHeadNHWC(nn.Module):
     def _forward_pm(self, x, plans):
         """The 4x4 section in POSITION-MAJOR rows (row = slot * R + roi, slots ordered centre | edges |
         corners by _plumbing.TapPlan): each 3x3 class GEMM writes its own contiguous slab; batch norm,
-        1x1 convolutions and residual adds do not care about row order, the final mean reduces over slots."""
+        1x1 convolutions and residual adds do not care about row order, the final mean reduces over slots -- inside
+        the last block's join (its exit form), else by the slot-mean kernel over the final norm's output: one order
+        of additions (csrc/plumbing/bn_math.hip.h) on every position-major route, so that they agree bit for bit."""
         R = x.shape[0]
-        y = _walk(list(self.group3), x, self.norm, _norm_relu,
-                  lambda blk, x, pre, nxt: blk.forward_pm(x, plans, R, pre, nxt))
-        return y.view(-1, R, y.shape[1]).mean(dim=0)
+        blocks = list(self.group3)
+        exit = _Exit(len(plans[1].slots))
+
+        def step(blk, x, pre, nxt):
+            last = self.norm is not None and nxt is self.norm and blk is blocks[-1]
+            return blk.forward_pm(x, plans, R, pre, nxt, exit if last else None)
+
+        y = _walk(blocks, x, self.norm, _norm_relu, step)
+        return y if exit.taken else _SlotMeanFn.apply(y, exit.n_slots)

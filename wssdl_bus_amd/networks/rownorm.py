@@ -88,26 +88,57 @@ class _JoinFn(torch.autograd.Function):
     bn3 (and bn_s), add and take bn_n's statistics in one pass over the tensors, and in the backward form
     g = bn_n's dx + the residual gradient together with the sums bn3's (bn_s's) backward takes over it; results
     are bit-identical to the separate layers and torch's adds.  Returns out, y, the three [5, C] statistic
-    blocks (stats_s is not written in the identity form) and the live-row count."""
+    blocks (stats_s is not written in the identity form) and the live-row count.
+
+    With exit_slots = n_slots -- the last join of the head, whose y is only ever averaged over the n_slots positions
+    of each RoI -- the second output is instead feat [M / n_slots, C] = slot_mean(y): one kernel reads out once and
+    y is never written; the backward takes feat's gradient and the kernels form y's, dfeat[r % R] * (1 / n_slots), in
+    registers.  Bit-identical to the plain form followed by _SlotMeanFn."""
 
     @staticmethod
-    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask, running=None):
+    def forward(ctx, x3, other, w3, b3, ws, bs, wn, bn, eps3, eps_s, eps_n, roi_mask, running=None, exit_slots=None):
         dual = ws is not None
         out, y, st3, sts, stn, count = _plumbing.rowbn_join_forward(
-            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask, running=running)
-        ctx.dual = dual
+            x3, (w3, b3, eps3), other, (ws, bs, eps_s) if dual else None, (wn, bn, eps_n), roi_mask, running=running,
+            exit_slots=exit_slots)
+        ctx.dual, ctx.exit_slots = dual, exit_slots
         ctx.save_for_backward(x3, other if dual else None, out, w3, ws, wn, st3, sts, stn, roi_mask)
         return out, y, st3, sts, stn, _side_outputs(ctx, count, stn, st3, sts, stn)
 
     @staticmethod
     def backward(ctx, dres, dy, *_):
         x3, xs, out, w3, ws, wn, st3, sts, stn, roi_mask = ctx.saved_tensors
+        n = ctx.exit_slots
+        if n and dy is None:
+            dy = out.new_zeros((out.shape[0] // n, out.shape[1]))
+        if n and dres is not None:               # a gradient for `out` as well: y's gradient in memory, the plain form
+            dy, n = _slot_mean_grad(dy, n), None
         g, dx3, dxs, dwbn, dwb3, dwbs = _plumbing.rowbn_join_backward(
-            out, _grad(dy, out), dres.contiguous() if dres is not None else None, x3, xs, wn, stn, w3, st3, ws, sts,
-            roi_mask)
+            out, dy.contiguous() if n else _grad(dy, out), dres.contiguous() if dres is not None else None, x3, xs, wn,
+            stn, w3, st3, ws, sts, roi_mask, exit_slots=n)
         if ctx.dual:
-            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None, None
-        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None, None
+            return dx3, dxs, dwb3[0], dwb3[1], dwbs[0], dwbs[1], dwbn[0], dwbn[1], None, None, None, None, None, None
+        return dx3, g, dwb3[0], dwb3[1], None, None, dwbn[0], dwbn[1], None, None, None, None, None, None
+
+
+def _slot_mean_grad(dfeat, n_slots):
+    """The gradient of the rows a slot mean was taken over: dfeat * (1 / n_slots) for every slot, [n_slots * R, C]."""
+    return (dfeat * (1.0 / n_slots)).unsqueeze(0).expand(n_slots, *dfeat.shape).reshape(-1, dfeat.shape[1])
+
+
+class _SlotMeanFn(torch.autograd.Function):
+    """[n_slots * R, C] position-major rows -> [R, C], the mean over the slots in the order of the exit kernels
+    (_plumbing.slot_mean; csrc/plumbing/bn_math.hip.h): what every position-major route of the head that does not take
+    the last join's exit form ends in, so that all of them produce the same bits."""
+
+    @staticmethod
+    def forward(ctx, y, n_slots):
+        ctx.n_slots = n_slots
+        return _plumbing.slot_mean(y.contiguous(), n_slots)
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        return _slot_mean_grad(dfeat, ctx.n_slots), None
 
 
 def _pm_rows(x, plan, s):
@@ -120,16 +151,16 @@ def _pm_rows(x, plan, s):
 class _EntryNormFn(torch.autograd.Function):
     """Block 1's pre-activation norm + ReLU on the position-major route, with both consumers of its output y in
     one Function: returns y (roi-major rows, for conv1) and the position-major rows of the positions the
-    projection shortcut samples (_pm_rows).  The backward takes the two gradients as they arrive and forms
+    projection shortcut samples (what _pm_rows(y) selects, written by the norm's apply pass while it holds them:
+    rowbn.hip, EntryRows).  The backward takes the two gradients as they arrive and forms
     their sum inside the norm's two backward passes (rowbn.hip, EntryGrad): no zero-fill, index_add, strided
     add or contiguous copy of a [R, 49, C] tensor.  Bit-identical to the separate layers."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps, roi_mask, plan, s, hw, running=None):
-        y, stats, count = _plumbing.rowbn_forward(x, weight, bias, eps, True, roi_mask, False, running=running)
         h, w = hw
-        r = x.shape[0] // (h * w)
-        ys = _pm_rows(y.view(r, h, w, -1), plan, s)
+        y, ys, stats, count = _plumbing.rowbn_forward_entry(x, weight, bias, eps, plan.subsample_slots(h, w, s, x.device),
+                                                            len(plan.slots), roi_mask, running=running)
         ctx.save_for_backward(x, weight, stats, roi_mask)
         ctx.geom = (plan, s, h, w)
         mean, var = stats[0], stats[1]
@@ -225,13 +256,14 @@ def join_norms(last, short, nxt):
     return last.bn, short.bn if short is not None else None, nxt
 
 
-def join_rows(b3, bs, nxt, r3, rs, mask):
+def join_rows(b3, bs, nxt, r3, rs, mask, exit_slots=None):
     """out = b3(r3) + (bs(rs) if bs is not None else rs), y = relu(nxt(out)) over [M, C] row matrices through _JoinFn,
-    running statistics included; returns (out, y)."""
+    running statistics included; returns (out, y) -- with exit_slots (_JoinFn's exit form) (out, the mean of y over
+    the slots)."""
     ws, bias_s, eps_s = (bs.weight, bs.bias, bs.eps) if bs is not None else (None, None, 0.0)
     run, done = running((b3, bs, nxt), mask, r3.shape[0])
     out, y, st3, sts, stn, n = _JoinFn.apply(r3, rs, b3.weight, b3.bias, ws, bias_s, nxt.weight, nxt.bias, b3.eps,
-                                             eps_s, nxt.eps, mask, run)
+                                             eps_s, nxt.eps, mask, run, *((exit_slots,) if exit_slots else ()))
     done((st3, sts, stn), n)
     return out, y
 
