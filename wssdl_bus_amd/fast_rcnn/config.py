@@ -26,6 +26,8 @@ cfg = __C
 __C.TRAIN = AttrDict()
 __C.TRAIN.LEARNING_RATE = 0.0005                    # config.py:40
 __C.TRAIN.WEIGHT_DECAY = 0.0005                     # config.py:46
+__C.TRAIN.GN_MIN_NUM_G = 8                          # :55  group norm: G = min(this, C // GN_MIN_CHS_PER_G)
+__C.TRAIN.GN_MIN_CHS_PER_G = 4                      # :56
 __C.TRAIN.WS_IMS_PER_BATCH = 2                      # :49
 __C.TRAIN.WS_LOSS_USE_ADAPTIVE_SCALE_FACTOR = True  # :51
 __C.TRAIN.WS_LOSS_SCALE_FACTOR = 0.5                # :52

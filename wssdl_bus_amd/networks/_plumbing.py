@@ -1,5 +1,5 @@
 """ctypes binding of ``libwssdl_plumbing_hip.so``: the fused row batch-norm (+ReLU) and residual-join kernels
-(``csrc/plumbing/rowbn.hip``), the 3x3 patch kernels (``im2col.hip``) and the class-packed 3x3 convolutions
+(``csrc/plumbing/rowbn.hip``), the group-norm kernels (``groupnorm.hip``), the 3x3 patch kernels (``im2col.hip``) and the class-packed 3x3 convolutions
 (``taps.hip``) of the two networks, and the one-launch L2 weight decay of the training step (``l2decay.hip``).  Plumbing around the hot path, not the drop-in C ABI; when the library has not
 been built the networks fall back to stock PyTorch ops (slower, same maths) and say so once.  Imports no sibling
 module: networks/rownorm.py, backbones.py and roi_head.py build on it, in that order.  Every export goes through
@@ -79,6 +79,17 @@ def lib():
             f = getattr(L, name)
             f.restype = _i
             f.argtypes = [_vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]
+        L.wsplumb_groupnorm_supported.restype = _i
+        L.wsplumb_groupnorm_supported.argtypes = [_ll, _ll, _i, _i]
+        L.wsplumb_groupnorm_workspace_bytes.restype = _sz
+        L.wsplumb_groupnorm_workspace_bytes.argtypes = [_ll, _ll, _i]
+        L.wsplumb_groupnorm_plan.restype = _i
+        L.wsplumb_groupnorm_plan.argtypes = [_ll, _ll, _i, _vp]
+        L.wsplumb_groupnorm_forward.restype = _i
+        L.wsplumb_groupnorm_forward.argtypes = [_vp, _ll, _ll, _i, _i, _ll, _ll, _vp, _vp, _f, _i] + [_vp] * 5 + [_sz, _vp]
+        L.wsplumb_groupnorm_backward.restype = _i
+        L.wsplumb_groupnorm_backward.argtypes = ([_vp, _vp, _ll, _ll, _i, _i, _ll, _ll] + [_vp] * 4 + [_i] + [_vp] * 5
+                                                 + [_sz, _vp])
         L.wsplumb_l2decay_chunk.restype = _i
         L.wsplumb_l2decay_chunk.argtypes = []
         L.wsplumb_l2decay_forward.restype = _i
@@ -104,6 +115,7 @@ SWITCHES = {
     "WSSDL_HEAD_UNFUSED_TAPNORM": "a bottleneck's conv1 norm as its own layer in front of the 3x3 patch gather "
                                   "(tapnorm_usable)",
     "WSSDL_HEAD_DENSE_3X3": "the head's 3x3 convolutions on the dense patch route (taps_usable)",
+    "WSSDL_DISABLE_FUSED_GN": "no group-norm kernel: stock PyTorch ops (groupnorm_usable)",
     "WSSDL_TORCH_L2_DECAY": "the L2 weight decay by torch's per-parameter multiply / sum chain (l2decay_usable)",
 }
 
@@ -361,6 +373,71 @@ def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, sta
           _p(stats_n), _p(w3), _p(stats3), _pn(ws_), _pn(stats_s), *_mask_args(mask, M), _p(g), _p(dx3), _pn(dxs),
           _p(dwb[0]), _p(dwb[1]), _p(dwb[2]) if dual else None, _p(coef), _p(ws), ws.numel())
     return g, dx3, dxs, dwb[0], dwb[1], dwb[2] if dual else None
+
+
+# ---- group normalisation over [S * P, C] rows (csrc/plumbing/groupnorm.hip) ----
+def groupnorm_usable(x, P, G):
+    """True when the fused group-norm kernels take this [M, C] tensor as M / P samples of P rows in G groups."""
+    if switch("WSSDL_DISABLE_FUSED_GN"):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0):
+        return False
+    if P < 1 or x.shape[0] == 0 or x.shape[0] % P:
+        return False
+    L = lib()
+    return L is not None and bool(L.wsplumb_groupnorm_supported(x.shape[0] // P, P, x.shape[1], G))
+
+
+def groupnorm_plan(S, P, C):
+    """(small regime?, workgroups or chunks per sample, rows per chunk) of a fused call: what the tests annotate."""
+    what = (_ll * 3)()
+    if lib().wsplumb_groupnorm_plan(S, P, C, what):
+        raise ValueError("group norm: unsupported shape")
+    return bool(what[0]), int(what[1]), int(what[2])
+
+
+def _gn_args(x, P, mask, pos_major):
+    """(S, P, C, the two row strides, the mask pointer) of a group-norm call over x [S * P, C]: row (s, p) is
+    s * P + p, or p * S + s when position-major."""
+    M, C = x.shape
+    S = M // P
+    assert M == S * P and x.is_contiguous() and x.dtype == torch.float32
+    assert mask is None or (mask.shape == (S,) and mask.dtype == torch.float32 and mask.is_contiguous())
+    ss, ps = (1, S) if pos_major else (P, 1)
+    return S, P, C, ss, ps, _pn(mask)
+
+
+def _gn_workspace(x, S, P):
+    n = lib().wsplumb_groupnorm_workspace_bytes(S, P, x.shape[1])
+    return torch.empty((max(n, 16),), dtype=torch.uint8, device=x.device)
+
+
+def groupnorm_forward(x, P, gamma, beta, eps, G, relu, mask=None, pos_major=False):
+    """y = act(group_norm(x)) over the S = M / P samples of x [M, C] (interleaved groups: channel c in group c % G);
+    mask [S] f32 (0 = dead sample: zeros out, rows not read).  Returns (y, mean [S, G], rstd [S, G])."""
+    S, P, C, ss, ps, pm = _gn_args(x, P, mask, pos_major)
+    y = torch.empty_like(x)
+    mean = torch.empty((S, G), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((S, G), dtype=torch.float32, device=x.device)
+    ws = _gn_workspace(x, S, P)
+    _call("wsplumb_groupnorm_forward", x.device, _p(x), S, P, C, G, ss, ps, _p(gamma), _p(beta), float(eps), int(relu), pm,
+          _p(y), _p(mean), _p(rstd), _p(ws), ws.numel())
+    return y, mean, rstd
+
+
+def groupnorm_backward(x, dy, P, gamma, beta, mean, rstd, relu, mask=None, pos_major=False):
+    """(dx, dgamma, dbeta) of groupnorm_forward from its input, the output's gradient and its mean / rstd; the ReLU gate
+    is recomputed from x (which is what beta is for)."""
+    S, P, C, ss, ps, pm = _gn_args(x, P, mask, pos_major)
+    G = mean.shape[1]
+    assert dy.shape == x.shape and dy.is_contiguous() and dy.dtype == torch.float32
+    assert mean.shape == (S, G) and rstd.shape == (S, G) and mean.is_contiguous() and rstd.is_contiguous()
+    dx = torch.empty_like(x)
+    dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    ws = _gn_workspace(x, S, P)
+    _call("wsplumb_groupnorm_backward", x.device, _p(x), _p(dy), S, P, C, G, ss, ps, _p(gamma), _p(beta), _p(mean),
+          _p(rstd), int(relu), pm, _p(dx), _p(dgb[0]), _p(dgb[1]), _p(ws), ws.numel())
+    return dx, dgb[0], dgb[1]
 
 
 def im2col_usable(x):

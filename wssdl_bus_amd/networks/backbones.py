@@ -38,8 +38,26 @@ def _bn(c):
     return BatchNormAct2d(c, eps=1e-3, momentum=0.01)
 
 
+class GroupNormAct2d(rownorm.RowGroupNorm):
+    """BatchNormAct2d's counterpart for norm_type 'GN': the reference's group norm (rownorm.RowGroupNorm) of an
+    [N, C, H, W] tensor, a sample being an image.  A channels_last tensor is normalised through its [N*H*W, C] row
+    view with no copy; any other layout through a copy of it."""
+
+    def forward(self, x, relu=False):
+        n, c, h, w = x.shape
+        r2 = _rows(x)
+        if r2 is not None:
+            return _nchw(super().forward(r2, n, relu=relu), x)
+        y = super().forward(x.permute(0, 2, 3, 1).reshape(-1, c), n, relu=relu)
+        return y.view(n, h, w, c).permute(0, 3, 1, 2)
+
+
+rownorm.NORM_MAKERS[("BN", False)] = _bn
+rownorm.NORM_MAKERS[("GN", False)] = lambda c: GroupNormAct2d(c, rownorm.gn_groups(c))
+
+
 class Conv(nn.Module):
-    """conv + optional BatchNorm + optional ReLU (network.py:100-135).  TF 'SAME' padding
+    """conv + optional norm (rownorm.make_norm) + optional ReLU (network.py:100-135).  TF 'SAME' padding
     is reproduced exactly (asymmetric when needed); bias only without normalisation."""
 
     def __init__(self, c_i, c_o, k, s, norm=None, relu=True, padding="SAME"):
@@ -49,7 +67,7 @@ class Conv(nn.Module):
         nn.init.trunc_normal_(self.conv.weight, std=0.01, a=-0.02, b=0.02)     # :110
         if self.conv.bias is not None:
             nn.init.zeros_(self.conv.bias)
-        self.bn = _bn(c_o) if norm == "BN" else None
+        self.bn = rownorm.make_norm(norm, c_o, rows=False)
 
     def forward(self, x, act=True):
         """act=False: the convolution's raw output (its norm is applied by the block's join, _join)."""
@@ -101,7 +119,7 @@ def _join(last, x, short, ori, nxt):
 
 
 def _norm_relu(bn, x):
-    """relu(bn(x)), bn a BatchNormAct2d or None."""
+    """relu(bn(x)), bn a BatchNormAct2d, a GroupNormAct2d or None."""
     return bn(x, relu=True) if bn is not None else F.relu(x)
 
 
@@ -116,13 +134,14 @@ def _preact(blk, x, pre, norm_relu):
     return y, (y if blk.preact == "both_preact" else x)
 
 
-def _init_block(blk, conv, bn, c_i, c_o, s, preact, norm):
-    """The layers of a residual block of either layout (`conv`, `bn`: its convolution and norm classes) from
+def _init_block(blk, conv, rows, c_i, c_o, s, preact, norm):
+    """The layers of a residual block of either layout (`conv`: its convolution class; `rows`: norms over row matrices,
+    rownorm.make_norm) from
     blk.chain, the (kernel, carries the stride) pairs of conv1, conv2, ...: pre_bn (None without pre-activation norm),
     the chain c_i -> c_o -> ... -> c_o * expansion with no ReLU on its last member, and the projection shortcut
     `short` (None when the channel counts agree)."""
     blk.preact, blk.stride = preact, s
-    blk.pre_bn = bn(c_i) if (preact != "no_preact" and norm == "BN") else None
+    blk.pre_bn = rownorm.make_norm(norm, c_i, rows) if preact != "no_preact" else None
     c_out, c = c_o * blk.expansion, c_i
     for i, (k, strided) in enumerate(blk.chain, 1):
         last = i == len(blk.chain)
@@ -140,7 +159,7 @@ class _Block(nn.Module):
 
     def __init__(self, c_i, c_o, s, preact, norm):
         super().__init__()
-        _init_block(self, Conv, _bn, c_i, c_o, s, preact, norm)
+        _init_block(self, Conv, False, c_i, c_o, s, preact, norm)
 
     def forward(self, x, pre=None, nxt=None):
         """pre: this block's pre-activation when the previous block's join computed it; nxt: the norm (+ReLU)
@@ -198,7 +217,7 @@ class ResNetTrunk(nn.Module):
         self.group0 = layer_group(block, 64, 64, defs[0], 1, norm, first=True)
         self.group1 = layer_group(block, 64 * e, 128, defs[1], 2, norm)
         self.group2 = layer_group(block, 128 * e, 256, defs[2], 2, norm)
-        self.norm = _bn(256 * e) if norm == "BN" else None
+        self.norm = rownorm.make_norm(norm, 256 * e, rows=False)
         self.out_channels = 256 * e
 
     def forward(self, x):
@@ -215,7 +234,7 @@ class ResNetHead(nn.Module):
         defs, block = RESNET_DEFS[depth]
         e = block.expansion
         self.group3 = layer_group(block, 256 * e, 512, defs[3], 2, norm)
-        self.norm = _bn(512 * e) if norm == "BN" else None
+        self.norm = rownorm.make_norm(norm, 512 * e, rows=False)
         self.out_features = 512 * e
 
     def forward(self, x):

@@ -19,12 +19,12 @@ import torch.nn.functional as F
 
 from . import _plumbing, rownorm
 from .backbones import RESNET_DEFS, _convs, _init_block, _preact, _same_pad, _walk, layer_group
-from .rownorm import (RowBatchNorm, _EntryNormFn, _FusedRowBatchNormFn, _JoinFn, _RowBatchNormFn,  # noqa: F401
+from .rownorm import (RowBatchNorm, RowGroupNorm, _EntryNormFn, _FusedRowBatchNormFn, _JoinFn, _RowBatchNormFn,  # noqa: F401
                       _SlotMeanFn, _pm_rows, set_roi_mask)
 
 
 class ConvNHWC(nn.Module):
-    """conv (TF 'SAME') + optional BN + optional ReLU on NHWC tensors via one GEMM.
+    """conv (TF 'SAME') + optional norm (rownorm.make_norm) + optional ReLU on NHWC tensors via one GEMM.
     weight [c_o, k*k*c_i] with the patch laid out (kh, kw, c_i)."""
 
     def __init__(self, c_i, c_o, k, s, norm=None, relu=True):
@@ -33,7 +33,7 @@ class ConvNHWC(nn.Module):
         self.weight = nn.Parameter(torch.empty(c_o, k * k * c_i))
         nn.init.trunc_normal_(self.weight, std=0.01, a=-0.02, b=0.02)
         self.bias = nn.Parameter(torch.zeros(c_o)) if norm is None else None
-        self.bn = RowBatchNorm(c_o) if norm == "BN" else None
+        self.bn = rownorm.make_norm(norm, c_o, rows=True)
 
     def forward(self, x):
         r, h, w, c = x.shape
@@ -52,11 +52,12 @@ class ConvNHWC(nn.Module):
             p = xp.unfold(1, k, s).unfold(2, k, s)            # [R, oh, ow, C, kh, kw]
             oh, ow = p.shape[1], p.shape[2]
             rows = p.permute(0, 1, 2, 4, 5, 3).reshape(-1, k * k * c)
-        return self._act(F.linear(rows, self.weight, self.bias)).view(r, oh, ow, self.c_o)
+        return self._act(F.linear(rows, self.weight, self.bias), r).view(r, oh, ow, self.c_o)
 
-    def _act(self, y, pos_major=False):
+    def _act(self, y, R, pos_major=False):
+        """norm and ReLU over the rows y of R RoIs (a group norm's samples)."""
         if self.bn is not None:
-            return self.bn(y, relu=self.relu, pos_major=pos_major)
+            return rownorm.apply_norm(self.bn, y, R, self.relu, pos_major)
         return F.relu(y) if self.relu else y
 
     # ---- position-major route of the head's 4x4 section (ResNetHeadNHWC.forward) ----
@@ -71,7 +72,7 @@ class ConvNHWC(nn.Module):
             if x.dim() == 4:
                 x = _pm_rows(x, plan, self.s)
             y = F.linear(x, self.weight, self.bias)
-        return self._act(y, pos_major=True) if act else y
+        return self._act(y, R, pos_major=True) if act else y
 
 
 def _norm_tap_conv(c1, c2, rows, plan, in_pm, R, mask):
@@ -85,14 +86,14 @@ def _norm_tap_conv(c1, c2, rows, plan, in_pm, R, mask):
     return y
 
 
-def _norm_relu(bn, x):
-    """relu(bn(x)), bn a RowBatchNorm or None, x a roi-major [R, h, w, C] map or position-major rows."""
+def _norm_relu(bn, x, R=None):
+    """relu(bn(x)), bn a row norm or None, x a roi-major [R, h, w, C] map or the position-major rows of R RoIs."""
     if bn is None:
         return F.relu(x)
     if x.dim() == 2:
-        return bn(x, relu=True, pos_major=True)
+        return rownorm.apply_norm(bn, x, R, True, pos_major=True)
     r, h, w, c = x.shape
-    return bn(x.reshape(-1, c), relu=True).view(r, h, w, c)
+    return rownorm.apply_norm(bn, x.reshape(-1, c), r, True).view(r, h, w, c)
 
 
 class _BlockNHWC(nn.Module):
@@ -100,7 +101,7 @@ class _BlockNHWC(nn.Module):
 
     def __init__(self, c_i, c_o, s, preact, norm):
         super().__init__()
-        _init_block(self, ConvNHWC, RowBatchNorm, c_i, c_o, s, preact, norm)
+        _init_block(self, ConvNHWC, True, c_i, c_o, s, preact, norm)
 
     def forward(self, x):
         x, ori = _preact(self, x, None, _norm_relu)
@@ -117,7 +118,7 @@ class _BlockNHWC(nn.Module):
         if self._entry_fused(x, pre):
             x, ori = _entry_pre_act(self.pre_bn, x, plans[s], s)   # ori: the shortcut's rows, already position-major
         else:
-            x, ori = _preact(self, x, pre, _norm_relu)
+            x, ori = _preact(self, x, pre, lambda bn, t: _norm_relu(bn, t, R))
         *body, last = _convs(self)
         if self._tapnorm_fused(body, x):
             x, body = self._conv12_pm(body[0], body[1], x, plans[body[1].s], R), ()
@@ -130,12 +131,12 @@ class _BlockNHWC(nn.Module):
     @staticmethod
     def _tapnorm_fused(body, x):
         """True when the body is a bottleneck's conv1 -> conv2 pair in the form TapConv3x3Fn's norm form covers: a 1x1 at
-        stride 1 with a training-mode norm and a ReLU, then a 3x3 without a bias, on the GPU, and the switch
+        stride 1 with a training-mode batch norm and a ReLU, then a 3x3 without a bias, on the GPU, and the switch
         WSSDL_HEAD_UNFUSED_TAPNORM not set."""
         if len(body) != 2 or _plumbing.switch("WSSDL_HEAD_UNFUSED_TAPNORM"):
             return False
         c1, c2 = body
-        return (c1.k == 1 and c1.s == 1 and c1.relu and c1.bn is not None and c1.bn.training and c2.k == 3
+        return (c1.k == 1 and c1.s == 1 and c1.relu and rownorm.is_bn(c1.bn) and c1.bn.training and c2.k == 3
                 and c2.bias is None and x.is_cuda and _plumbing.lib() is not None)
 
     @staticmethod
@@ -148,18 +149,18 @@ class _BlockNHWC(nn.Module):
         if _plumbing.tapnorm_usable(rows) and fits and (mask is None or mask.shape[0] == R):
             y = _norm_tap_conv(c1, c2, rows, plan, in_pm, R, mask)
         else:
-            y1 = c1._act(rows, pos_major=in_pm)
+            y1 = c1._act(rows, R, pos_major=in_pm)
             y = _plumbing.TapConv3x3Fn.apply(y1 if in_pm else y1.view(R, plan.h, plan.w, -1), c2.weight, c2.bias, plan,
                                              in_pm, R)
-        return c2._act(y, pos_major=True)
+        return c2._act(y, R, pos_major=True)
 
     def _entry_fused(self, x, pre):
         """True when this is block 1 of the position-major route in the form _EntryNormFn covers: a roi-major
-        input, a training-mode pre-activation norm whose output feeds both a 1x1 conv1 (the bottleneck's; the basic
+        input, a training-mode pre-activation batch norm whose output feeds both a 1x1 conv1 (the bottleneck's; the basic
         block's 3x3 conv1 was never routed through it) and a projection shortcut."""
         bn = self.pre_bn
-        if (x.dim() != 4 or pre is not None or self.preact != "both_preact" or self.short is None or bn is None
-                or self.conv1.k != 1):
+        if (x.dim() != 4 or pre is not None or self.preact != "both_preact" or self.short is None
+                or not rownorm.is_bn(bn) or self.conv1.k != 1):
             return False
         rows = x.reshape(-1, x.shape[3])
         return (bn.training and torch.is_grad_enabled() and _plumbing.entry_usable(rows)
@@ -197,7 +198,7 @@ def _join_pm(last, x3, short, ori, plan, s, R, nxt, exit=None):
     bns = rownorm.join_norms(last, short, nxt)
     mask, fits = rownorm.live_mask(x3.shape[0])
     if bns is None or not _plumbing.join_usable(x3) or not fits:
-        return last._act(x3, pos_major=True) + (short._act(xs, pos_major=True) if short is not None else xs), None
+        return last._act(x3, R, pos_major=True) + (short._act(xs, R, pos_major=True) if short is not None else xs), None
     if exit is not None and _plumbing.exit_usable(x3) and (mask is None or mask.shape[0] == R):
         exit.taken = True
         return rownorm.join_rows(*bns, x3, xs.contiguous(), mask, exit.n_slots)
@@ -223,7 +224,7 @@ class ResNetHeadNHWC(nn.Module):
         blk = BottleneckNHWC if block.expansion == 4 else BasicBlockNHWC
         e = blk.expansion
         self.group3 = layer_group(blk, 256 * e, 512, defs[3], 2, norm)
-        self.norm = RowBatchNorm(512 * e) if norm == "BN" else None
+        self.norm = rownorm.make_norm(norm, 512 * e, rows=True)
         self.out_features = 512 * e
 
     def forward(self, x):
@@ -260,5 +261,5 @@ class ResNetHeadNHWC(nn.Module):
             last = self.norm is not None and nxt is self.norm and blk is blocks[-1]
             return blk.forward_pm(x, plans, R, pre, nxt, exit if last else None)
 
-        y = _walk(blocks, x, self.norm, _norm_relu, step)
+        y = _walk(blocks, x, self.norm, lambda bn, t: _norm_relu(bn, t, R), step)
         return y if exit.taken else _SlotMeanFn.apply(y, exit.n_slots)

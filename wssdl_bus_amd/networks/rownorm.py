@@ -1,15 +1,18 @@
-"""Batch norm over the rows of an [M, C] matrix, the one form both networks normalise in: the trunk's [N, H, W, C]
+"""Batch norm and group norm over the rows of an [M, C] matrix, the one form both networks normalise in: the trunk's [N, H, W, C]
 maps are [N*H*W, C] row views (backbones.BatchNormAct2d), the per-RoI head's activations are rows already
 (RowBatchNorm, roi-major or position-major).  Here live the autograd Functions over the kernels of
 csrc/plumbing/rowbn.hip (single norm, block-1 entry norm, residual join) with their stock-PyTorch stand-ins, the
 live-row mask of the head, the one running-statistics update (`track`, `running`) and the one residual join over row
-matrices (`join_norms`, `join_rows`).  Imports only _plumbing; backbones.py and roi_head.py import from here.
+matrices (`join_norms`, `join_rows`).  Group norm (norm_type 'GN': RowGroupNorm over csrc/plumbing/groupnorm.hip)
+has no batch statistics and takes none of the batch-norm fusions (`is_bn`); `make_norm` is the one place that turns a
+norm_type into a module.  Imports only _plumbing and the config; backbones.py and roi_head.py import from here.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _plumbing
+from ..fast_rcnn.config import cfg
 
 
 class _RowBatchNormFn(torch.autograd.Function):
@@ -249,9 +252,9 @@ def running(bns, mask, rows):
 def join_norms(last, short, nxt):
     """The norms (bn3, bn_s or None, bn_n) of a residual block's end when the join kernels can stand for them: `nxt`
     (the norm that follows the block) is given, `last` (the block's final convolution) applies no ReLU, and every
-    norm exists and is in training mode.  Else None.  These conditions both networks share; each adds its own."""
+    norm exists, is a batch norm (is_bn) and is in training mode.  Else None.  These conditions both networks share; each adds its own."""
     bns = (last.bn, nxt) + ((short.bn,) if short is not None else ())
-    if nxt is None or last.relu or any(b is None or not b.training for b in bns):
+    if nxt is None or last.relu or any(not is_bn(b) or not b.training for b in bns):
         return None
     return last.bn, short.bn if short is not None else None, nxt
 
@@ -307,3 +310,104 @@ class RowBatchNorm(nn.Module):
             n = x.shape[0]
         track(self, mean, var, n)
         return y
+
+
+# ---- group normalisation (norm_type 'GN') ----
+def _group_norm_rows(x, samples, weight, bias, eps, groups, relu, mask, pos_major):
+    """The reference's group_norm on rows with stock PyTorch ops (any G, any dtype, any device): x [M, C] is `samples`
+    samples of M / samples rows -- row s * P + p, or p * S + s when position-major -- reshaped to [S, P, C/G, G]
+    (channel c in group c % G), one mean and one biased variance per (sample, group).  mask [S]: zeros for its dead
+    samples, whatever their rows hold."""
+    M, C = x.shape
+    S, P = samples, M // samples
+    v = x.view(P, S, C).transpose(0, 1) if pos_major else x.view(S, P, C)
+    g = v.reshape(S, P, C // groups, groups)
+    var, mean = torch.var_mean(g, dim=(1, 2), unbiased=False, keepdim=True)
+    y = ((g - mean) * torch.rsqrt(var + eps)).reshape(S, P, C) * weight + bias
+    if relu:
+        y = F.relu(y)
+    if mask is not None:
+        y = torch.where(mask.view(S, 1, 1) != 0, y, torch.zeros_like(y))
+    return (y.transpose(0, 1) if pos_major else y).reshape(M, C)
+
+
+class _FusedRowGroupNormFn(torch.autograd.Function):
+    """Group norm (optionally with its ReLU) on the kernels of csrc/plumbing/groupnorm.hip: the forward keeps the
+    per-(sample, group) mean / rstd, the backward recomputes the ReLU gate from x, so y is not saved."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, groups, rows_per_sample, relu, roi_mask, pos_major):
+        y, mean, rstd = _plumbing.groupnorm_forward(x, rows_per_sample, weight, bias, eps, groups, relu, roi_mask,
+                                                    pos_major)
+        ctx.save_for_backward(x, weight, bias, mean, rstd, roi_mask)
+        ctx.args = (rows_per_sample, relu, pos_major)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, bias, mean, rstd, roi_mask = ctx.saved_tensors
+        P, relu, pos_major = ctx.args
+        dx, dw, db = _plumbing.groupnorm_backward(x, dy.contiguous(), P, weight, bias, mean, rstd, relu, roi_mask,
+                                                  pos_major)
+        return dx, dw, db, None, None, None, None, None, None
+
+
+class RowGroupNorm(nn.Module):
+    """The reference's group norm over rows ([M, C] input, `samples` samples of M / samples rows each): interleaved
+    groups, eps 1e-5, gamma / beta per channel as `weight` / `bias`, no buffers and no difference between training and
+    evaluation.  `relu=True` applies the ReLU that follows it inside the same kernels; rows are sample-major or, with
+    `pos_major=True`, position-major.  The head's live-row mask, when set, is the live-sample mask (one entry per
+    RoI).  On the fused kernels when they take the tensor (_plumbing.groupnorm_usable), else stock PyTorch ops."""
+
+    def __init__(self, num_features, groups, eps=1e-5):
+        super().__init__()
+        if groups < 1 or num_features % groups:
+            raise ValueError("group norm: %d channels do not split into %d groups" % (num_features, groups))
+        self.groups, self.eps = groups, eps
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+
+    def forward(self, x, samples, relu=False, pos_major=False):
+        M = x.shape[0]
+        if samples < 1 or M % samples:
+            raise ValueError("group norm: %d rows are not %d samples" % (M, samples))
+        mask = _ROI_MASK
+        if mask is not None and mask.shape[0] != samples:
+            raise ValueError("group norm: the live-row mask has %d entries for %d samples" % (mask.shape[0], samples))
+        if M and _plumbing.groupnorm_usable(x, M // samples, self.groups):
+            return _FusedRowGroupNormFn.apply(x, self.weight, self.bias, self.eps, self.groups, M // samples,
+                                              bool(relu), mask, bool(pos_major))
+        return _group_norm_rows(x, samples, self.weight, self.bias, self.eps, self.groups, relu, mask, pos_major)
+
+
+def is_bn(norm):
+    """True for a batch-norm module: what the batch-norm fusions (joins, entry, the norm inside the patch gather) may
+    stand for.  None and group norms are not."""
+    return norm is not None and not isinstance(norm, RowGroupNorm)
+
+
+def apply_norm(norm, x, samples, relu, pos_major=False):
+    """norm(x) over [M, C] rows for either kind of row norm; `samples` (what a group norm needs) is the RoI count."""
+    if isinstance(norm, RowGroupNorm):
+        return norm(x, samples, relu=relu, pos_major=pos_major)
+    return norm(x, relu=relu, pos_major=pos_major)
+
+
+def gn_groups(c):
+    """The reference's group count for c channels (network.py:126): min(GN_MIN_NUM_G, c // GN_MIN_CHS_PER_G), at most c."""
+    return max(min(cfg.TRAIN.GN_MIN_NUM_G, c // cfg.TRAIN.GN_MIN_CHS_PER_G, c), 1)
+
+
+# (kind, rows) -> factory(c).  rows=True: modules over [M, C] rows (the head); rows=False: over NCHW-shaped tensors
+# (the trunk, the NCHW head), registered by backbones.py.
+NORM_MAKERS = {("BN", True): lambda c: RowBatchNorm(c), ("GN", True): lambda c: RowGroupNorm(c, gn_groups(c))}
+
+
+def make_norm(kind, c, rows):
+    """The norm module of a site with c channels: None for kind None, batch norm for 'BN', group norm for 'GN' (group
+    count from cfg); anything else is an error."""
+    if kind is None:
+        return None
+    if kind not in ("BN", "GN"):
+        raise ValueError("norm_type must be None, 'BN' or 'GN', not %r" % (kind,))
+    return NORM_MAKERS[(kind, bool(rows))](c)
