@@ -364,13 +364,80 @@ __device__ __forceinline__ float running_update(float r, float stat, double unbi
     return (float)((double)r + p);
 }
 
-// forward finish: mean / biased var / scale / shift per column, and the running statistics
-__global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel(
+// Batch renormalisation (Ioffe 2017; tf.layers.batch_normalization(renorm=True), no clipping) of one norm: the
+// layer's three state vectors, each f32 [C] and updated in place by the forward finish kernel, the moving-average
+// factor rho of that update, and where the step's correction factors go (rows 5 and 6 of a [7, C] statistic block).
+// The weight is kept per column (all entries equal): a column's thread reads and writes only its own entries, so no
+// finish workgroup can see another's update.  mean == nullptr: a plain batch norm.
+//   W, Rm, Rs = weight, mean, stddev BEFORE this step;  sigma = sqrt(v + eps)
+//   mixed_mean = Rm + (1 - W) * mu;   mixed_std = Rs + (1 - W) * sigma
+//   r = sigma / mixed_std;   d = (mu - mixed_mean) / mixed_std             (constants of the backward)
+//   y = w * ((x - mu) / sigma * r + d) + b = x * scale + shift
+// all of it in f64 from the f64 mu / v of the column sums and the f32 state, every operation rounded on its own; r, d
+// and mixed_mean are rounded to f32 once, then in f32, as the plain layer forms them,
+//   scale = (rstd * r) * w;   shift = fmaf(-scale, mixed_mean, b)          (w * d + b - scale * mu, regrouped)
+// so that a fresh layer (W = Rm = Rs = 0: r = 1, d = 0, mixed_mean = mu exactly) writes the plain layer's bits.
+// Then the state and, from the ROUNDED new state, the running statistics (no n / (n - 1) factor on this path):
+//   Rm' = (float)(Rm + (mu - Rm) * (1 - rho));  Rs' = (float)(Rs + (sigma - Rs) * (1 - rho));
+//   W'  = (float)(W + (1 - W) * (1 - rho))
+//   running_mean += momentum * (Rm' / W' - running_mean);   running_var += momentum * ((Rs' / W')^2 - eps - running_var)
+struct Renorm {
+    float *mean, *stddev, *weight;
+    double momentum;                // rho, a double: 1 - rho cancels, and f32(0.99) would put 1e-6 of error into every update
+    float *r, *d;
+};
+
+// s + (x - s) * k, every f64 operation rounded on its own (the host restates it)
+__device__ __forceinline__ double renorm_lerp(double s, double x, double k) {
+#pragma clang fp contract(off)
+    const double t = x - s;
+    const double p = t * k;
+    return s + p;
+}
+
+struct RenormFactors {
+    float r, d, mixed_mean;
+};
+
+// the renorm part of the forward finish for column c: r, d and mixed_mean of this step, the state and the running
+// statistics updated (struct Renorm above has the operation order)
+__device__ __forceinline__ RenormFactors renorm_column(const Renorm &rn, const Running &run, int c, double mu, double v,
+                                                       float eps) {
+#pragma clang fp contract(off)
+    const double sigma = sqrt(v + (double)eps);
+    const double W = rn.weight[c], Rm = rn.mean[c], Rs = rn.stddev[c];
+    const double omw = 1.0 - W;
+    const double pm = omw * mu;
+    const double mixed_mean = Rm + pm;
+    const double ps = omw * sigma;
+    const double mixed_std = Rs + ps;
+    const double dm = mu - mixed_mean;
+    const RenormFactors f = {(float)(sigma / mixed_std), (float)(dm / mixed_std), (float)mixed_mean};
+    const double k = 1.0 - rn.momentum;
+    const float Rm1 = (float)renorm_lerp(Rm, mu, k), Rs1 = (float)renorm_lerp(Rs, sigma, k);
+    const float W1 = (float)renorm_lerp(W, 1.0, k);
+    rn.mean[c] = Rm1;
+    rn.stddev[c] = Rs1;
+    rn.weight[c] = W1;
+    const double mom = (double)run.momentum;
+    if (run.mean) run.mean[c] = (float)renorm_lerp((double)run.mean[c], (double)Rm1 / (double)W1, mom);
+    if (run.var) {
+        const double q = (double)Rs1 / (double)W1;
+        const double q2 = q * q;
+        run.var[c] = (float)renorm_lerp((double)run.var[c], q2 - (double)eps, mom);
+    }
+    return f;
+}
+
+// forward finish: mean / biased var / scale / shift per column, and the running statistics; RENORM: the layer is a
+// batch renormalisation (struct Renorm), which changes scale and shift and adds r, d and the state update
+template <bool RENORM>
+__device__ __forceinline__ void fwd_finish(
     const double *__restrict__ partial, int nblocks, int C, long long M,
     const float *__restrict__ weight, const float *__restrict__ bias, float eps,
     float *__restrict__ mean, float *__restrict__ var, float *__restrict__ rstd,
     float *__restrict__ scale, float *__restrict__ shift, const float *__restrict__ mask, int n_rois, int per,
-    float *__restrict__ count, Running run) {
+    float *__restrict__ count, const Running &run, const Renorm &rn) {
     __shared__ double red[FIN_GROUPS][FIN_COLS][2];
     const int grp = threadIdx.x / FIN_COLS;
     const int c = blockIdx.x * FIN_COLS + threadIdx.x % FIN_COLS;
@@ -388,6 +455,18 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel
     double v = __builtin_fma(-mu, mu, q / Mn);
     if (v < 0.0) v = 0.0;
     const float rs = (float)(1.0 / sqrt(v + (double)eps));
+    if (RENORM) {
+        const RenormFactors f = renorm_column(rn, run, c, mu, v, eps);
+        const float scl = (rs * f.r) * weight[c];
+        mean[c] = (float)mu;
+        var[c] = (float)v;
+        rstd[c] = rs;
+        scale[c] = scl;
+        shift[c] = __builtin_fmaf(-scl, f.mixed_mean, bias[c]);
+        rn.r[c] = f.r;
+        rn.d[c] = f.d;
+        return;
+    }
     const float scl = rs * weight[c];
     mean[c] = (float)mu;
     var[c] = (float)v;
@@ -399,12 +478,36 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel
     if (run.var) run.var[c] = running_update(run.var[c], (float)v, Mn / (Mn - 1.0 > 1.0 ? Mn - 1.0 : 1.0), mom);
 }
 
-// backward finish: dweight, dbias and the three coefficients of dx = a*g - k0 - k1*x
-__global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_kernel(
+__global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_kernel(
+    const double *__restrict__ partial, int nblocks, int C, long long M,
+    const float *__restrict__ weight, const float *__restrict__ bias, float eps,
+    float *__restrict__ mean, float *__restrict__ var, float *__restrict__ rstd,
+    float *__restrict__ scale, float *__restrict__ shift, const float *__restrict__ mask, int n_rois, int per,
+    float *__restrict__ count, Running run) {
+    fwd_finish<false>(partial, nblocks, C, M, weight, bias, eps, mean, var, rstd, scale, shift, mask, n_rois, per, count,
+                      run, Renorm());
+}
+
+__global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_fwd_finish_renorm_kernel(
+    const double *__restrict__ partial, int nblocks, int C, long long M,
+    const float *__restrict__ weight, const float *__restrict__ bias, float eps,
+    float *__restrict__ mean, float *__restrict__ var, float *__restrict__ rstd,
+    float *__restrict__ scale, float *__restrict__ shift, const float *__restrict__ mask, int n_rois, int per,
+    float *__restrict__ count, Running run, Renorm rn) {
+    fwd_finish<true>(partial, nblocks, C, M, weight, bias, eps, mean, var, rstd, scale, shift, mask, n_rois, per, count,
+                     run, rn);
+}
+
+// backward finish: dweight, dbias and the three coefficients of dx = a*g - k0 - k1*x.  RENORM: the forward's r and d
+// (constants: no gradient flows through them) enter as a = (w * r) * rstd and dweight = r * sum_g_xhat + d * sum_g,
+// product, product and sum each rounded on its own in f64; k1 and k0 follow from that a.
+template <bool RENORM>
+__device__ __forceinline__ void bwd_finish(
     const double *__restrict__ partial, int nblocks, int C, long long M,
     const float *__restrict__ weight, const float *__restrict__ mean,
     const float *__restrict__ rstd, float *__restrict__ dweight, float *__restrict__ dbias,
-    float *__restrict__ coef, const float *__restrict__ mask, int n_rois, int per) {
+    float *__restrict__ coef, const float *__restrict__ mask, int n_rois, int per,
+    const float *__restrict__ rn_r, const float *__restrict__ rn_d) {
     __shared__ double red[FIN_GROUPS][FIN_COLS][2];
     const int grp = threadIdx.x / FIN_COLS;
     const int c = blockIdx.x * FIN_COLS + threadIdx.x % FIN_COLS;
@@ -415,14 +518,41 @@ __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_kernel
     // fused multiply-adds written out as in the forward finish: fma(-mu, sg, sgx) and k0 = fma(-k1, mu, a * sg / n)
     const double mu = mean[c], rs = rstd[c], w = weight[c];
     const double sum_g_xhat = __builtin_fma(-mu, sg, sgx) * rs;
-    const double a = w * rs;
+    double a = w * rs, dw = sum_g_xhat;
+    if (RENORM) {
+#pragma clang fp contract(off)
+        const double r = rn_r[c], d = rn_d[c];
+        const double wr = w * r;
+        a = wr * rs;
+        const double p0 = r * sum_g_xhat;
+        const double p1 = d * sg;
+        dw = p0 + p1;
+    }
     const double k1 = a * rs * sum_g_xhat / Mn;
     const double k0 = __builtin_fma(-k1, mu, a * sg / Mn);
-    dweight[c] = (float)sum_g_xhat;
+    dweight[c] = (float)dw;
     dbias[c] = (float)sg;
     coef[c] = (float)a;
     coef[C + c] = (float)k0;
     coef[2 * C + c] = (float)k1;
+}
+
+__global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_kernel(
+    const double *__restrict__ partial, int nblocks, int C, long long M,
+    const float *__restrict__ weight, const float *__restrict__ mean,
+    const float *__restrict__ rstd, float *__restrict__ dweight, float *__restrict__ dbias,
+    float *__restrict__ coef, const float *__restrict__ mask, int n_rois, int per) {
+    bwd_finish<false>(partial, nblocks, C, M, weight, mean, rstd, dweight, dbias, coef, mask, n_rois, per, nullptr,
+                      nullptr);
+}
+
+__global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void rowbn_bwd_finish_renorm_kernel(
+    const double *__restrict__ partial, int nblocks, int C, long long M,
+    const float *__restrict__ weight, const float *__restrict__ mean,
+    const float *__restrict__ rstd, float *__restrict__ dweight, float *__restrict__ dbias,
+    float *__restrict__ coef, const float *__restrict__ mask, int n_rois, int per,
+    const float *__restrict__ rn_r, const float *__restrict__ rn_d) {
+    bwd_finish<true>(partial, nblocks, C, M, weight, mean, rstd, dweight, dbias, coef, mask, n_rois, per, rn_r, rn_d);
 }
 
 // Block 1's entry (networks/roi_head.py, _EntryNormFn): besides y (roi-major rows, `per` positions per RoI), the
@@ -837,26 +967,46 @@ inline void launch_grad_sums(const Geom &g, const float *x, const float *dy, con
         });
 }
 
+// rn (null, or with a null mean: a plain norm): the norm's renorm state, the renorm form of the kernel
 inline void launch_fwd_finish(const Geom &g, const double *partial, const float *weight, const float *bias, float eps,
                               float *mean, float *var, float *rstd, float *scale, float *shift, float *count,
-                              Running run) {
-    hipLaunchKernelGGL(rowbn_fwd_finish_kernel, dim3((g.C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
-                       g.st, partial, g.nb, g.C, g.M, weight, bias, eps, mean, var, rstd, scale, shift, g.mask, g.n_rois,
-                       g.per, g.mask ? count : nullptr, run);
+                              Running run, const Renorm *rn = nullptr) {
+    const dim3 grid((g.C + FIN_COLS - 1) / FIN_COLS), block(FIN_COLS * FIN_GROUPS);
+    if (rn && rn->mean)
+        hipLaunchKernelGGL(rowbn_fwd_finish_renorm_kernel, grid, block, 0, g.st, partial, g.nb, g.C, g.M, weight, bias, eps,
+                           mean, var, rstd, scale, shift, g.mask, g.n_rois, g.per, g.mask ? count : nullptr, run, *rn);
+    else
+        hipLaunchKernelGGL(rowbn_fwd_finish_kernel, grid, block, 0, g.st, partial, g.nb, g.C, g.M, weight, bias, eps, mean,
+                           var, rstd, scale, shift, g.mask, g.n_rois, g.per, g.mask ? count : nullptr, run);
 }
 
-// the same into a [5, C] statistic block: mean, var, rstd, scale, shift (the layout of the Python binding)
+// the same into a statistic block: [5, C] = mean, var, rstd, scale, shift (the layout of the Python binding), or with
+// rn [7, C], r and d after them
 inline void launch_fwd_finish(const Geom &g, const double *partial, const float *weight, const float *bias, float eps,
-                              float *stats, float *count, Running run) {
+                              float *stats, float *count, Running run, const Renorm *rn = nullptr) {
     const int C = g.C;
+    Renorm block;
+    if (rn && rn->mean) {
+        block = *rn;
+        block.r = stats + 5 * C;
+        block.d = stats + 6 * C;
+        rn = &block;
+    }
     launch_fwd_finish(g, partial, weight, bias, eps, stats, stats + C, stats + 2 * C, stats + 3 * C, stats + 4 * C, count,
-                      run);
+                      run, rn);
 }
 
+// r, d (both or neither): the forward's renorm factors of the norm, the renorm form of the kernel
 inline void launch_bwd_finish(const Geom &g, const double *partial, const float *weight, const float *mean,
-                              const float *rstd, float *dweight, float *dbias, float *coef) {
-    hipLaunchKernelGGL(rowbn_bwd_finish_kernel, dim3((g.C + FIN_COLS - 1) / FIN_COLS), dim3(FIN_COLS * FIN_GROUPS), 0,
-                       g.st, partial, g.nb, g.C, g.M, weight, mean, rstd, dweight, dbias, coef, g.mask, g.n_rois, g.per);
+                              const float *rstd, float *dweight, float *dbias, float *coef, const float *r = nullptr,
+                              const float *d = nullptr) {
+    const dim3 grid((g.C + FIN_COLS - 1) / FIN_COLS), block(FIN_COLS * FIN_GROUPS);
+    if (r)
+        hipLaunchKernelGGL(rowbn_bwd_finish_renorm_kernel, grid, block, 0, g.st, partial, g.nb, g.C, g.M, weight, mean, rstd,
+                           dweight, dbias, coef, g.mask, g.n_rois, g.per, r, d);
+    else
+        hipLaunchKernelGGL(rowbn_bwd_finish_kernel, grid, block, 0, g.st, partial, g.nb, g.C, g.M, weight, mean, rstd,
+                           dweight, dbias, coef, g.mask, g.n_rois, g.per);
 }
 
 // er: block 1's entry form (relu, roi-major rows): the sampled rows go to er->ys as well
@@ -908,12 +1058,33 @@ inline void launch_slot_mean(hipStream_t st, const float *x, const float *scale,
 inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 
 // the backward of one layer; eg: dy comes in the two parts of block 1's entry gradient (relu, roi-major rows)
+// r, d: the forward's renorm factors (both or neither)
 int backward_impl(const Geom &g, const float *x, const float *dy, const EntryGrad *eg, const float *weight,
                   const float *mean, const float *rstd, const float *scale, const float *shift, bool relu, float *dx,
-                  float *dweight, float *dbias, float *coef) {
+                  float *dweight, float *dbias, float *coef, const float *r = nullptr, const float *d = nullptr) {
+    if ((r != nullptr) != (d != nullptr)) return 1;
     launch_grad_sums(g, x, dy, scale, shift, relu, eg, g.p0);
-    launch_bwd_finish(g, g.p0, weight, mean, rstd, dweight, dbias, coef);
+    launch_bwd_finish(g, g.p0, weight, mean, rstd, dweight, dbias, coef, r, d);
     launch_apply_bwd(g, x, dy, scale, shift, coef, relu, eg, dx);
+    return launched();
+}
+
+// the renorm state of a single-norm entry point from its arguments; complete, or the call is rejected
+struct RenormArgs {
+    Renorm rn;
+    bool ok;
+    RenormArgs(float *mean, float *stddev, float *weight, double momentum, float *r, float *d)
+        : rn{mean, stddev, weight, momentum, r, d}, ok(mean && stddev && weight && r && d) {}
+};
+
+// the forward of one layer: sums, finish and, with y, the apply pass (er: block 1's entry form).  rn: the layer's
+// renorm state, or null for a plain norm.
+int forward_impl(const Geom &g, const float *x, const float *weight, const float *bias, float eps, bool relu, float *y,
+                 const EntryRows *er, float *mean, float *var, float *rstd, float *scale, float *shift, float *count,
+                 Running run, const Renorm *rn = nullptr) {
+    launch_sums(g, x, g.p0);
+    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count, run, rn);
+    if (y) launch_apply_fwd(g, x, scale, shift, relu, y, er);
     return launched();
 }
 
@@ -937,11 +1108,28 @@ PLUMB_API int wsplumb_rowbn_forward(const float *x, long long M, int C, const fl
     if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, !mask || count, workspace, workspace_bytes, 1,
                   stream))
         return 1;
-    launch_sums(g, x, g.p0);
-    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
-                      Running{running_mean, running_var, momentum, num_batches_tracked});
-    launch_apply_fwd(g, x, scale, shift, relu != 0, y);
-    return launched();
+    return forward_impl(g, x, weight, bias, eps, relu != 0, y, nullptr, mean, var, rstd, scale, shift, count,
+                        Running{running_mean, running_var, momentum, num_batches_tracked});
+}
+
+// wsplumb_rowbn_forward of a batch renormalisation layer (struct Renorm): renorm_mean / renorm_stddev / renorm_weight
+// (f32 [C], the layer's state, updated in place), renorm_momentum (a double: struct Renorm), and r, d (f32 [C], written: the step's correction
+// factors, which the backward takes).  scale and shift are the renorm layer's; the running statistics follow the
+// renorm state.  Everything else as wsplumb_rowbn_forward.
+PLUMB_API int wsplumb_rowbn_forward_renorm(const float *x, long long M, int C, const float *weight, const float *bias,
+                                           float eps, int relu, const float *mask, int n_rois, int per, int pos_major,
+                                           float *y, float *mean, float *var, float *rstd, float *scale, float *shift,
+                                           float *count, void *workspace, size_t workspace_bytes, void *stream,
+                                           float *running_mean, float *running_var, float momentum,
+                                           long long *num_batches_tracked, float *renorm_mean, float *renorm_stddev,
+                                           float *renorm_weight, double renorm_momentum, float *r, float *d) {
+    Geom g;
+    const RenormArgs ra(renorm_mean, renorm_stddev, renorm_weight, renorm_momentum, r, d);
+    if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, ra.ok && y && (!mask || count), workspace,
+                  workspace_bytes, 1, stream))
+        return 1;
+    return forward_impl(g, x, weight, bias, eps, relu != 0, y, nullptr, mean, var, rstd, scale, shift, count,
+                        Running{running_mean, running_var, momentum, num_batches_tracked}, &ra.rn);
 }
 
 // wsplumb_rowbn_forward without its apply pass: the statistics (and the running statistics) of the layer, for a
@@ -956,10 +1144,25 @@ PLUMB_API int wsplumb_rowbn_stats(const float *x, long long M, int C, const floa
     if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, !mask || count, workspace, workspace_bytes, 1,
                   stream))
         return 1;
-    launch_sums(g, x, g.p0);
-    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
-                      Running{running_mean, running_var, momentum, num_batches_tracked});
-    return launched();
+    return forward_impl(g, x, weight, bias, eps, false, nullptr, nullptr, mean, var, rstd, scale, shift, count,
+                        Running{running_mean, running_var, momentum, num_batches_tracked});
+}
+
+// wsplumb_rowbn_stats of a batch renormalisation layer (the renorm arguments of wsplumb_rowbn_forward_renorm)
+PLUMB_API int wsplumb_rowbn_stats_renorm(const float *x, long long M, int C, const float *weight, const float *bias,
+                                         float eps, const float *mask, int n_rois, int per, int pos_major, float *mean,
+                                         float *var, float *rstd, float *scale, float *shift, float *count,
+                                         void *workspace, size_t workspace_bytes, void *stream, float *running_mean,
+                                         float *running_var, float momentum, long long *num_batches_tracked,
+                                         float *renorm_mean, float *renorm_stddev, float *renorm_weight,
+                                         double renorm_momentum, float *r, float *d) {
+    Geom g;
+    const RenormArgs ra(renorm_mean, renorm_stddev, renorm_weight, renorm_momentum, r, d);
+    if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, ra.ok && (!mask || count), workspace,
+                  workspace_bytes, 1, stream))
+        return 1;
+    return forward_impl(g, x, weight, bias, eps, false, nullptr, nullptr, mean, var, rstd, scale, shift, count,
+                        Running{running_mean, running_var, momentum, num_batches_tracked}, &ra.rn);
 }
 
 // wsplumb_rowbn_forward with ReLU for block 1's pre-activation norm (roi-major rows, n_rois groups of `per`; mask may
@@ -977,12 +1180,30 @@ PLUMB_API int wsplumb_rowbn_forward_entry(const float *x, long long M, int C, co
     if (make_geom(g, M, C, mask, n_rois, per, false, true,
                   (!mask || count) && ys && possel && n_slots >= 1 && n_slots <= per, workspace, workspace_bytes, 1, stream))
         return 1;
-    launch_sums(g, x, g.p0);
-    launch_fwd_finish(g, g.p0, weight, bias, eps, mean, var, rstd, scale, shift, count,
-                      Running{running_mean, running_var, momentum, num_batches_tracked});
     const EntryRows er = {ys, possel, per, n_rois};
-    launch_apply_fwd(g, x, scale, shift, true, y, &er);
-    return launched();
+    return forward_impl(g, x, weight, bias, eps, true, y, &er, mean, var, rstd, scale, shift, count,
+                        Running{running_mean, running_var, momentum, num_batches_tracked});
+}
+
+// wsplumb_rowbn_forward_entry of a batch renormalisation layer (the renorm arguments of wsplumb_rowbn_forward_renorm)
+PLUMB_API int wsplumb_rowbn_forward_entry_renorm(const float *x, long long M, int C, const float *weight,
+                                                 const float *bias, float eps, const float *mask, int n_rois, int per,
+                                                 const int *possel, int n_slots, float *y, float *ys, float *mean,
+                                                 float *var, float *rstd, float *scale, float *shift, float *count,
+                                                 void *workspace, size_t workspace_bytes, void *stream,
+                                                 float *running_mean, float *running_var, float momentum,
+                                                 long long *num_batches_tracked, float *renorm_mean,
+                                                 float *renorm_stddev, float *renorm_weight, double renorm_momentum,
+                                                 float *r, float *d) {
+    Geom g;
+    const RenormArgs ra(renorm_mean, renorm_stddev, renorm_weight, renorm_momentum, r, d);
+    if (make_geom(g, M, C, mask, n_rois, per, false, true,
+                  ra.ok && y && (!mask || count) && ys && possel && n_slots >= 1 && n_slots <= per, workspace,
+                  workspace_bytes, 1, stream))
+        return 1;
+    const EntryRows er = {ys, possel, per, n_rois};
+    return forward_impl(g, x, weight, bias, eps, true, y, &er, mean, var, rstd, scale, shift, count,
+                        Running{running_mean, running_var, momentum, num_batches_tracked}, &ra.rn);
 }
 
 // feat [R, C] = the mean over the slots of the position-major rows x [n_slots * R, C] (row slot * R + roi), in the one
@@ -1015,6 +1236,20 @@ PLUMB_API int wsplumb_rowbn_backward(const float *x, const float *dy, long long 
     return backward_impl(g, x, dy, nullptr, weight, mean, rstd, scale, shift, relu != 0, dx, dweight, dbias, coef);
 }
 
+// gradients of wsplumb_rowbn_forward_renorm: r, d (f32 [C]) are the factors that call wrote, constants of the
+// backward (bwd_finish); scale and shift are the renorm layer's.  Everything else as wsplumb_rowbn_backward.
+PLUMB_API int wsplumb_rowbn_backward_renorm(const float *x, const float *dy, long long M, int C, const float *weight,
+                                            const float *mean, const float *rstd, const float *scale,
+                                            const float *shift, int relu, const float *mask, int n_rois, int per,
+                                            int pos_major, float *dx, float *dweight, float *dbias, float *coef,
+                                            void *workspace, size_t workspace_bytes, void *stream, const float *r,
+                                            const float *d) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, pos_major != 0, false, r && d, workspace, workspace_bytes, 1, stream))
+        return 1;
+    return backward_impl(g, x, dy, nullptr, weight, mean, rstd, scale, shift, relu != 0, dx, dweight, dbias, coef, r, d);
+}
+
 // gradients of wsplumb_rowbn_forward with ReLU for block 1's pre-activation norm (roi-major rows), the output's
 // gradient given in its two parts (EntryGrad above): dy [n_rois * per, C] roi-major from conv1, dys
 // [n_slots * n_rois, C] position-major from the projection shortcut, possel [per] (device) the slot of each position
@@ -1033,6 +1268,21 @@ PLUMB_API int wsplumb_rowbn_backward_entry(const float *x, const float *dy, cons
     return backward_impl(g, x, dy, &eg, weight, mean, rstd, scale, shift, true, dx, dweight, dbias, coef);
 }
 
+// gradients of wsplumb_rowbn_forward_entry_renorm (r, d as in wsplumb_rowbn_backward_renorm)
+PLUMB_API int wsplumb_rowbn_backward_entry_renorm(const float *x, const float *dy, const float *dys, const int *possel,
+                                                  int n_slots, long long M, int C, const float *weight,
+                                                  const float *mean, const float *rstd, const float *scale,
+                                                  const float *shift, const float *mask, int n_rois, int per,
+                                                  float *dx, float *dweight, float *dbias, float *coef, void *workspace,
+                                                  size_t workspace_bytes, void *stream, const float *r, const float *d) {
+    Geom g;
+    if (make_geom(g, M, C, mask, n_rois, per, false, true, r && d && dys && possel && n_slots >= 1 && n_slots <= per,
+                  workspace, workspace_bytes, 1, stream))
+        return 1;
+    const EntryGrad eg = {dys, possel, per, n_rois, 0.0f};
+    return backward_impl(g, x, dy, &eg, weight, mean, rstd, scale, shift, true, dx, dweight, dbias, coef, r, d);
+}
+
 // ---- residual joins (position-major rows; mask may be null: every row live) ----
 // Statistic blocks are [5, C] f32: mean, var, rstd, scale, shift (the layout of the Python binding).
 
@@ -1045,7 +1295,8 @@ int join_forward_impl(const float *x3, const float *other, long long M, int C, c
                       const float *bias_n, float eps_n, const float *mask, int n_rois, int per, float *out, float *y,
                       float *stats3, float *stats_s, float *stats_n, float *count, void *workspace,
                       size_t workspace_bytes, void *stream, float *const *running, const float *momentum,
-                      long long *const *batches, int exit_slots) {
+                      long long *const *batches, int exit_slots, float *const *renorm = nullptr,
+                      const double *renorm_momentum = nullptr) {
     const bool dual = weight_s != nullptr;
     Geom g;
     const bool exit_ok = exit_slots == 0 || (exit_slots > 0 && M % exit_slots == 0 && M <= 0x7fffffffLL &&
@@ -1054,16 +1305,21 @@ int join_forward_impl(const float *x3, const float *other, long long M, int C, c
                   exit_ok && (!mask || count) && (!dual || (bias_s && stats_s)), workspace, workspace_bytes, 2, stream))
         return 1;
     Running run[3] = {};
+    Renorm rn[3] = {};          // per norm: its renorm state, or none (mean null: a plain norm, a [5, C] block)
     for (int k = 0; k < 3; ++k) {
         if (running) { run[k].mean = running[2 * k]; run[k].var = running[2 * k + 1]; }
         if (momentum) run[k].momentum = momentum[k];
         if (batches) run[k].batches = batches[k];
+        if (renorm && renorm[3 * k]) {
+            if (!renorm[3 * k + 1] || !renorm[3 * k + 2] || !renorm_momentum) return 1;
+            rn[k] = Renorm{renorm[3 * k], renorm[3 * k + 1], renorm[3 * k + 2], renorm_momentum[k], nullptr, nullptr};
+        }
     }
     launch_sums(g, x3, g.p0);
-    launch_fwd_finish(g, g.p0, weight3, bias3, eps3, stats3, nullptr, run[0]);
+    launch_fwd_finish(g, g.p0, weight3, bias3, eps3, stats3, nullptr, run[0], &rn[0]);
     if (dual) {
         launch_sums(g, other, g.p0);
-        launch_fwd_finish(g, g.p0, weight_s, bias_s, eps_s, stats_s, nullptr, run[1]);
+        launch_fwd_finish(g, g.p0, weight_s, bias_s, eps_s, stats_s, nullptr, run[1], &rn[1]);
     }
     const float *sco = dual ? stats_s + 3 * C : nullptr, *sho = dual ? stats_s + 4 * C : nullptr;
     pick<false, true>(dual, [&](auto DUAL) {
@@ -1072,7 +1328,7 @@ int join_forward_impl(const float *x3, const float *other, long long M, int C, c
                                stats3 + 4 * C, other, sco, sho, M, C, g.rpb, out, g.p0, mask, g.div);
         });
     });
-    launch_fwd_finish(g, g.p0, weight_n, bias_n, eps_n, stats_n, count, run[2]);
+    launch_fwd_finish(g, g.p0, weight_n, bias_n, eps_n, stats_n, count, run[2], &rn[2]);
     if (exit_slots)
         launch_slot_mean(g.st, out, stats_n + 3 * C, stats_n + 4 * C, exit_slots, (int)(M / exit_slots), C, mask, y);
     else
@@ -1126,6 +1382,27 @@ PLUMB_API int wsplumb_rowbn_join_forward_exit(const float *x3, const float *othe
                              running, momentum, batches, n_slots);
 }
 
+// wsplumb_rowbn_join_forward (n_slots = 0) or its exit form (n_slots >= 1) with batch renormalisation layers:
+// renorm [9] (host array) holds the renorm_mean, renorm_stddev, renorm_weight pointers of bn3, bn_s, bn_n in that
+// order and renorm_momentum [3] their factors (struct Renorm); a norm whose first pointer is null is a plain norm.
+// The statistic block of a renorm norm is [7, C]: r and d after the five rows (wsplumb_rowbn_join_backward_renorm
+// reads them); scale and shift are the renorm layer's, so the join, apply and exit kernels run unchanged.
+PLUMB_API int wsplumb_rowbn_join_forward_renorm(const float *x3, const float *other, long long M, int C,
+                                                const float *weight3, const float *bias3, float eps3,
+                                                const float *weight_s, const float *bias_s, float eps_s,
+                                                const float *weight_n, const float *bias_n, float eps_n,
+                                                const float *mask, int n_rois, int per, float *out, float *y,
+                                                float *stats3, float *stats_s, float *stats_n, float *count,
+                                                void *workspace, size_t workspace_bytes, void *stream,
+                                                float *const *running, const float *momentum,
+                                                long long *const *batches, int n_slots, float *const *renorm,
+                                                const double *renorm_momentum) {
+    if (n_slots < 0 || !renorm) return 1;
+    return join_forward_impl(x3, other, M, C, weight3, bias3, eps3, weight_s, bias_s, eps_s, weight_n, bias_n, eps_n, mask,
+                             n_rois, per, out, y, stats3, stats_s, stats_n, count, workspace, workspace_bytes, stream,
+                             running, momentum, batches, n_slots, renorm, renorm_momentum);
+}
+
 namespace {
 
 // exit_slots = n_slots > 0: dy is dfeat [M / n_slots, C] of the forward's exit form, and there is no dres
@@ -1133,7 +1410,7 @@ int join_backward_impl(const float *out, const float *dy, const float *dres, con
                        int C, const float *weight_n, const float *stats_n, const float *weight3, const float *stats3,
                        const float *weight_s, const float *stats_s, const float *mask, int n_rois, int per, float *gout,
                        float *dx3, float *dxs, float *dwb_n, float *dwb3, float *dwb_s, float *coef, void *workspace,
-                       size_t workspace_bytes, void *stream, int exit_slots) {
+                       size_t workspace_bytes, void *stream, int exit_slots, int renorm = 0) {
     const bool dual = xs != nullptr;
     Geom g;
     const bool exit_ok = exit_slots == 0 || (exit_slots > 0 && !dres && M % exit_slots == 0 && M <= 0x7fffffffLL &&
@@ -1143,10 +1420,13 @@ int join_backward_impl(const float *out, const float *dy, const float *dres, con
         return 1;
     float *coef_n = coef, *coef3 = coef + 3 * C, *coefs = coef + 6 * C;
     const float *scn = stats_n + 3 * C, *shn = stats_n + 4 * C;
+    // r, d of a norm the renorm bits name (1: bn3, 2: bn_s, 4: bn_n), rows 5 and 6 of its [7, C] block
+    auto rd = [&](int bit, const float *stats, int row) { return (renorm & bit) ? stats + row * C : nullptr; };
     if (exit_slots) {
         const EntryGrad eg = {nullptr, nullptr, exit_slots, (int)(M / exit_slots), slot_mean_scale(exit_slots)};
         launch_grad_sums(g, out, dy, scn, shn, true, &eg, g.p0, true);
-        launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n);
+        launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n, rd(4, stats_n, 5),
+                          rd(4, stats_n, 6));
         pick<false, true>(dual, [&](auto DUAL) {
             pick<0, 2>(g.mode, [&](auto MASK) {
                 hipLaunchKernelGGL((rowbn_join_bwd_kernel<DUAL, false, MASK, DY_EXIT>), dim3(g.nb), dim3(BLOCK), 0, g.st, out,
@@ -1155,7 +1435,8 @@ int join_backward_impl(const float *out, const float *dy, const float *dres, con
         });
     } else {
         launch_grad_sums(g, out, dy, scn, shn, true, nullptr, g.p0);
-        launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n);
+        launch_bwd_finish(g, g.p0, weight_n, stats_n, stats_n + 2 * C, dwb_n, dwb_n + C, coef_n, rd(4, stats_n, 5),
+                          rd(4, stats_n, 6));
         pick<false, true>(dual, [&](auto DUAL) {
             pick<false, true>(dres != nullptr, [&](auto RES) {
                 pick<0, 2>(g.mode, [&](auto MASK) {
@@ -1165,9 +1446,10 @@ int join_backward_impl(const float *out, const float *dy, const float *dres, con
             });
         });
     }
-    launch_bwd_finish(g, g.p0, weight3, stats3, stats3 + 2 * C, dwb3, dwb3 + C, coef3);
+    launch_bwd_finish(g, g.p0, weight3, stats3, stats3 + 2 * C, dwb3, dwb3 + C, coef3, rd(1, stats3, 5), rd(1, stats3, 6));
     if (dual) {
-        launch_bwd_finish(g, g.p1, weight_s, stats_s, stats_s + 2 * C, dwb_s, dwb_s + C, coefs);
+        launch_bwd_finish(g, g.p1, weight_s, stats_s, stats_s + 2 * C, dwb_s, dwb_s + C, coefs, rd(2, stats_s, 5),
+                          rd(2, stats_s, 6));
         pick<0, 2>(g.mode, [&](auto MASK) {
             hipLaunchKernelGGL((rowbn_apply_bwd_dual_kernel<MASK>), dim3(apply_grid(g.total4)), dim3(BLOCK), 0, g.st, x3, xs,
                                gout, coef3, coefs, g.total4, C / 4, dx3, dxs, mask, g.div);
@@ -1210,4 +1492,20 @@ PLUMB_API int wsplumb_rowbn_join_backward_exit(const float *out, const float *df
     return join_backward_impl(out, dfeat, nullptr, x3, xs, M, C, weight_n, stats_n, weight3, stats3, weight_s, stats_s,
                               mask, n_rois, per, gout, dx3, dxs, dwb_n, dwb3, dwb_s, coef, workspace, workspace_bytes,
                               stream, n_slots);
+}
+
+// gradients of wsplumb_rowbn_join_forward_renorm (n_slots = 0: dy is y's gradient; n_slots >= 1, the exit form: dy is
+// dfeat and there is no dres).  renorm: bit 0 / 1 / 2 set when bn3 / bn_s / bn_n is a renorm norm, whose [7, C]
+// statistic block then carries the forward's r and d in rows 5 and 6.
+PLUMB_API int wsplumb_rowbn_join_backward_renorm(const float *out, const float *dy, const float *dres, int n_slots,
+                                                 const float *x3, const float *xs, long long M, int C,
+                                                 const float *weight_n, const float *stats_n, const float *weight3,
+                                                 const float *stats3, const float *weight_s, const float *stats_s,
+                                                 const float *mask, int n_rois, int per, float *gout, float *dx3,
+                                                 float *dxs, float *dwb_n, float *dwb3, float *dwb_s, float *coef,
+                                                 void *workspace, size_t workspace_bytes, void *stream, int renorm) {
+    if (n_slots < 0 || renorm < 0 || renorm > 7) return 1;
+    return join_backward_impl(out, dy, dres, x3, xs, M, C, weight_n, stats_n, weight3, stats3, weight_s, stats_s, mask,
+                              n_rois, per, gout, dx3, dxs, dwb_n, dwb3, dwb_s, coef, workspace, workspace_bytes, stream,
+                              n_slots, renorm);
 }

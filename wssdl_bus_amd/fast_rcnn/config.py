@@ -26,7 +26,11 @@ cfg = __C
 __C.TRAIN = AttrDict()
 __C.TRAIN.LEARNING_RATE = 0.0005                    # config.py:40
 __C.TRAIN.WEIGHT_DECAY = 0.0005                     # config.py:46
-__C.TRAIN.GN_MIN_NUM_G = 8                          # :55  group norm: G = min(this, C // GN_MIN_CHS_PER_G)
+# batch renormalisation at every 'BN' site (network.py:123,160,342,384,507,519: renorm=cfg.TRAIN.USE_BRN).  The reference's
+# default is True (:54); here it is False, so that 'BN' stays the plain batch norm every golden and the benchmark
+# measure.  Read by rownorm.make_norm when a network is built.  Parity with TF's layer is UNPINNED.
+__C.TRAIN.USE_BRN = False                           # :54 (reference: True)
+__C.TRAIN.GN_MIN_NUM_G = 8                        # :55  group norm: G = min(this, C // GN_MIN_CHS_PER_G)
 __C.TRAIN.GN_MIN_CHS_PER_G = 4                      # :56
 __C.TRAIN.WS_IMS_PER_BATCH = 2                      # :49
 __C.TRAIN.WS_LOSS_USE_ADAPTIVE_SCALE_FACTOR = True  # :51

@@ -18,6 +18,7 @@ _warned = [False]
 
 _vp, _i, _ll, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t
 _RUN = [_vp, _vp, _f, _vp]          # running_mean, running_var, momentum, num_batches_tracked (struct Running)
+_REN = [_vp, _vp, _vp, ctypes.c_double, _vp, _vp]   # renorm_mean, renorm_stddev, renorm_weight, renorm_momentum, r, d (struct Renorm)
 
 
 def lib():
@@ -63,6 +64,17 @@ def lib():
         L.wsplumb_rowbn_join_backward_exit.restype = _i
         L.wsplumb_rowbn_join_backward_exit.argtypes = ([_vp, _vp, _i, _vp, _vp, _ll, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 8
                                                        + [_sz, _vp])
+        # the batch-renormalisation twins: the plain export's arguments, then the renorm state / factors
+        for name, extra in (("forward", _REN), ("stats", _REN), ("forward_entry", _REN), ("backward", [_vp, _vp]),
+                            ("backward_entry", [_vp, _vp])):
+            f = getattr(L, "wsplumb_rowbn_%s_renorm" % name)
+            f.restype = _i
+            f.argtypes = getattr(L, "wsplumb_rowbn_" + name).argtypes + extra
+        L.wsplumb_rowbn_join_forward_renorm.restype = _i
+        L.wsplumb_rowbn_join_forward_renorm.argtypes = L.wsplumb_rowbn_join_forward.argtypes + [_i, _vp, _vp]
+        L.wsplumb_rowbn_join_backward_renorm.restype = _i
+        L.wsplumb_rowbn_join_backward_renorm.argtypes = ([_vp] * 3 + [_i, _vp, _vp, _ll, _i] + [_vp] * 7 + [_i, _i]
+                                                         + [_vp] * 8 + [_sz, _vp, _i])
         L.wsplumb_tap_table_ints.restype = _i
         L.wsplumb_tap_table_ints.argtypes = []
         for name in ("wsplumb_tap_gather", "wsplumb_tap_col2im"):
@@ -104,7 +116,9 @@ def lib():
 # out for a measurement or a test.  Read at call time (switch), never cached: tests set them mid-process.
 SWITCHES = {
     "WSSDL_DISABLE_FUSED_BN": "no row batch-norm kernel at all: stock PyTorch ops (usable)",
-    "WSSDL_BN_TORCH_RUNNING_STATS": "running statistics by torch's lerp_, not the finish kernels (fused_running_stats)",
+    "WSSDL_BN_TORCH_RUNNING_STATS": "running statistics by torch's lerp_, not the finish kernels (fused_running_stats); "
+                                    "plain batch norms only: a renorm layer's state and running statistics are always "
+                                    "the finish kernel's",
     "WSSDL_HEAD_UNFUSED_ENTRY": "block 1's entry: torch's index_select forward, scatter and add, then the plain "
                                 "backward (entry_usable)",
     "WSSDL_HEAD_UNFUSED_EXIT": "the head's exit: the last join writes y, the slot-mean kernel reads it back, the mean's "
@@ -186,10 +200,19 @@ def fused_running_stats():
 def running_of(bn):
     """The `running` argument of rowbn_forward / rowbn_join_forward for a norm module: (running_mean, running_var,
     momentum, num_batches_tracked or None), or None when torch updates the buffers (fused_running_stats)."""
-    if not fused_running_stats():
+    if not fused_running_stats() and renorm_of(bn) is None:     # (a renorm layer's buffers are always the kernel's)
         return None
     mom = bn.momentum if bn.momentum is not None else 0.1
     return bn.running_mean, bn.running_var, mom, getattr(bn, "num_batches_tracked", None)
+
+
+def renorm_of(bn):
+    """The `renorm` argument of the fused forwards for a norm module: (renorm_mean, renorm_stddev, renorm_weight,
+    renorm_momentum) of a batch renormalisation layer (rownorm.RowBatchNorm / backbones.BatchNormAct2d built with
+    renorm=True), None for a plain batch norm."""
+    if not getattr(bn, "renorm", False):
+        return None
+    return bn.renorm_mean, bn.renorm_stddev, bn.renorm_weight, bn.renorm_momentum
 
 
 def _run_args(running):
@@ -201,32 +224,62 @@ def _run_args(running):
     return _p(rm), _p(rv), float(mom), _pn(nbt)
 
 
-def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False, *, running=None):
+def _state_ok(t, C):
+    return t.dtype == torch.float32 and t.shape == (C,) and t.is_contiguous()
+
+
+def _stats_block(x, renorm, n=None):
+    """The statistic block(s) of a fused forward over x [M, C]: [5, C] = mean, var, rstd, scale, shift, or for a batch
+    renormalisation layer [7, C], the step's r and d after them ([n, 5 or 7, C] for n norms)."""
+    rows = 7 if renorm is not None else 5
+    shape = (rows, x.shape[1]) if n is None else (n, rows, x.shape[1])
+    return torch.empty(shape, dtype=torch.float32, device=x.device)
+
+
+def _renorm_tail(renorm, stats):
+    """(export suffix, the arguments after the running statistics) of a single-norm forward: the layer's renorm state
+    (renorm_of) and rows 5 / 6 of its statistic block for r / d."""
+    if renorm is None:
+        return "", ()
+    rm, rs, rw, rho = renorm
+    assert all(_state_ok(t, stats.shape[1]) for t in (rm, rs, rw))
+    return "_renorm", (_p(rm), _p(rs), _p(rw), float(rho), _p(stats[5]), _p(stats[6]))
+
+
+def _rd(stats):
+    """(export suffix, the r / d arguments) of a single-norm backward from the forward's statistic block"""
+    return ("_renorm", (_p(stats[5]), _p(stats[6]))) if stats.shape[0] == 7 else ("", ())
+
+
+def rowbn_forward(x, weight, bias, eps, relu, mask=None, pos_major=False, *, running=None, renorm=None):
     """mask: [n_rois] f32 on x's device (0 = dead RoI), x = [n_rois * per, C] with row r belonging to RoI
     r // per, or r % n_rois when pos_major; returns (y, stats, count) where count is None without a mask,
     else a [1] tensor holding the number of live rows.  running: the layer's buffers to update in the same
-    kernels (running_of), or None."""
+    kernels (running_of), or None.  renorm: the state of a batch renormalisation layer (renorm_of), updated in the
+    same kernels; stats is then [7, C] (_stats_block) and scale / shift are the renorm layer's."""
     M, C = x.shape
     y = torch.empty_like(x)
-    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)   # mean, var, rstd, scale, shift
+    stats = _stats_block(x, renorm)
     count = torch.empty((1,), dtype=torch.float32, device=x.device) if mask is not None else None
     ws = _workspace(x)
-    _call("wsplumb_rowbn_forward", x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), int(relu),
+    suffix, ren = _renorm_tail(renorm, stats)
+    _call("wsplumb_rowbn_forward" + suffix, x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), int(relu),
           *_mask_args(mask, M), int(bool(pos_major) and mask is not None), _p(y), *[_p(stats[i]) for i in range(5)],
-          _pn(count), _p(ws), ws.numel(), tail=_run_args(running))
+          _pn(count), _p(ws), ws.numel(), tail=_run_args(running) + ren)
     return y, stats, count
 
 
-def rowbn_stats(x, weight, bias, eps, mask=None, pos_major=False, *, running=None):
+def rowbn_stats(x, weight, bias, eps, mask=None, pos_major=False, *, running=None, renorm=None):
     """rowbn_forward without its apply pass: (stats, count), the layer's output left to a consumer that applies
     stats[3] / stats[4] (scale / shift) while it reads x (tap_gather_norm)."""
     M, C = x.shape
-    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)
+    stats = _stats_block(x, renorm)
     count = torch.empty((1,), dtype=torch.float32, device=x.device) if mask is not None else None
     ws = _workspace(x)
-    _call("wsplumb_rowbn_stats", x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), *_mask_args(mask, M),
+    suffix, ren = _renorm_tail(renorm, stats)
+    _call("wsplumb_rowbn_stats" + suffix, x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), *_mask_args(mask, M),
           int(bool(pos_major) and mask is not None), *[_p(stats[i]) for i in range(5)], _pn(count), _p(ws), ws.numel(),
-          tail=_run_args(running))
+          tail=_run_args(running) + ren)
     return stats, count
 
 
@@ -248,9 +301,10 @@ def rowbn_backward(x, dy, weight, stats, relu, mask=None, pos_major=False):
     M, C = x.shape
     dx, dwb, coef = _backward_outputs(x)
     ws = _workspace(x)
-    _call("wsplumb_rowbn_backward", x.device, _p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]),
+    suffix, rd = _rd(stats)                        # a [7, C] block: the backward of a renorm layer
+    _call("wsplumb_rowbn_backward" + suffix, x.device, _p(x), _p(dy), M, C, _p(weight), _p(stats[0]), _p(stats[2]),
           _p(stats[3]), _p(stats[4]), int(relu), *_mask_args(mask, M), int(bool(pos_major) and mask is not None),
-          _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), ws.numel())
+          _p(dx), _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), ws.numel(), tail=rd)
     return dx, dwb[0], dwb[1]
 
 
@@ -260,7 +314,7 @@ def entry_usable(x):
     return not switch("WSSDL_HEAD_UNFUSED_ENTRY") and usable(x) and x.shape[0] < 2 ** 31
 
 
-def rowbn_forward_entry(x, weight, bias, eps, possel, n_slots, mask=None, *, running=None):
+def rowbn_forward_entry(x, weight, bias, eps, possel, n_slots, mask=None, *, running=None, renorm=None):
     """rowbn_forward(relu=True) of roi-major rows x [R * per, C] that also hands out, position-major, the rows of the
     positions possel names (int32 [per] on the device: the slot of each position or -1; every slot 0 .. n_slots - 1
     exactly once): returns (y, ys [n_slots * R, C], stats, count) with ys[possel[p] * R + roi] = y[roi * per + p],
@@ -272,12 +326,13 @@ def rowbn_forward_entry(x, weight, bias, eps, possel, n_slots, mask=None, *, run
     assert mask is None or mask.shape[0] == n_rois
     y = torch.empty_like(x)
     ys = torch.empty((n_slots * n_rois, C), dtype=torch.float32, device=x.device)
-    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)
+    stats = _stats_block(x, renorm)
     count = torch.empty((1,), dtype=torch.float32, device=x.device) if mask is not None else None
     ws = _workspace(x)
-    _call("wsplumb_rowbn_forward_entry", x.device, _p(x), M, C, _p(weight), _p(bias), float(eps), _mask_args(mask, M)[0],
-          n_rois, per, _p(possel), n_slots, _p(y), _p(ys), *[_p(stats[i]) for i in range(5)], _pn(count), _p(ws),
-          ws.numel(), tail=_run_args(running))
+    suffix, ren = _renorm_tail(renorm, stats)
+    _call("wsplumb_rowbn_forward_entry" + suffix, x.device, _p(x), M, C, _p(weight), _p(bias), float(eps),
+          _mask_args(mask, M)[0], n_rois, per, _p(possel), n_slots, _p(y), _p(ys), *[_p(stats[i]) for i in range(5)],
+          _pn(count), _p(ws), ws.numel(), tail=_run_args(running) + ren)
     return y, ys, stats, count
 
 
@@ -293,9 +348,10 @@ def rowbn_backward_entry(x, dy, dys, possel, n_slots, weight, stats, mask=None):
     assert mask is None or mask.shape[0] == n_rois
     dx, dwb, coef = _backward_outputs(x)
     ws = _workspace(x)
-    _call("wsplumb_rowbn_backward_entry", x.device, _p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight),
+    suffix, rd = _rd(stats)
+    _call("wsplumb_rowbn_backward_entry" + suffix, x.device, _p(x), _p(dy), _p(dys), _p(possel), n_slots, M, C, _p(weight),
           _p(stats[0]), _p(stats[2]), _p(stats[3]), _p(stats[4]), _mask_args(mask, M)[0], n_rois, per, _p(dx),
-          _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), ws.numel())
+          _p(dwb[0]), _p(dwb[1]), _p(coef), _p(ws), ws.numel(), tail=rd)
     return dx, dwb[0], dwb[1]
 
 
@@ -320,13 +376,16 @@ def slot_mean(x, n_slots):
     return feat
 
 
-def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None, exit_slots=None):
+def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None, exit_slots=None, renorm=None):
     """out = bn3(x3) + (bns(other) if bns else other); y = relu(bnn(out)): training-mode row batch norms over
     position-major rows, each bn a (weight, bias, eps) triple, mask as in rowbn_forward(pos_major=True).
     Returns (out, y, stats3, stats_s, stats_n, count or None), stats_s unwritten without bns; bit-identical to the
     separate calls.  running: None, or the running_of() of bn3, bns (None without it) and bnn.
     exit_slots = n_slots (the head's exit): y is never written; in its place comes feat [M / n_slots, C] =
-    slot_mean(y, n_slots), bit for bit."""
+    slot_mean(y, n_slots), bit for bit.
+    renorm: None, or the renorm_of() of bn3, bns and bnn (None for a plain norm among them): the three statistic
+    blocks are then [7, C] (_stats_block; rows 5 / 6 of a plain norm's are not written) and rowbn_join_backward needs
+    renorm_bits(renorm)."""
     M, C = x3.shape
     dev = x3.device
     assert other.shape == x3.shape and other.is_contiguous() and other.dtype == torch.float32
@@ -336,7 +395,9 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None, exi
         y = torch.empty((M // exit_slots, C), dtype=torch.float32, device=dev)
     else:
         y = torch.empty_like(x3)
-    stats = torch.empty((3, 5, C), dtype=torch.float32, device=dev)
+    if renorm is not None and all(r is None for r in renorm):
+        renorm = None
+    stats = _stats_block(x3, renorm, 3)
     count = torch.empty((1,), dtype=torch.float32, device=dev) if mask is not None else None
     ws_, bs_, es_ = bns if bns is not None else (None, None, 0.0)
     run = (None, None, None)
@@ -346,18 +407,35 @@ def rowbn_join_forward(x3, bn3, other, bns, bnn, mask=None, *, running=None, exi
         run = ((_vp * 6)(*[val(q) for r in a for q in r[:2]]), (_f * 3)(*[r[2] for r in a]),
                (_vp * 3)(*[val(r[3]) for r in a]))
     ws = _workspace(x3, join=True)
-    _call("wsplumb_rowbn_join_forward_exit" if exit_slots else "wsplumb_rowbn_join_forward", dev, _p(x3), _p(other), M, C,
+    if renorm is not None:
+        assert bns is not None or renorm[1] is None
+        assert all(_state_ok(t, C) for r in renorm if r is not None for t in r[:3])
+        name = "wsplumb_rowbn_join_forward_renorm"
+        tail = run + (int(exit_slots or 0),
+                      (_vp * 9)(*[t.data_ptr() if r is not None else None for r in renorm for t in (r or (0, 0, 0))[:3]]),
+                      (ctypes.c_double * 3)(*[float(r[3]) if r is not None else 0.0 for r in renorm]))
+    else:
+        name = "wsplumb_rowbn_join_forward_exit" if exit_slots else "wsplumb_rowbn_join_forward"
+        tail = run + ((int(exit_slots),) if exit_slots else ())
+    _call(name, dev, _p(x3), _p(other), M, C,
           _p(bn3[0]), _p(bn3[1]), float(bn3[2]), _pn(ws_), _pn(bs_), float(es_), _p(bnn[0]), _p(bnn[1]), float(bnn[2]),
           *_mask_args(mask, M), _p(out), _p(y), _p(stats[0]), _p(stats[1]) if bns is not None else None, _p(stats[2]),
-          _pn(count), _p(ws), ws.numel(), tail=run + ((int(exit_slots),) if exit_slots else ()))
+          _pn(count), _p(ws), ws.numel(), tail=tail)
     return out, y, stats[0], stats[1], stats[2], count
 
 
-def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, stats_s, mask=None, exit_slots=None):
+def renorm_bits(renorm):
+    """rowbn_join_backward's `renorm` from rowbn_join_forward's: bit 0 / 1 / 2 for a renorm bn3 / bns / bnn."""
+    return sum(1 << k for k, r in enumerate(renorm or ()) if r is not None)
+
+
+def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, stats_s, mask=None, exit_slots=None,
+                        renorm=0):
     """Gradients of rowbn_join_forward: dy for y, dres (or None) for out; xs / ws_ / stats_s None in the identity
     form.  Returns (g, dx3, dxs or None, dwb_n, dwb3, dwb_s or None), the dwb [2, C] = (dweight, dbias); g is the
     gradient of `other` in the identity form.  exit_slots = n_slots: dy is the gradient of feat [M / n_slots, C] and
-    dres must be None; bit-identical to the plain form on (dy * (1 / n_slots)) repeated over the slots."""
+    dres must be None; bit-identical to the plain form on (dy * (1 / n_slots)) repeated over the slots.
+    renorm: renorm_bits() of the forward's renorm argument (the [7, C] blocks of those norms carry their r and d)."""
     M, C = x3.shape
     if exit_slots:
         assert dres is None and dy.shape == (M // exit_slots, C) and dy.is_contiguous()
@@ -367,11 +445,17 @@ def rowbn_join_backward(out, dy, dres, x3, xs, wn, stats_n, w3, stats3, ws_, sta
     dwb = torch.empty((3, 2, C), dtype=torch.float32, device=x3.device)
     coef = torch.empty((9, C), dtype=torch.float32, device=x3.device)
     ws = _workspace(x3, join=True)
-    name, third = ("wsplumb_rowbn_join_backward_exit", int(exit_slots)) if exit_slots else \
-        ("wsplumb_rowbn_join_backward", _pn(dres))
-    _call(name, x3.device, _p(out), _p(dy), third, _p(x3), _pn(xs), M, C, _p(wn),
+    tail = ()
+    if renorm:
+        assert all(st is None or st.shape[0] == 7 for st in (stats_n, stats3, stats_s))
+        name, third, tail = "wsplumb_rowbn_join_backward_renorm", (_pn(dres), int(exit_slots or 0)), (int(renorm),)
+    elif exit_slots:
+        name, third = "wsplumb_rowbn_join_backward_exit", (int(exit_slots),)
+    else:
+        name, third = "wsplumb_rowbn_join_backward", (_pn(dres),)
+    _call(name, x3.device, _p(out), _p(dy), *third, _p(x3), _pn(xs), M, C, _p(wn),
           _p(stats_n), _p(w3), _p(stats3), _pn(ws_), _pn(stats_s), *_mask_args(mask, M), _p(g), _p(dx3), _pn(dxs),
-          _p(dwb[0]), _p(dwb[1]), _p(dwb[2]) if dual else None, _p(coef), _p(ws), ws.numel())
+          _p(dwb[0]), _p(dwb[1]), _p(dwb[2]) if dual else None, _p(coef), _p(ws), ws.numel(), tail=tail)
     return g, dx3, dxs, dwb[0], dwb[1], dwb[2] if dual else None
 
 
@@ -714,7 +798,7 @@ class TapConv3x3Fn(torch.autograd.Function):
     position-major [oh*ow*R, c_o] output.  One GEMM per class group (torch's hipBLASLt); patches, weights
     and their gradients move between the dense and the class-packed layouts in taps.hip.
 
-    With norm_w / norm_b (a row batch norm's weight and bias; eps, roi_mask and running as rowbn_forward takes them)
+    With norm_w / norm_b (a row batch norm's weight and bias; eps, roi_mask, running and renorm as rowbn_forward takes them)
     x is instead the RAW rows [h*w*R, C] in front of that norm + ReLU -- a bottleneck's conv1 output -- and the
     convolution runs over relu(bn(x)): the forward takes the norm's statistics (two of the layer's three kernels,
     running statistics included) and the patch gather applies scale, shift and ReLU while it copies
@@ -723,14 +807,15 @@ class TapConv3x3Fn(torch.autograd.Function):
     (out, mean, var, live-row count) then; bit-identical to the separate layers."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, plan, in_pm, R, norm_w=None, norm_b=None, eps=0.0, roi_mask=None, running=None):
+    def forward(ctx, x, weight, bias, plan, in_pm, R, norm_w=None, norm_b=None, eps=0.0, roi_mask=None, running=None,
+                renorm=None):
         C, CO = weight.shape[1] // 9, weight.shape[0]
         x = x.contiguous()
         assert x.shape[-1] == C and x.numel() == plan.h * plan.w * R * C and (not in_pm or plan.h == plan.oh)
         normed = norm_w is not None
         if normed:
             x = x.view(-1, C)
-            stats, count = rowbn_stats(x, norm_w, norm_b, eps, roi_mask, in_pm, running=running)
+            stats, count = rowbn_stats(x, norm_w, norm_b, eps, roi_mask, in_pm, running=running, renorm=renorm)
             cols = tap_gather_norm(x, plan, in_pm, R, stats[3], stats[4], roi_mask)
         else:
             cols = tap_gather(x, plan, in_pm, R)
@@ -761,7 +846,7 @@ class TapConv3x3Fn(torch.autograd.Function):
         if normed and need_x:
             x, norm_w, stats, roi_mask = ctx.saved_tensors[2:]
             dx, dwn, dbn = rowbn_backward(x, dx.view(x.shape), norm_w, stats, True, roi_mask, in_pm)
-        return dx, dw, db, None, None, None, dwn, dbn, None, None, None
+        return dx, dw, db, None, None, None, dwn, dbn, None, None, None, None
 
 # ---- L2 weight decay over all the decayed parameters as one device op (csrc/plumbing/l2decay.hip) ----
 _L2_CHUNK = 4096                    # floats per chunk: keep in sync with CHUNK of l2decay.hip

@@ -19,7 +19,14 @@ class BatchNormAct2d(nn.BatchNorm2d):
     """nn.BatchNorm2d (same parameters and buffers) whose forward can also apply the ReLU that
     follows it.  On channels_last GPU tensors in training mode the layer runs on the fused row
     batch-norm kernels of the plumbing library ([N,H,W,C] is an [N*H*W, C] row matrix there);
-    anywhere else it is the stock module followed by F.relu."""
+    anywhere else it is the stock module followed by F.relu.  `renorm=True`: batch renormalisation
+    (rownorm.init_renorm) on the same kernels; where they do not take the tensor, rownorm.stock_rows over the rows."""
+    renorm = False
+
+    def __init__(self, *args, renorm=False, **kwargs):
+        super().__init__(*args, **kwargs)
+        if renorm:
+            rownorm.init_renorm(self, self.num_features)
 
     def forward(self, x, relu=False):
         if self.training and x.is_cuda and self.track_running_stats:
@@ -27,15 +34,20 @@ class BatchNormAct2d(nn.BatchNorm2d):
             if r2 is not None and _plumbing.usable(r2):
                 run, done = rownorm.running((self,), None, r2.shape[0])
                 y, mean, var, n = rownorm._FusedRowBatchNormFn.apply(r2, self.weight, self.bias, self.eps, bool(relu),
-                                                                     None, False, run)
+                                                                     None, False, run,
+                                                                     *((rownorm.renorm((self,)),) if self.renorm else ()))
                 done(((mean, var),), n)
                 return _nchw(y, x)
+        if self.renorm and self.training:
+            n, c, h, w = x.shape
+            y = rownorm.stock_rows(self, x.permute(0, 2, 3, 1).reshape(-1, c), relu)
+            return y.view(n, h, w, c).permute(0, 3, 1, 2)
         y = super().forward(x)
         return F.relu(y) if relu else y
 
 
 def _bn(c):
-    return BatchNormAct2d(c, eps=1e-3, momentum=0.01)
+    return BatchNormAct2d(c, eps=1e-3, momentum=0.01, renorm=bool(rownorm.cfg.TRAIN.USE_BRN))
 
 
 class GroupNormAct2d(rownorm.RowGroupNorm):

@@ -81,7 +81,7 @@ def _norm_tap_conv(c1, c2, rows, plan, in_pm, R, mask):
     bn = c1.bn
     run, done = rownorm.running((bn,), mask, rows.shape[0])
     y, mean, var, n = _plumbing.TapConv3x3Fn.apply(rows, c2.weight, None, plan, in_pm, R, bn.weight, bn.bias, bn.eps,
-                                                   mask, run)
+                                                   mask, run, *((rownorm.renorm((bn,)),) if bn.renorm else ()))
     done(((mean, var),), n)
     return y
 
@@ -210,7 +210,8 @@ def _entry_pre_act(bn, x, plan, s):
     r, h, w, c = x.shape
     mask, _ = rownorm.live_mask(r * h * w)
     run, done = rownorm.running((bn,), mask, r * h * w)
-    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, mask, plan, s, (h, w), run)
+    y, ys, mean, var, n = _EntryNormFn.apply(x.reshape(-1, c), bn.weight, bn.bias, bn.eps, mask, plan, s, (h, w), run,
+                                             *((rownorm.renorm((bn,)),) if bn.renorm else ()))
     done(((mean, var),), n)
     return y.view(r, h, w, c), ys
 
