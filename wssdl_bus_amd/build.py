@@ -111,7 +111,7 @@ def build(force=False, verbose=True):
 PLUMB_OUT = os.path.join(HERE, "libwssdl_plumbing_hip.so")
 PLUMB_SOURCES = [os.path.join("plumbing", "rowbn.hip"), os.path.join("plumbing", "im2col.hip"),
                  os.path.join("plumbing", "taps.hip"), os.path.join("plumbing", "l2decay.hip"),
-                 os.path.join("plumbing", "groupnorm.hip")]
+                 os.path.join("plumbing", "groupnorm.hip"), os.path.join("plumbing", "optim.hip")]
 PLUMB_HEADERS = [os.path.join("plumbing", "bn_math.hip.h")]
 PLUMB_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-fvisibility=hidden",
                "-Wall"]

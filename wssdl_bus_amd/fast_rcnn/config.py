@@ -25,6 +25,7 @@ cfg = __C
 
 __C.TRAIN = AttrDict()
 __C.TRAIN.LEARNING_RATE = 0.0005                    # config.py:40
+__C.TRAIN.MOMENTUM = 0.9                            # config.py:41  SolverWrapper(opt='sgd'): Nesterov momentum
 __C.TRAIN.WEIGHT_DECAY = 0.0005                     # config.py:46
 # batch renormalisation at every 'BN' site (network.py:123,160,342,384,507,519: renorm=cfg.TRAIN.USE_BRN).  The reference's
 # default is True (:54); here it is False, so that 'BN' stays the plain batch norm every golden and the benchmark

@@ -3,8 +3,8 @@
 Reference: code/lib/fast_rcnn/train_bus.py:184-270 (alternating losses), :603-678 (combined
 losses), :286-301 / :694-705 (optimisers and the per-variable sum of the two gradient sets),
 :334-394 (one alternating iteration = a supervised step then a weak step).  Only what drives
-the hot path's backward is restated here; data loading, LR
-schedules, snapshots and logging are out of scope.
+the hot path's backward is restated here, with the optimisers and
+learning-rate schedules of fast_rcnn/optim.py; data loading, snapshots and logging are out of scope.
 """
 import os
 
@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from ..mil import core as mil_core
 from ..networks import _plumbing
 from ..roi_pooling_layer import roi_pooling_op
+from . import optim
 from .config import cfg
 
 
@@ -142,19 +143,49 @@ def supervised_loss(layers, params, n_sup=None):
 # ------------------------------------------------------------ train steps ---
 
 class SolverWrapper(object):
-    """The part of the reference's SolverWrapper (train_bus.py:97-131) that a step needs:
-    the network, Adam(eps=0.1) (:286-289,:694-695), the global step, and -- new in this
-    implementation -- gradient averaging across data-parallel ranks."""
+    """The part of the reference's SolverWrapper (train_bus.py:97-131) that a step needs: the network, the
+    optimiser, the learning-rate schedule, the global step, and -- new in this implementation -- gradient
+    averaging across data-parallel ranks.
 
-    def __init__(self, network, lr=None, dist_ctx=None):
+    opt: None (the default) is torch.optim.Adam(lr, eps=0.1).  That is NOT the reference's Adam: torch adds eps to
+    sqrt(v) / sqrt(1 - b2^t), TensorFlow to sqrt(v), and with eps = 0.1 above most gradients torch's first step is
+    about 30 times TF's (fast_rcnn/optim.py).  It stays the default because the benchmark and every golden step
+    measure it; flipping it is a separate decision.  'adam', 'amsgrad' and 'sgd' are the reference's `--opt`
+    choices (:286-294, :694-697) in TF's arithmetic, one HIP launch per step (optim.ReferenceOptimizer); 'sgd'
+    reads cfg.TRAIN.MOMENTUM.  'amsgrad' is UNPINNED: the reference's module is not in its tree.
+
+    lr_scheduling: 'const'; 'pc', 0.1 * lr once the global step has passed int(0.75 * max_iters) (:276-279; needs
+    max_iters); 'rop', optim.ReduceLROnPlateau fed by on_val_end(val_loss) (:281).  The current rate is written
+    into whichever optimiser takes the step, right before it.
+
+    Alternating mode under 'sgd': the reference's supervised op is minimize(loss, global_step=global_step) (:293),
+    so BOTH halves of an iteration count the global step (two per iteration); under the other optimisers only the
+    weak half does.  The MIL scale factor 1 - 0.99 * 0.9^floor(step / 2000) and the 'pc' schedule read that count,
+    so this is reproduced."""
+
+    OPTS = (None, 'adam', 'amsgrad', 'sgd')
+    SCHEDULES = ('const', 'pc', 'rop')
+
+    def __init__(self, network, lr=None, dist_ctx=None, opt=None, lr_scheduling='const', max_iters=None):
+        if opt not in self.OPTS:
+            raise ValueError("opt=%r: one of %r" % (opt, self.OPTS))
+        if lr_scheduling not in self.SCHEDULES:
+            raise ValueError("lr_scheduling=%r: one of %r" % (lr_scheduling, self.SCHEDULES))
+        if lr_scheduling == 'pc' and max_iters is None:
+            raise ValueError("lr_scheduling='pc' needs max_iters")
         self.net = network
         self.lr = cfg.TRAIN.get('LEARNING_RATE', 0.0005) if lr is None else lr
+        self.opt, self.lr_scheduling, self.max_iters = opt, lr_scheduling, max_iters
+        self.rop = None
+        if lr_scheduling == 'rop':
+            self.rop = optim.ReduceLROnPlateau(self.lr, factor=0.5, patience=5, mode='min', epsilon=1e-3,
+                                               cooldown=0, min_lr=0)
         self.params = [p for p in network.parameters() if p.requires_grad]
         # combined mode: ONE Adam applies the summed gradients and counts the global step
         # (:694-705).  Alternating mode: the supervised op is Adam.minimize(loss) WITHOUT a
         # global step, the weak op a SECOND Adam whose apply_gradients counts it (:286-301);
-        # the two keep their own moments and bias-correction powers.
-        self.optimizer = self._adam()
+        # the two keep their own moments and bias-correction powers.  (Likewise for every `opt`.)
+        self.optimizer = self._make_optimizer()
         self.optimizer_ws = None                  # created by the first alternating iteration
         self.global_step = 0
         self.dist = dist_ctx
@@ -174,13 +205,33 @@ class SolverWrapper(object):
         return torch.optim.Adam(self.params, lr=self.lr, eps=0.1, fused=True) if fused \
             else torch.optim.Adam(self.params, lr=self.lr, eps=0.1)
 
+    def _make_optimizer(self):
+        return self._adam() if self.opt is None else optim.make(self.opt, self.params, self.lr)
+
+    def current_lr(self):
+        """The learning rate of the step about to be taken (train_bus.py:338-344, :739-745)."""
+        if self.lr_scheduling == 'pc':
+            return optim.piecewise_lr(self.lr, self.global_step, self.max_iters)
+        if self.lr_scheduling == 'rop':
+            return self.rop.get_cur_lr()
+        return self.lr
+
+    def on_val_end(self, val_loss):
+        """After a validation pass: feeds the 'rop' schedule (train_bus.py:70-91); nothing under the others."""
+        if self.rop is not None:
+            self.rop.on_val_end(val_loss)
+
     def _apply(self, optimizer=None, count_step=True):
+        optimizer = optimizer or self.optimizer
+        if self.lr_scheduling != 'const':
+            for group in optimizer.param_groups:
+                group['lr'] = self.current_lr()
         if self.overlap is not None:
             self.overlap.finish()
         elif self.dist is not None:
             self.dist.allreduce_gradients(self.params)
         roi_pooling_op.poll_flags()               # deferred error flags of the RoI-pool pair: no read-back
-        (optimizer or self.optimizer).step()      # parameters whose grad is None are skipped,
+        optimizer.step()                          # parameters whose grad is None are skipped,
         self.optimizer.zero_grad(set_to_none=True)  # like apply_gradients with a None gradient
         if count_step:
             self.global_step += 1
@@ -242,9 +293,10 @@ class SolverWrapper(object):
         """One alternating iteration (train_bus.py:334-394): a supervised step on `loss`, then
         a weak step on the MIL loss alone with is_ws=True."""
         losses = self.supervised_backward(blobs_s)
-        self._apply(self.optimizer, count_step=False)              # train_op_s: no global_step
+        # train_op_s: no global_step -- except under 'sgd', whose minimize() is given it (:293)
+        self._apply(self.optimizer, count_step=self.opt == 'sgd')
         losses['mil_cross_entropy'] = self.weak_backward(blobs_ws)
         if self.optimizer_ws is None:
-            self.optimizer_ws = self._adam()
+            self.optimizer_ws = self._make_optimizer()
         self._apply(self.optimizer_ws, count_step=True)            # train_op_ws counts the step
         return losses

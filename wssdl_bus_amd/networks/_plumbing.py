@@ -1,6 +1,6 @@
 """ctypes binding of ``libwssdl_plumbing_hip.so``: the fused row batch-norm (+ReLU) and residual-join kernels
 (``csrc/plumbing/rowbn.hip``), the group-norm kernels (``groupnorm.hip``), the 3x3 patch kernels (``im2col.hip``) and the class-packed 3x3 convolutions
-(``taps.hip``) of the two networks, and the one-launch L2 weight decay of the training step (``l2decay.hip``).  Plumbing around the hot path, not the drop-in C ABI; when the library has not
+(``taps.hip``) of the two networks, the one-launch L2 weight decay of the training step (``l2decay.hip``) and the one-launch reference optimisers (``optim.hip``, bound by fast_rcnn/optim.py).  Plumbing around the hot path, not the drop-in C ABI; when the library has not
 been built the networks fall back to stock PyTorch ops (slower, same maths) and say so once.  Imports no sibling
 module: networks/rownorm.py, backbones.py and roi_head.py build on it, in that order.  Every export goes through
 `_call`; the `*_usable` predicates, `fused_running_stats`, `running_of`, TAPS_MIN_ROIS and TAP_GEMM_GROUPED are
@@ -108,6 +108,10 @@ def lib():
         L.wsplumb_l2decay_forward.argtypes = [_vp, _i, _vp, _f, _vp, _vp]
         L.wsplumb_l2decay_backward.restype = _i
         L.wsplumb_l2decay_backward.argtypes = [_vp, _i, _vp, _f, _vp, _vp]
+        L.wsplumb_optim_chunk.restype = _i
+        L.wsplumb_optim_chunk.argtypes = []
+        L.wsplumb_optim_step.restype = _i
+        L.wsplumb_optim_step.argtypes = [_i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_f] * 6 + [_vp]
         _lib = L
     return _lib
 
@@ -131,6 +135,8 @@ SWITCHES = {
     "WSSDL_HEAD_DENSE_3X3": "the head's 3x3 convolutions on the dense patch route (taps_usable)",
     "WSSDL_DISABLE_FUSED_GN": "no group-norm kernel: stock PyTorch ops (groupnorm_usable)",
     "WSSDL_TORCH_L2_DECAY": "the L2 weight decay by torch's per-parameter multiply / sum chain (l2decay_usable)",
+    "WSSDL_TORCH_OPTIM": "the reference optimisers (fast_rcnn/optim.py) as a per-parameter chain of torch ops, not the "
+                         "one-launch kernel (optim.hip_usable)",
 }
 
 
