@@ -614,6 +614,37 @@ WSSDL_API int wssdl_post_detections_batched(const float *rois, const float *scor
                      int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
                      wssdl_stream_t stream);
 
+/* The class-agnostic variant of both (cfg.TEST.CLS_AGNOSTIC_NMS, fast_rcnn/test_bus.py:371-384): after the
+ * per-class step above (score filter, NMS at nms_thresh, kept rows in descending score order) the classes' kept
+ * rows are concatenated in class order j = 1 .. num_classes-1 and the same greedy NMS runs once more over that
+ * union, at the same nms_thresh, visiting it in descending score order (equal scores: the later row of the
+ * concatenation first, the tie-break of every ranking here).  Class j's detections are the union's survivors that
+ * came from class j, still in descending score order; the cap then applies to them exactly as above.
+ * Arguments, output layout (dets, counts, the -1 flag of an image with more rows than max_rows_per_image) and the
+ * limits are those of the per-class pair, so whatever consumes its output (WSSDL_EVAL_BATCHED below) takes this one
+ * unchanged.  One limit more: the union of one image is ONE NMS segment of
+ *   U = (num_classes-1) * max_rows_per_image <= WSSDL_POST_AGNOSTIC_MAX_UNION
+ * items, ranked and swept by the kernels the proposal layer runs at 12000 candidates per image; its suppression
+ * matrix takes U * ceil(U / 1024) * 128 bytes per image of the workspace (18.4 MB at the limit).  Beyond the limit:
+ * WSSDL_ERR_INVALID_ARGUMENT.  One set of launches for all images and classes, no host read-back.
+ * Every image's output is bit for bit that of the single-image call on its rows alone.  With num_classes == 2 the
+ * second pass finds nothing left to suppress, and the output is bit for bit the per-class one as long as no two kept
+ * rows of an image have the same score: among equal scores the union ranks the LATER kept row first (the tie-break
+ * above, applied to the concatenation as the reference's nms call sees it), which is the reverse of their per-class
+ * order.
+ * The single-image call is the case n_images = 1, rois = NULL, max_rows_per_image = R. */
+#define WSSDL_POST_AGNOSTIC_MAX_UNION 12000
+WSSDL_API size_t wssdl_post_detections_agnostic_workspace_bytes(int R, int num_classes);
+WSSDL_API int wssdl_post_detections_agnostic(const float *scores, const float *boxes, int R, int num_classes,
+                     float score_thresh, double nms_thresh, int max_per_image, float *dets,
+                     int32_t *counts, void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
+WSSDL_API size_t wssdl_post_detections_agnostic_batched_workspace_bytes(int n_images, int max_rows_per_image,
+                     int num_classes);
+WSSDL_API int wssdl_post_detections_agnostic_batched(const float *rois, const float *scores, const float *boxes, int R,
+                     int n_images, int max_rows_per_image, int num_classes, float score_thresh, double nms_thresh,
+                     int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
+                     wssdl_stream_t stream);
+
 /* ---------------------------------------------------------------- evaluation ---
  * Detection evaluation, datasets/voc_eval_bus.py + the 44 calls of datasets/bus.py:_do_python_eval in one pass:
  * for every class j = 1 .. n_classes-1 the PASCAL VOC precision / recall curve and AP (11-point and area), and for

@@ -2,7 +2,10 @@
 """Random post-detection cases (f3: per-class score filter, NMS 0.3, max_per_image cap; fast_rcnn/test_bus.py:360-401): the one-call
 device op and the step-by-step form against the NumPy formulas with the oracle's NMS -- random row counts (0 ... 2500), 2 ... 8
 classes, score thresholds, caps (none, small, larger than the survivors), pairwise distinct scores.
-    python3 tools/post_detect_fuzz.py [--cases 60] [--seed 0]"""
+--agnostic: the same cases under cfg.TEST.CLS_AGNOSTIC_NMS (the second NMS over the classes' kept rows, test_bus.py:371-384)
+against the same NumPy formulas with the union pass between the per-class step and the cap; the device op runs wherever
+(K-1) * R is within its union bound, and the last line counts the cases beyond it (checked in the step-by-step form only).
+    python3 tools/post_detect_fuzz.py [--cases 60] [--seed 0] [--agnostic]"""
 import argparse
 import os
 import sys
@@ -12,15 +15,18 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from oracle import np_oracle as O  # noqa: E402
+from wssdl_bus_amd._lib import POST_AGNOSTIC_MAX_UNION  # noqa: E402
 from wssdl_bus_amd.fast_rcnn.config import cfg  # noqa: E402
-from wssdl_bus_amd.fast_rcnn.test_bus import postprocess_detections  # noqa: E402
+from wssdl_bus_amd.fast_rcnn.post_detections import postprocess_detections  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--cases", type=int, default=60)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--agnostic", action="store_true", help="run the cases under cfg.TEST.CLS_AGNOSTIC_NMS")
 args = ap.parse_args()
+cfg.TEST.CLS_AGNOSTIC_NMS = bool(args.agnostic)
 rs = np.random.RandomState(args.seed)
-bad = 0
+bad = beyond = 0
 for k in range(args.cases):
     R = int(rs.choice([0, 1, 2, 63, 64, 65, 300, 1000, 2500])) if k % 3 else int(rs.randint(1, 1200))
     K = int(rs.randint(2, 9))
@@ -35,6 +41,13 @@ for k in range(args.cases):
         inds = np.where(scores[:, j] > thresh)[0]
         d = np.hstack((boxes[inds, 4 * j:4 * j + 4], scores[inds, j:j + 1])).astype(np.float32)
         want[j] = d[O.nms(d, cfg.TEST.NMS)] if len(d) else d
+    if args.agnostic:
+        # test_bus.py:371-384: the classes' kept rows in class order, tagged; one more NMS; split by tag
+        alld = np.vstack([np.hstack((want[j].reshape(-1, 5), np.full((len(want[j]), 1), j, np.float32))) for j in range(1, K)])
+        if len(alld):
+            alld = alld[O.nms(np.ascontiguousarray(alld[:, :5]), cfg.TEST.NMS)]
+        want = {j: alld[alld[:, 5] == j][:, :5] for j in range(1, K)}
+        beyond += (K - 1) * R > POST_AGNOSTIC_MAX_UNION
     alls = np.hstack([want[j][:, 4] for j in range(1, K)])
     if cap > 0 and len(alls) > cap:
         th = np.sort(alls)[-cap]
@@ -56,5 +69,6 @@ for k in range(args.cases):
         print("MISMATCH case %d R %d K %d thresh %.2f cap %d" % (k, R, K, thresh, cap), flush=True)
     if (k + 1) % 20 == 0:
         print("case %d ok so far (%d mismatches)" % (k + 1, bad), flush=True)
-print("cases %d mismatches %d" % (args.cases, bad))
+print("cases %d mismatches %d" % (args.cases, bad) +
+      (" (device op in %d cases, %d beyond the union bound)" % (args.cases - beyond, beyond) if args.agnostic else ""))
 sys.exit(1 if bad else 0)

@@ -18,6 +18,7 @@ ROUND_CUDA, ROUND_CPU = 0, 1
 DATASET_SNUBH, DATASET_SNUBH_FG, DATASET_FG_ONLY = 0, 1, 2
 MAX_ANCHORS, MAX_GT = 32, 64
 EVAL_QUANTISE, EVAL_BATCHED = 1, 2
+POST_AGNOSTIC_MAX_UNION = 12000         # WSSDL_POST_AGNOSTIC_MAX_UNION: (K-1) * rows per image of the class-agnostic op
 
 # every symbol include/wssdl_bus_hip.h declares: (restype, argtypes)
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
@@ -102,6 +103,10 @@ SYMBOLS = {
     "wssdl_post_detections": (_i, [_vp, _vp, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_post_detections_batched_workspace_bytes": (_sz, [_i, _i, _i]),
     "wssdl_post_detections_batched": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wssdl_post_detections_agnostic_workspace_bytes": (_sz, [_i, _i]),
+    "wssdl_post_detections_agnostic": (_i, [_vp, _vp, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wssdl_post_detections_agnostic_batched_workspace_bytes": (_sz, [_i, _i, _i]),
+    "wssdl_post_detections_agnostic_batched": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_eval_detections_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wssdl_eval_detections": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _d,
                                    _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

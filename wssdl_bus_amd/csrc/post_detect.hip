@@ -19,6 +19,15 @@
 // start): the keys' tie-break and the kept list are then those of the single-image call on that image's rows, so
 // every image's output is bit for bit the one wssdl_post_detections gives on its rows alone.
 // wssdl_post_detections itself is the one-image case (no RoI blob: rows 0 .. R-1, P = R).
+//
+// Class-agnostic variant (cfg.TEST.CLS_AGNOSTIC_NMS, test_bus.py:371-384): after the per-class step the classes'
+// kept rows are concatenated in class order and a second NMS runs over that union; class j keeps the union's
+// survivors that came from it.  Here the union of one image is one more segment, of pitch U = (K-1) * P (padded to
+// a multiple of 16): item u = c * P + p is kept position p of class c, ranked by score_key(score, u).  u grows with
+// the position in the reference's concatenation, so the order -- ties included -- is that of the NMS on the
+// compacted array, whatever P is: the batched and the single-image call agree bit for bit here too.  The same
+// ranking and mask + sweep launches run over the n_images union segments, and one workgroup per image takes the cap
+// from the union's kept list and splits that list by class (c = u / P) in order.
 #include "nms.hip.h"
 #include "select.hip.h"
 
@@ -31,10 +40,8 @@ struct PostWs {
     int *img_lo, *img_hi;       // per image: first and last row of its run in the RoI blob (batched calls)
 };
 
-// nseg = n_images * (num_classes - 1) segments of P rows each
-static size_t carve_post(void *ws, int n_images, int P, int nc, PostWs *out) {
-    Carver c(ws);
-    PostWs w;
+// nseg = n_images * nc segments of P rows each
+static void carve_segments(Carver &c, int n_images, int P, int nc, PostWs &w) {
     const int ncb = nms_mask_pitch(P);
     const size_t nseg = (size_t)n_images * nc;
     w.keys = c.take<unsigned long long>(nseg * P);
@@ -52,6 +59,13 @@ static size_t carve_post(void *ws, int n_images, int P, int nc, PostWs *out) {
     w.summ = c.take<unsigned long long>(nms_summary_alloc_words((int)nseg, P));
     w.img_lo = c.take<int>((size_t)n_images + 64);
     w.img_hi = c.take<int>((size_t)n_images + 64);
+}
+
+// the (image, class) segments of the per-class step: nc = num_classes - 1
+static size_t carve_post(void *ws, int n_images, int P, int nc, PostWs *out) {
+    Carver c(ws);
+    PostWs w;
+    carve_segments(c, n_images, P, nc, w);
     if (out) *out = w;
     return c.off;
 }
@@ -192,18 +206,167 @@ __global__ __launch_bounds__(CAP_BLOCK) void post_cap_kernel(const int *__restri
     if (t < nc && t < 64) counts[seg0 + t] = s_count[t];
 }
 
+// ---------------------------------------------------------------------------------- class-agnostic union ---
+// union pitch: (K-1) * P padded to a multiple of 16 (the alignment contract of the fused mask + sweep, nms.hip.h)
+static int union_pitch(int P, int nc) { return (int)(((long long)nc * P + 15) / 16 * 16); }
+
+// the per-class slices first (the same offsets as the per-class op), behind them the same set for one segment of
+// pitch U per image (its img_lo / img_hi, 2 x 256-byte slices for up to 64 images, stay unused: the union reads the
+// per-class pair), and the union's scores [n_images, U].
+// The union's boxes and scores are written for the items with a non-zero key only.  Nothing else is read: the box
+// gather reads boxes[sorted_index[q]] for q < n_sorted, and sorted_index[q] is the low word of a non-zero key; the
+// cap kernel reads item keep[q] for q < num_keep, a value of sorted_index.
+static size_t carve_post_agnostic(void *ws, int n_images, int P, int nc, PostWs *pw, PostWs *uw, float **uscores) {
+    Carver c(ws);
+    PostWs w, u;
+    const int U = union_pitch(P, nc);
+    carve_segments(c, n_images, P, nc, w);
+    carve_segments(c, n_images, U, 1, u);
+    float *us = c.take<float>((size_t)n_images * U);
+    if (pw) *pw = w;
+    if (uw) *uw = u;
+    if (uscores) *uscores = us;
+    return c.off;
+}
+
+// keys of image img's union segment: item u = c * P + p is kept position p of class c -> score_key(score, u), its
+// box and its score side by side; 0 for p >= num_keep[c], for the padding beyond (K-1) * P and for a kept entry
+// that does not name a row of the image.  Also the initialisations the ranking expects.
+__global__ __launch_bounds__(256) void post_union_keys_kernel(const int *__restrict__ lo, const int *__restrict__ hi,
+                                                              const float *__restrict__ scores, const float *__restrict__ cboxes,
+                                                              const int *__restrict__ keep, const int *__restrict__ num_keep,
+                                                              int R, int K, int n_images, int P, int U,
+                                                              unsigned long long *__restrict__ ukeys, float *__restrict__ uboxes,
+                                                              float *__restrict__ uscores, int *__restrict__ sorted_index,
+                                                              int *__restrict__ n_sorted, int *__restrict__ cand_fill) {
+    const int nc = K - 1;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_images) { n_sorted[i] = 0;  cand_fill[i] = 0; }
+    if (i >= (long long)n_images * U) return;
+    const int img = (int)(i / U), u = (int)(i - (long long)img * U);
+    sorted_index[i] = -1;
+    ukeys[i] = 0ull;
+    if (u >= nc * P) return;
+    const int c = u / P, p = u - c * P;
+    const size_t seg = (size_t)img * nc + c;
+    if (p >= num_keep[seg]) return;
+    int start, count;
+    image_rows(lo, hi, img, R, start, count);
+    const int row = keep[seg * P + p];
+    if (row < 0 || row >= P || row >= count) return;
+    const float s = scores[((size_t)start + row) * K + c + 1];
+    const float *b = cboxes + (seg * P + row) * 4;
+    float *o = uboxes + (size_t)i * 4;
+    o[0] = b[0];  o[1] = b[1];  o[2] = b[2];  o[3] = b[3];
+    uscores[i] = s;
+    ukeys[i] = score_key(s, (unsigned)u);
+}
+
+// One workgroup per image: the max_per_image-th largest score of the union's kept list (test_bus.py:389-392), then
+// the list split by class: kept position q holds item u = c * P + p, and class c receives its items in the order
+// of the list, so every class stays in descending score order and "score >= image_thresh" keeps a prefix of it.
+// An image with more rows than P reports counts[i, 0] = -1.
+constexpr int CAP_WAVES = CAP_BLOCK / 64;
+
+__global__ __launch_bounds__(CAP_BLOCK) void post_union_cap_kernel(const int *__restrict__ lo, const int *__restrict__ hi,
+                                                                   const float *__restrict__ uboxes, const float *__restrict__ uscores,
+                                                                   const int *__restrict__ ukeep, const int *__restrict__ unum_keep,
+                                                                   int R, int K, int P, int U, int max_per_image,
+                                                                   float *__restrict__ dets, int *__restrict__ counts) {
+    __shared__ SelectScratch<CAP_LIST> sc;
+    __shared__ int s_count[64], s_base[64];
+    __shared__ int s_wave[CAP_WAVES][64];
+    const int nc = K - 1, t = threadIdx.x, img = blockIdx.x, lane = t & 63, wave = t >> 6;
+    int start, count;
+    image_rows(lo, hi, img, R, start, count);
+    const size_t seg0 = (size_t)img * nc;
+    if (count > P) {            // the same for the whole workgroup: no barrier is skipped by part of it
+        if (t < nc) counts[seg0 + t] = t == 0 ? -1 : 0;
+        return;
+    }
+    const int live = nc * P;                                     // items of the union; U - live padding slots
+    const int nk = min(max(unum_keep[img], 0), live);
+    const int *kp = ukeep + (size_t)img * U;
+    const float *ub = uboxes + (size_t)img * U * 4;
+    const float *us = uscores + (size_t)img * U;
+    float *d = dets + seg0 * P * 5;
+    if (t < 64) { s_count[t] = 0;  s_base[t] = 0; }
+    // item q = kept position q of the union; its key: score bits over a unique low word
+    auto key_at = [&](int q, unsigned long long &v) -> bool {
+        if (q >= nk) return false;
+        const int u = kp[q];
+        if ((unsigned)u >= (unsigned)live) return false;
+        v = score_key(us[u], (unsigned)q);
+        return true;
+    };
+    const unsigned long long kth = block_radix_select<CAP_BLOCK, CAP_LIST, true>(
+        key_at, nk, [max_per_image](int m) { return (max_per_image > 0 && m > max_per_image) ? max_per_image : 0; }, sc);
+    // image_thresh as order-preserving score bits (0: no cap -- every kept row passes)
+    const unsigned cut = (unsigned)(kth >> 32);
+    __syncthreads();
+    for (int q0 = 0; q0 < nk; q0 += CAP_BLOCK) {                 // nk is the same for the whole workgroup
+        const int q = q0 + t;
+        int u = q < nk ? kp[q] : -1;
+        const bool valid = (unsigned)u < (unsigned)live;
+        const int c = valid ? u / P : 0;
+        s_wave[wave][lane] = 0;
+        // position among the wave's items of the same class, class by class (every lane of the wave takes every turn)
+        int before = 0;
+        unsigned long long active = __ballot(valid);
+        while (active != 0ull) {
+            const int leader = __ffsll((long long)active) - 1;
+            const int c0 = __builtin_amdgcn_readlane(c, leader);
+            const unsigned long long same = __ballot(valid && c == c0);
+            if (valid && c == c0) before = __popcll(same & ((1ull << lane) - 1ull));
+            if (lane == leader) s_wave[wave][c0] = __popcll(same);
+            active &= ~same;
+        }
+        __syncthreads();
+        if (valid) {
+            int pos = s_base[c] + before;
+            for (int w = 0; w < wave; ++w) pos += s_wave[w][c];
+            const float s = us[u];
+            if (pos < P) {
+                const float *b = ub + (size_t)u * 4;
+                float *o = d + ((size_t)c * P + pos) * 5;
+                o[0] = b[0];  o[1] = b[1];  o[2] = b[2];  o[3] = b[3];  o[4] = s;
+                if ((unsigned)(score_key(s, 0u) >> 32) >= cut) atomicAdd(&s_count[c], 1);    // a prefix: descending order
+            }
+        }
+        __syncthreads();
+        if (t < 64) {
+            int add = 0;
+            for (int w = 0; w < CAP_WAVES; ++w) add += s_wave[w][t];
+            s_base[t] += add;
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    if (t < nc && t < 64) counts[seg0 + t] = s_count[t];
+}
+
 // Limits of the batched form: the segments' rows are 32-bit item numbers of one select (<= 2^24), and the ranking
 // and mask grids put the segments on a grid dimension of at most 65535 blocks.
 constexpr long long POST_MAX_ITEMS = 1LL << 24;
 constexpr long long POST_MAX_SEGMENTS = 65535;
+// The union segment of the class-agnostic form: (K-1) * P items per image in one ranking and one mask + sweep with
+// max_keep = the segment.  12000 is the segment the proposal layer runs both at; the kept list of the general
+// sweep (which takes over beyond 2240 kept) fits LDS up to 15296 entries, the suppression matrix is
+// U * nms_mask_pitch(U) words = 18.4 MB per image there.
+constexpr long long POST_MAX_UNION = WSSDL_POST_AGNOSTIC_MAX_UNION;
+static_assert(POST_MAX_UNION % 16 == 0, "the padded union pitch must not pass the limit");
 
 static int post_detections_run(const float *rois, const float *scores, const float *boxes, int R, int n_images, int P,
                                int num_classes, float score_thresh, double nms_thresh, int max_per_image, float *dets,
-                               int32_t *counts, void *workspace, hipStream_t st) {
+                               int32_t *counts, void *workspace, bool agnostic, hipStream_t st) {
     const int nc = num_classes - 1;
     const int nseg = n_images * nc;
-    PostWs w;
-    carve_post(workspace, n_images, P, nc, &w);
+    PostWs w, uw;
+    float *uscores = nullptr;
+    if (agnostic)
+        carve_post_agnostic(workspace, n_images, P, nc, &w, &uw, &uscores);
+    else
+        carve_post(workspace, n_images, P, nc, &w);
     const int *lo = nullptr, *hi = nullptr;
     if (rois) {
         hipLaunchKernelGGL(post_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, w.img_lo, w.img_hi);
@@ -227,6 +390,26 @@ static int post_detections_run(const float *rois, const float *scores, const flo
     if ((rc = launch_nms_two_pass(w.sorted_boxes, P * 4, w.n_sorted, P, nseg, nms_thresh, w.mask, w.cand, w.summ, P,
                                   w.sorted_index, P, w.keep, w.num_keep, nullptr, w.kept, nullptr, st)))
         return rc;
+    if (agnostic) {
+        const int U = union_pitch(P, nc);
+        const int ublocks = cdiv((long long)n_images * U, 256);
+        hipLaunchKernelGGL(post_union_keys_kernel, dim3(ublocks), dim3(256), 0, st, lo, hi, scores, w.boxes, w.keep,
+                           w.num_keep, R, num_classes, n_images, P, U, uw.keys, uw.boxes, uscores, uw.sorted_index,
+                           uw.n_sorted, uw.cand_fill);
+        if ((rc = check_launch())) return rc;
+        if ((rc = launch_rank_topk(uw.keys, U, n_images, U, uw.cand, uw.thresh, uw.cand_fill, uw.sorted_index, uw.n_sorted,
+                                   uw.mask, sizeof(unsigned long long) * (size_t)n_images * U * nms_mask_pitch(U), st)))
+            return rc;
+        hipLaunchKernelGGL(post_gather_kernel, dim3(ublocks), dim3(256), 0, st, uw.boxes, uw.sorted_index, uw.n_sorted, U,
+                           n_images, uw.sorted_boxes);
+        if ((rc = check_launch())) return rc;
+        if ((rc = launch_nms_two_pass(uw.sorted_boxes, U * 4, uw.n_sorted, U, n_images, nms_thresh, uw.mask, uw.cand,
+                                      uw.summ, U, uw.sorted_index, U, uw.keep, uw.num_keep, nullptr, uw.kept, nullptr, st)))
+            return rc;
+        hipLaunchKernelGGL(post_union_cap_kernel, dim3(n_images), dim3(CAP_BLOCK), 0, st, lo, hi, uw.boxes, uscores,
+                           uw.keep, uw.num_keep, R, num_classes, P, U, max_per_image, dets, counts);
+        return check_launch();
+    }
     hipLaunchKernelGGL(post_cap_kernel, dim3(n_images), dim3(CAP_BLOCK), 0, st, lo, hi, scores, w.boxes, w.keep, w.num_keep,
                        R, num_classes, P, max_per_image, dets, counts);
     return check_launch();
@@ -245,15 +428,25 @@ extern "C" size_t wssdl_post_detections_workspace_bytes(int R, int num_classes) 
     return wssdl_post_detections_batched_workspace_bytes(1, R, num_classes);
 }
 
-extern "C" int wssdl_post_detections_batched(const float *rois, const float *scores, const float *boxes, int R,
-                                             int n_images, int max_rows_per_image, int num_classes, float score_thresh,
-                                             double nms_thresh, int max_per_image, float *dets, int32_t *counts,
-                                             void *workspace, size_t workspace_bytes, wssdl_stream_t stream) {
+extern "C" size_t wssdl_post_detections_agnostic_batched_workspace_bytes(int n_images, int max_rows_per_image, int num_classes) {
+    if (n_images < 1 || max_rows_per_image < 1 || num_classes < 2) return 256;
+    return carve_post_agnostic(nullptr, n_images, max_rows_per_image, num_classes - 1, nullptr, nullptr, nullptr);
+}
+
+extern "C" size_t wssdl_post_detections_agnostic_workspace_bytes(int R, int num_classes) {
+    return wssdl_post_detections_agnostic_batched_workspace_bytes(1, R, num_classes);
+}
+
+static int post_detections_entry(const float *rois, const float *scores, const float *boxes, int R, int n_images,
+                                 int max_rows_per_image, int num_classes, float score_thresh, double nms_thresh,
+                                 int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
+                                 bool agnostic, wssdl_stream_t stream) {
     const int nc = num_classes - 1;
     const int P = max_rows_per_image;
     if (R < 0 || n_images < 0 || num_classes < 2 || nc > 64) return WSSDL_ERR_INVALID_ARGUMENT;
     if (R > 0 && (P < 1 || (long long)n_images * nc * P > POST_MAX_ITEMS || (long long)n_images * nc > POST_MAX_SEGMENTS))
         return WSSDL_ERR_INVALID_ARGUMENT;
+    if (R > 0 && agnostic && (long long)nc * P > POST_MAX_UNION) return WSSDL_ERR_INVALID_ARGUMENT;
     if (n_images == 0) return WSSDL_OK;
     if (!counts) return WSSDL_ERR_INVALID_ARGUMENT;
     hipStream_t st = as_stream(stream);
@@ -262,9 +455,28 @@ extern "C" int wssdl_post_detections_batched(const float *rois, const float *sco
         return WSSDL_OK;
     }
     if (!scores || !boxes || !dets || !workspace || (!rois && n_images != 1)) return WSSDL_ERR_INVALID_ARGUMENT;
-    if (workspace_bytes < wssdl_post_detections_batched_workspace_bytes(n_images, P, num_classes)) return WSSDL_ERR_WORKSPACE;
+    const size_t need = agnostic ? wssdl_post_detections_agnostic_batched_workspace_bytes(n_images, P, num_classes)
+                                 : wssdl_post_detections_batched_workspace_bytes(n_images, P, num_classes);
+    if (workspace_bytes < need) return WSSDL_ERR_WORKSPACE;
     return post_detections_run(rois, scores, boxes, R, n_images, P, num_classes, score_thresh, nms_thresh, max_per_image,
-                               dets, counts, workspace, st);
+                               dets, counts, workspace, agnostic, st);
+}
+
+extern "C" int wssdl_post_detections_batched(const float *rois, const float *scores, const float *boxes, int R,
+                                             int n_images, int max_rows_per_image, int num_classes, float score_thresh,
+                                             double nms_thresh, int max_per_image, float *dets, int32_t *counts,
+                                             void *workspace, size_t workspace_bytes, wssdl_stream_t stream) {
+    return post_detections_entry(rois, scores, boxes, R, n_images, max_rows_per_image, num_classes, score_thresh, nms_thresh,
+                                 max_per_image, dets, counts, workspace, workspace_bytes, false, stream);
+}
+
+extern "C" int wssdl_post_detections_agnostic_batched(const float *rois, const float *scores, const float *boxes, int R,
+                                                      int n_images, int max_rows_per_image, int num_classes,
+                                                      float score_thresh, double nms_thresh, int max_per_image, float *dets,
+                                                      int32_t *counts, void *workspace, size_t workspace_bytes,
+                                                      wssdl_stream_t stream) {
+    return post_detections_entry(rois, scores, boxes, R, n_images, max_rows_per_image, num_classes, score_thresh, nms_thresh,
+                                 max_per_image, dets, counts, workspace, workspace_bytes, true, stream);
 }
 
 extern "C" int wssdl_post_detections(const float *scores, const float *boxes, int R, int num_classes,
@@ -276,4 +488,14 @@ extern "C" int wssdl_post_detections(const float *scores, const float *boxes, in
                                                      max_per_image, dets, counts, workspace, workspace_bytes, stream);
     return wssdl_post_detections_batched(nullptr, scores, boxes, R, 1, R, num_classes, score_thresh, nms_thresh,
                                          max_per_image, dets, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wssdl_post_detections_agnostic(const float *scores, const float *boxes, int R, int num_classes,
+                                              float score_thresh, double nms_thresh, int max_per_image, float *dets,
+                                              int32_t *counts, void *workspace, size_t workspace_bytes,
+                                              wssdl_stream_t stream) {
+    if (R < 0 || num_classes < 2 || num_classes - 1 > 64 || !counts) return WSSDL_ERR_INVALID_ARGUMENT;
+    return wssdl_post_detections_agnostic_batched(nullptr, scores, boxes, R, 1, R == 0 ? 1 : R, num_classes, score_thresh,
+                                                  nms_thresh, max_per_image, dets, counts, workspace, workspace_bytes,
+                                                  stream);
 }

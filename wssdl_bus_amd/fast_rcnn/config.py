@@ -79,7 +79,9 @@ __C.TEST = AttrDict()
 __C.TEST.SCALES = (600,)                            # :231
 __C.TEST.MAX_SIZE = 1000                            # :234
 __C.TEST.NMS = 0.3                                  # :238
-__C.TEST.CLS_AGNOSTIC_NMS = False                   # :241
+# :241; the second, class-agnostic NMS pass over the classes' kept rows (test_bus.py:371-384) -- on the GPU part of
+# the same device op as the per-class step (wssdl_post_detections_agnostic[_batched]; fast_rcnn/post_detections.py)
+__C.TEST.CLS_AGNOSTIC_NMS = False
 __C.TEST.BBOX_REG = True                            # :248
 # (addition) the post-detection step (test_bus.py:360-401) as one device op when the tensors are on the GPU
 __C.TEST.FUSED_POST_DETECTIONS = True

@@ -3,16 +3,18 @@ at N images per forward.
 
 The reference detects one image per forward (test_bus.py:208); so does ``test_bus.im_detect``.  Here
 get_test_blobs builds the blob of N images, im_detect_batch decodes every RoI with its own image's scale and
-bounds, postprocess_detections_batch runs the per-class NMS and max_per_image cap of all images as ONE device op
-(wssdl_post_detections_batched) with one read-back, and detect_images strings them together.  Every image's
+bounds, postprocess_detections_batch runs the per-class NMS, the class-agnostic pass (cfg.TEST.CLS_AGNOSTIC_NMS) and
+the max_per_image cap of all images as ONE device op (wssdl_post_detections_batched or its _agnostic_ twin) with one
+read-back, and detect_images strings them together.  Every image's
 detections are bit for bit those of the single-image arithmetic (test_bus.im_detect's decode / clip,
-test_bus.postprocess_detections) on that image's rows of the same network outputs."""
+test_bus.postprocess_detections, of which post_detections.postprocess_detections is the form with a device op
+under the flag) on that image's rows of the same network outputs."""
 import numpy as np
 import torch
 
 from .bbox_transform import bbox_transform_inv
 from .config import cfg
-from .test_bus import postprocess_detections
+from .post_detections import device_post_detections_fit, postprocess_detections
 
 
 def get_test_blobs(planes, net_name):
@@ -80,21 +82,33 @@ def im_detect_batch(net, data, im_info):
     return scores, pred, rois
 
 
+def _rows_pitch(max_rows_per_image=None):
+    """P of the batched op: max_rows_per_image, default cfg.TEST.RPN_POST_NMS_TOP_N (<= 0: the largest image)."""
+    return int(max_rows_per_image if max_rows_per_image is not None else cfg.TEST.RPN_POST_NMS_TOP_N)
+
+
 def _device_post_detections_apply(scores, num_classes):
-    return scores.is_cuda and not cfg.TEST.CLS_AGNOSTIC_NMS and scores.shape[1] == num_classes and \
-        2 <= num_classes <= 65 and cfg.TEST.get("FUSED_POST_DETECTIONS", True)
+    # (a pitch <= 0 is the largest image of the blob: never more than its rows)
+    P = _rows_pitch()
+    return scores.is_cuda and scores.shape[1] == num_classes and \
+        device_post_detections_fit(num_classes, P if P > 0 else scores.shape[0])
 
 
 @torch.no_grad()
 def post_detections_batched_device(scores, boxes, rois, n_images, num_classes, thresh=0.05, max_per_image=300,
-                                   max_rows_per_image=None):
-    """The post-detection step of N images as one C-ABI call (wssdl_post_detections_batched: one set of
-    launches, no read-back).  rois [R,5] is the blob behind scores [R,K] / boxes [R,4K]; only its batch
+                                   max_rows_per_image=None, agnostic=None):
+    """The post-detection step of N images as one C-ABI call (wssdl_post_detections_batched, or
+    wssdl_post_detections_agnostic_batched for the class-agnostic variant; agnostic=None reads
+    cfg.TEST.CLS_AGNOSTIC_NMS: one set of launches, no read-back).
+    rois [R,5] is the blob behind scores [R,K] / boxes [R,4K]; only its batch
     column is read.  Returns (dets [N, K-1, P, 5] f32, counts [N, K-1] i32) on the GPU with
     P = max_rows_per_image (default cfg.TEST.RPN_POST_NMS_TOP_N, or the largest image when that is <= 0);
     dets[i, j-1, :counts[i, j-1]] are image i's class-j detections, best first; counts[i, 0] == -1 flags an
     image with more than P rows."""
     from .. import _lib
+    if agnostic is None:
+        agnostic = bool(cfg.TEST.CLS_AGNOSTIC_NMS)
+    name = "wssdl_post_detections_agnostic_batched" if agnostic else "wssdl_post_detections_batched"
     s = scores.to(torch.float32).contiguous()
     b = boxes.to(torch.float32).contiguous()
     r = rois.to(torch.float32).contiguous()
@@ -102,20 +116,22 @@ def post_detections_batched_device(scores, boxes, rois, n_images, num_classes, t
     N = int(n_images)
     if K != num_classes or b.shape != (R, 4 * K) or r.shape != (R, 5):
         raise ValueError("expected scores [R,K], boxes [R,4K], rois [R,5] with K = num_classes")
-    P = int(max_rows_per_image if max_rows_per_image is not None else cfg.TEST.RPN_POST_NMS_TOP_N)
+    P = _rows_pitch(max_rows_per_image)
     if P <= 0:
         live = r[:, 0][(r[:, 0] >= 0) & (r[:, 0] < N)].to(torch.int64)
         P = int(torch.bincount(live, minlength=1).max()) if live.numel() else 1
+    if agnostic and (K - 1) * P > _lib.POST_AGNOSTIC_MAX_UNION:
+        raise ValueError("class-agnostic NMS on the device: (K-1) * max_rows_per_image = %d exceeds "
+                         "WSSDL_POST_AGNOSTIC_MAX_UNION = %d" % ((K - 1) * P, _lib.POST_AGNOSTIC_MAX_UNION))
     L = _lib.lib()
     dets = torch.empty((N, K - 1, max(P, 1), 5), dtype=torch.float32, device=s.device)
     counts = torch.empty((N, K - 1), dtype=torch.int32, device=s.device)
     with torch.cuda.device(s.device):
-        n = L.wssdl_post_detections_batched_workspace_bytes(N, P, K)
+        n = getattr(L, name + "_workspace_bytes")(N, P, K)
         ws = torch.empty((n,), dtype=torch.uint8, device=s.device)
-        _lib.check(L.wssdl_post_detections_batched(_lib.ptr(r), _lib.ptr(s), _lib.ptr(b), R, N, P, K, float(thresh),
-                                                   float(cfg.TEST.NMS), int(max_per_image), _lib.ptr(dets),
-                                                   _lib.ptr(counts), _lib.ptr(ws), n, _lib.stream()),
-                   "wssdl_post_detections_batched")
+        _lib.check(getattr(L, name)(_lib.ptr(r), _lib.ptr(s), _lib.ptr(b), R, N, P, K, float(thresh), float(cfg.TEST.NMS),
+                                    int(max_per_image), _lib.ptr(dets), _lib.ptr(counts), _lib.ptr(ws), n,
+                                    _lib.stream()), name)
     return dets, counts
 
 
@@ -124,9 +140,10 @@ def postprocess_detections_batch(scores, boxes, rois, n_images, num_classes, thr
     """postprocess_detections for every image of a batch: rows r of scores [R,K] / boxes [R,4K] belong to
     image rois[r, 0] (rows with a negative index are dead and ignored).  Returns a list of n_images dicts
     {j: dets [n,5]}, each equal to postprocess_detections on that image's rows.  On the GPU: one device op
-    (post_detections_batched_device) and ONE read-back of the counts [N, K-1] for the whole batch; the
-    class-agnostic variant, CPU tensors, more than 64 classes and FUSED_POST_DETECTIONS off loop over the
-    images with postprocess_detections."""
+    (post_detections_batched_device), class-agnostic or not, and ONE read-back of the counts [N, K-1] for the
+    whole batch; CPU tensors, more than 64 classes, a class-agnostic union (K-1) * RPN_POST_NMS_TOP_N beyond
+    WSSDL_POST_AGNOSTIC_MAX_UNION and FUSED_POST_DETECTIONS off loop over the images with
+    postprocess_detections."""
     n_images = int(n_images)
     if _device_post_detections_apply(scores, num_classes):
         dets, counts = post_detections_batched_device(scores, boxes, rois, n_images, num_classes, thresh, max_per_image)

@@ -7,7 +7,10 @@ from .detect_batch import get_test_blobs, im_detect_batch, post_detections_batch
 
 
 def accumulate_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_image=300):
-    """The detections of `planes` at `batch_size` images per forward, kept on the GPU: a DetectionAccumulator."""
+    """The detections of `planes` at `batch_size` images per forward, kept on the GPU: a DetectionAccumulator.
+    cfg.TEST.CLS_AGNOSTIC_NMS is honoured (post_detections_batched_device reads it); a class-agnostic union the
+    device op does not take (post_detections_batched_device) raises -- per-class detections are never scored in its
+    place."""
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     acc = None
