@@ -490,6 +490,28 @@ WSSDL_API int wssdl_multi_task_loss_backward(
     const float *bbox_outside_w, int n_rows, int rows_total, int num_classes, const float *grad_losses,
     const void *workspace, float *grad_rpn_cls_score, float *grad_rpn_bbox_pred, float *grad_cls_score,
     float *grad_bbox_pred, wssdl_stream_t stream);
+/* The same four terms PER IMAGE, forward only: what a validation pass averages (fast_rcnn/train_bus.py:427-534 /
+ * :792-899 evaluate the training losses on one validation image per step).  Inputs and layouts as
+ * wssdl_multi_task_loss_forward; every image is a batch of its own, so there is no n_box_images.  The image of row r
+ * of the RoI list is roi_image[r * roi_image_stride] (f32; column 0 of the rois blob [n_rows,5]: stride 5); rows need
+ * not be grouped or ordered by image, and a row whose index is outside [0, n_images) or whose label is outside
+ * [0, num_classes) contributes to nothing.
+ *   losses [n_images,4]  row i = rpn_cross_entropy, rpn_loss_box, cross_entropy, loss_box of image i, each as the
+ *                        forward above defines it for a batch holding that image alone (no labelled anchor / no
+ *                        labelled row: NaN for the two cross-entropies) -- except that loss_box sums the labelled
+ *                        rows only (the forward above adds the box sum of every row, padding rows included, which
+ *                        carry zero weights there), divided by max(labelled rows, 1)
+ *   counts [n_images,2]  labelled anchors (label != -1) and labelled rows of image i
+ * One launch and one finish launch for all images, f64 sums combined in a fixed order (bit-identical from run to run),
+ * no atomics, nothing read back.  A workspace smaller than the query's answer is WSSDL_ERR_INVALID_ARGUMENT. */
+WSSDL_API size_t wssdl_multi_task_loss_per_image_workspace_bytes(int n_images, int H, int W, int A);
+WSSDL_API int wssdl_multi_task_loss_per_image(
+    const float *rpn_cls_score, const int32_t *rpn_labels, const float *rpn_bbox_pred,
+    const float *rpn_bbox_targets, const float *rpn_inside_w, const float *rpn_outside_w, int n_images,
+    int H, int W, int A, const float *cls_score, const int32_t *labels, const float *bbox_pred,
+    const float *bbox_targets, const float *bbox_inside_w, const float *bbox_outside_w, int n_rows,
+    int num_classes, const float *roi_image, int roi_image_stride, float *losses, float *counts,
+    void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
 /* y[i] = expf(x[i]) (which = 0) or log1pf(x[i]) (which = 1) for n f32 values on the device, computed by the
  * library functions exactly as the loss kernels get them (same translation unit, same compiler flags): what the
  * tests measure against f64 to fix the allowance of their error bounds. */

@@ -120,6 +120,9 @@ SYMBOLS = {
     "wssdl_multi_task_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wssdl_multi_task_loss_per_image_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wssdl_multi_task_loss_per_image": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_loss_libm_probe": (_i, [_vp, _i64, _i, _vp, _vp]),
 }
 

@@ -78,6 +78,46 @@ __device__ __forceinline__ long long rpn_target_off(const MtlArgs &x, long long 
     return ((n * C4 + ch) * x.H + h) * x.W + w;
 }
 
+// The per-element arithmetic of the forward, shared by the batch kernel and the per-image kernel (same f32
+// expressions, so the same bits).  One labelled anchor's CE term is added to s and counted in c:
+__device__ __forceinline__ void rpn_ce_element(const MtlArgs &x, long long e, double &s, double &c) {
+    long long so, lo;
+    rpn_anchor(x, e, so, lo);
+    const int l = x.rpn_labels[lo];
+    if (l < 0) return;
+    const float bg = x.rpn_cls_score[so], fg = x.rpn_cls_score[so + x.A];
+    // (max - own score) + log1p(...): adding the maximum first and subtracting it again would round the small term away
+    s += (double)((fmaxf(bg, fg) - (l ? fg : bg)) + log1pf(expf(-fabsf(bg - fg))));
+    c += 1.0;
+}
+
+// element e of rpn_bbox_pred: out_w * [0.5 (3 in_w d)^2 or |d| - 0.5/9]
+__device__ __forceinline__ double rpn_box_element(const MtlArgs &x, long long e) {
+    const long long to = rpn_target_off(x, e);
+    const float d = x.rpn_bbox_pred[e] - x.rpn_tg[to];
+    const float iw = x.rpn_inw[to], ow = x.rpn_outw[to];
+    const float ad = fabsf(d);
+    const float q = iw * d * 3.0f;
+    const float per = (ad < 1.0f) ? 0.5f * q * q : (ad - (float)(0.5 / 9.0));
+    return (double)(ow * per);
+}
+
+// CE term of row r against label l in [0, K)
+__device__ __forceinline__ double rcnn_ce_row(const MtlArgs &x, int r, int l) {
+    const float *sc = x.cls_score + (size_t)r * x.K;
+    float m;
+    const float lz = lse_minus_max(sc, x.K, &m);
+    return (double)((m - sc[l]) + lz);
+}
+
+// sum_j out_w * in_w * |pred - target| of row r, added in f32 in column order
+__device__ __forceinline__ double rcnn_box_row(const MtlArgs &x, int r) {
+    const size_t o = (size_t)r * 4 * x.K;
+    float row = 0.0f;
+    for (int j = 0; j < 4 * x.K; ++j) row += x.outw[o + j] * (x.inw[o + j] * fabsf(x.bbox_pred[o + j] - x.tg[o + j]));
+    return (double)row;
+}
+
 // partials: [nb_cls] CE sums, [nb_cls] counts, [nb_box] box sums, then 3 values of the R-CNN block
 __global__ __launch_bounds__(MTL_BLOCK) void mtl_forward_kernel(MtlArgs x, double *__restrict__ partials) {
     __shared__ double scratch[MTL_BLOCK / 64];
@@ -88,14 +128,7 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_forward_kernel(MtlArgs x, doubl
         for (int i = 0; i < MTL_ITEMS; ++i) {
             const long long e = ((long long)b * MTL_ITEMS + i) * MTL_BLOCK + t;
             if (e >= total) break;
-            long long so, lo;
-            rpn_anchor(x, e, so, lo);
-            const int l = x.rpn_labels[lo];
-            if (l < 0) continue;
-            const float bg = x.rpn_cls_score[so], fg = x.rpn_cls_score[so + x.A];
-            // (max - own score) + log1p(...): adding the maximum first and subtracting it again would round the small term away
-            s += (double)((fmaxf(bg, fg) - (l ? fg : bg)) + log1pf(expf(-fabsf(bg - fg))));
-            c += 1.0;
+            rpn_ce_element(x, e, s, c);
         }
         const double ss = block_sum(s, scratch), cc = block_sum(c, scratch);
         if (t == 0) { partials[b] = ss;  partials[x.nb_cls + b] = cc; }
@@ -106,13 +139,7 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_forward_kernel(MtlArgs x, doubl
         for (int i = 0; i < MTL_ITEMS; ++i) {
             const long long e = ((long long)bb * MTL_ITEMS + i) * MTL_BLOCK + t;
             if (e >= total) break;
-            const long long to = rpn_target_off(x, e);
-            const float d = x.rpn_bbox_pred[e] - x.rpn_tg[to];
-            const float iw = x.rpn_inw[to], ow = x.rpn_outw[to];
-            const float ad = fabsf(d);
-            const float q = iw * d * 3.0f;
-            const float per = (ad < 1.0f) ? 0.5f * q * q : (ad - (float)(0.5 / 9.0));
-            s += (double)(ow * per);
+            s += rpn_box_element(x, e);
         }
         const double ss = block_sum(s, scratch);
         if (t == 0) partials[2 * x.nb_cls + bb] = ss;
@@ -122,16 +149,10 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_forward_kernel(MtlArgs x, doubl
         for (int r = t; r < x.n_rows; r += MTL_BLOCK) {
             const int l = x.labels[r];
             if (l >= 0 && l < x.K) {       // (a label outside [0, K) is ignored like padding, not read through)
-                const float *sc = x.cls_score + (size_t)r * x.K;
-                float m;
-                const float lz = lse_minus_max(sc, x.K, &m);
-                ce += (double)((m - sc[l]) + lz);
+                ce += rcnn_ce_row(x, r, l);
                 cnt += 1.0;
             }
-            const size_t o = (size_t)r * 4 * x.K;
-            float row = 0.0f;
-            for (int j = 0; j < 4 * x.K; ++j) row += x.outw[o + j] * (x.inw[o + j] * fabsf(x.bbox_pred[o + j] - x.tg[o + j]));
-            box += (double)row;
+            box += rcnn_box_row(x, r);
         }
         const double a = block_sum(ce, scratch), c = block_sum(cnt, scratch), d = block_sum(box, scratch);
         if (t == 0) {
@@ -141,23 +162,112 @@ __global__ __launch_bounds__(MTL_BLOCK) void mtl_forward_kernel(MtlArgs x, doubl
     }
 }
 
+// The four values from one set of partials (the batch's, or one image's): workgroup sums in index order per thread,
+// then block_sum.  rcnn = the 3 values of the R-CNN block.  Valid on thread 0.
+struct MtlTerms { float v[4];  double rpn_count, row_count; };
+
+__device__ __forceinline__ MtlTerms finish_terms(const double *__restrict__ ce, const double *__restrict__ cnt,
+                                                 const double *__restrict__ box, const double *__restrict__ rcnn,
+                                                 int nb_cls, int nb_box, int n_box_images, int A, double *scratch) {
+    const int t = threadIdx.x;
+    double s = 0.0, c = 0.0, b = 0.0;
+    for (int i = t; i < nb_cls; i += MTL_BLOCK) { s += ce[i];  c += cnt[i]; }
+    for (int i = t; i < nb_box; i += MTL_BLOCK) b += box[i];
+    const double ss = block_sum(s, scratch), cc = block_sum(c, scratch), bb = block_sum(b, scratch);
+    MtlTerms o;
+    o.rpn_count = cc;
+    o.row_count = rcnn[1];
+    o.v[0] = (float)(ss / cc);                                               // no labelled anchor: NaN, like the mean of nothing
+    o.v[1] = (float)(10.0 * bb / ((double)n_box_images * 4.0 * A));
+    o.v[2] = (float)(rcnn[0] / rcnn[1]);
+    o.v[3] = (float)(rcnn[2] / (rcnn[1] < 1.0 ? 1.0 : rcnn[1]));
+    return o;
+}
+
 __global__ __launch_bounds__(MTL_BLOCK) void mtl_finish_kernel(const double *__restrict__ partials, int nb_cls,
                                                                int nb_box, int n_box_images, int A,
                                                                MtlState *__restrict__ state, float *__restrict__ losses) {
     __shared__ double scratch[MTL_BLOCK / 64];
-    const int t = threadIdx.x;
-    double s = 0.0, c = 0.0, b = 0.0;
-    for (int i = t; i < nb_cls; i += MTL_BLOCK) { s += partials[i];  c += partials[nb_cls + i]; }
-    for (int i = t; i < nb_box; i += MTL_BLOCK) b += partials[2 * nb_cls + i];
-    const double ss = block_sum(s, scratch), cc = block_sum(c, scratch), bb = block_sum(b, scratch);
-    if (t == 0) {
-        const double *p = partials + 2 * nb_cls + nb_box;
-        state->rpn_count = cc;
-        state->row_count = p[1];
-        losses[0] = (float)(ss / cc);                                        // no labelled anchor: NaN, like the mean of nothing
-        losses[1] = (float)(10.0 * bb / ((double)n_box_images * 4.0 * A));
-        losses[2] = (float)(p[0] / p[1]);
-        losses[3] = (float)(p[2] / (p[1] < 1.0 ? 1.0 : p[1]));
+    const MtlTerms o = finish_terms(partials, partials + nb_cls, partials + 2 * nb_cls, partials + 2 * nb_cls + nb_box,
+                                    nb_cls, nb_box, n_box_images, A, scratch);
+    if (threadIdx.x == 0) {
+        state->rpn_count = o.rpn_count;
+        state->row_count = o.row_count;
+        for (int k = 0; k < 4; ++k) losses[k] = o.v[k];
+    }
+}
+
+// ---- the four terms per image, forward only (the validation pass: fast_rcnn/train_bus.py:427-534 / :792-899 run the
+// training losses on one validation image per step).  Image i is treated as a batch of its own: pc workgroups of
+// MTL_BLOCK * MTL_ITEMS anchors starting at the image's first anchor, pb workgroups of box elements likewise, and one
+// workgroup that scans ALL rows of the RoI list and keeps those whose image column equals i (rows need not be grouped
+// or ordered; an index outside [0, N) matches no workgroup; R is at most a few thousand).  The partials of image i
+// are [pc] CE sums, [pc] counts, [pb] box sums, 3 R-CNN values, laid out as the batch kernel's.
+struct MtlImageArgs {
+    const float *roi_image;                  // image index of row r at roi_image[r * stride] (column 0 of the rois blob)
+    int stride;
+    int pc, pb;                              // workgroups per image of the two RPN terms
+};
+
+__global__ __launch_bounds__(MTL_BLOCK) void mtl_per_image_kernel(MtlArgs x, MtlImageArgs y, double *__restrict__ partials) {
+    __shared__ double scratch[MTL_BLOCK / 64];
+    const int per = y.pc + y.pb + 1;
+    const int img = blockIdx.x / per, j = blockIdx.x % per, t = threadIdx.x;
+    double *p = partials + (size_t)img * (2 * y.pc + y.pb + 3);
+    if (j < y.pc) {
+        const long long n = (long long)x.H * x.W * x.A, base = (long long)img * n;
+        double s = 0.0, c = 0.0;
+        for (int i = 0; i < MTL_ITEMS; ++i) {
+            const long long e = ((long long)j * MTL_ITEMS + i) * MTL_BLOCK + t;
+            if (e >= n) break;
+            rpn_ce_element(x, base + e, s, c);
+        }
+        const double ss = block_sum(s, scratch), cc = block_sum(c, scratch);
+        if (t == 0) { p[j] = ss;  p[y.pc + j] = cc; }
+    } else if (j < y.pc + y.pb) {
+        const int jb = j - y.pc;
+        const long long n = (long long)x.H * x.W * 4 * x.A, base = (long long)img * n;
+        double s = 0.0;
+        for (int i = 0; i < MTL_ITEMS; ++i) {
+            const long long e = ((long long)jb * MTL_ITEMS + i) * MTL_BLOCK + t;
+            if (e >= n) break;
+            s += rpn_box_element(x, base + e);
+        }
+        const double ss = block_sum(s, scratch);
+        if (t == 0) p[2 * y.pc + jb] = ss;
+    } else {
+        // the box sum too is over the labelled rows only (the batch kernel adds every row's; a padding row carries
+        // zero weights there)
+        const float want = (float)img;
+        double ce = 0.0, cnt = 0.0, box = 0.0;
+        for (int r = t; r < x.n_rows; r += MTL_BLOCK) {
+            const int l = x.labels[r];
+            if (y.roi_image[(size_t)r * y.stride] == want && l >= 0 && l < x.K) {
+                ce += rcnn_ce_row(x, r, l);
+                cnt += 1.0;
+                box += rcnn_box_row(x, r);
+            }
+        }
+        const double a = block_sum(ce, scratch), c = block_sum(cnt, scratch), d = block_sum(box, scratch);
+        if (t == 0) {
+            double *q = p + 2 * y.pc + y.pb;
+            q[0] = a;  q[1] = c;  q[2] = d;
+        }
+    }
+}
+
+// one workgroup per image: finish_terms on the image's partials (n_box_images = 1: the image alone)
+__global__ __launch_bounds__(MTL_BLOCK) void mtl_per_image_finish_kernel(const double *__restrict__ partials, int pc, int pb,
+                                                                         int A, float *__restrict__ losses,
+                                                                         float *__restrict__ counts) {
+    __shared__ double scratch[MTL_BLOCK / 64];
+    const int img = blockIdx.x;
+    const double *p = partials + (size_t)img * (2 * pc + pb + 3);
+    const MtlTerms o = finish_terms(p, p + pc, p + 2 * pc, p + 2 * pc + pb, pc, pb, 1, A, scratch);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 4; ++k) losses[img * 4 + k] = o.v[k];
+        counts[img * 2] = (float)o.rpn_count;
+        counts[img * 2 + 1] = (float)o.row_count;
     }
 }
 
@@ -288,6 +398,16 @@ static size_t mtl_workspace(int n_images, int H, int W, int A) {
     return 256 + sizeof(double) * (size_t)(2 * nb_cls + nb_box + 4);
 }
 
+static long long mtl_blocks(long long elements) {
+    const long long per = (long long)MTL_BLOCK * MTL_ITEMS;
+    return (elements + per - 1) / per;
+}
+
+static size_t mtl_per_image_workspace(int n_images, int H, int W, int A) {
+    const long long pc = mtl_blocks((long long)H * W * A), pb = mtl_blocks((long long)H * W * 4 * A);
+    return sizeof(double) * (size_t)n_images * (size_t)(2 * pc + pb + 3);
+}
+
 }  // namespace wssdl
 
 using namespace wssdl;
@@ -317,6 +437,40 @@ extern "C" int wssdl_multi_task_loss_forward(
     if ((rc = check_launch())) return rc;
     hipLaunchKernelGGL(mtl_finish_kernel, dim3(1), dim3(MTL_BLOCK), 0, st, partials, x.nb_cls, x.nb_box, n_box_images, A,
                        state, losses);
+    return check_launch();
+}
+
+extern "C" size_t wssdl_multi_task_loss_per_image_workspace_bytes(int n_images, int H, int W, int A) {
+    if (n_images < 1 || H < 1 || W < 1 || A < 1) return 0;
+    return mtl_per_image_workspace(n_images, H, W, A);
+}
+
+extern "C" int wssdl_multi_task_loss_per_image(
+    const float *rpn_cls_score, const int32_t *rpn_labels, const float *rpn_bbox_pred, const float *rpn_bbox_targets,
+    const float *rpn_inside_w, const float *rpn_outside_w, int n_images, int H, int W, int A, const float *cls_score,
+    const int32_t *labels, const float *bbox_pred, const float *bbox_targets, const float *bbox_inside_w,
+    const float *bbox_outside_w, int n_rows, int num_classes, const float *roi_image, int roi_image_stride,
+    float *losses, float *counts, void *workspace, size_t workspace_bytes, wssdl_stream_t stream) {
+    MtlArgs x;
+    int rc = fill_args(&x, rpn_cls_score, rpn_labels, rpn_bbox_pred, rpn_bbox_targets, rpn_inside_w, rpn_outside_w,
+                       n_images, n_images, H, W, A, cls_score, labels, bbox_pred, bbox_targets, bbox_inside_w,
+                       bbox_outside_w, n_rows, n_rows, num_classes, false);
+    if (rc) return rc;
+    if (!losses || !counts || !workspace || roi_image_stride < 1 || (n_rows > 0 && !roi_image))
+        return WSSDL_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < mtl_per_image_workspace(n_images, H, W, A)) return WSSDL_ERR_INVALID_ARGUMENT;
+    MtlImageArgs y;
+    y.roi_image = roi_image;  y.stride = roi_image_stride;
+    y.pc = (int)mtl_blocks((long long)H * W * A);
+    y.pb = (int)mtl_blocks((long long)H * W * 4 * A);
+    const long long grid = (long long)n_images * (y.pc + y.pb + 1);
+    if (grid > 0x7fffffffLL) return WSSDL_ERR_INVALID_ARGUMENT;
+    hipStream_t st = as_stream(stream);
+    double *partials = static_cast<double *>(workspace);
+    hipLaunchKernelGGL(mtl_per_image_kernel, dim3((unsigned)grid), dim3(MTL_BLOCK), 0, st, x, y, partials);
+    if ((rc = check_launch())) return rc;
+    hipLaunchKernelGGL(mtl_per_image_finish_kernel, dim3(n_images), dim3(MTL_BLOCK), 0, st, partials, y.pc, y.pb, A, losses,
+                       counts);
     return check_launch();
 }
 

@@ -68,10 +68,7 @@ def mil_loss(cls_score_ws, batch_inds, mil_label, n_bags, global_step, funcs, co
     [0, WS_MAL_PCT, 1-WS_MAL_PCT] and by 1 - 0.99*0.9^floor(step/2000) (or a constant).
     On the GPU the bag selection is the HIP op (no host round trip); on CPU tensors (tests) the
     host-side restatement of mil/core.py runs."""
-    if cfg.TRAIN.WS_LOSS_USE_ADAPTIVE_SCALE_FACTOR:
-        scale = 1.0 - 0.99 * (0.9 ** (int(global_step) // 2000))      # exponential_decay, staircase
-    else:
-        scale = cfg.TRAIN.WS_LOSS_SCALE_FACTOR
+    scale = _mil_scale(global_step)
     # (the fused MIL op takes 3..8 classes, the reference has 3; anything else: selection op + torch CE)
     if cls_score_ws.is_cuda and cfg.get('FUSED_LOSS', True) and 3 <= cls_score_ws.shape[1] <= 8:
         # selection + weighted CE + mean as one device op with its own backward (f1)
@@ -90,6 +87,12 @@ def mil_loss(cls_score_ws, batch_inds, mil_label, n_bags, global_step, funcs, co
         w = w * valid.to(w.dtype)
     ce = F.cross_entropy(bag_logits, label, reduction='none')
     return (scale * (w * ce)).mean()
+
+
+def _mil_scale(global_step):
+    if cfg.TRAIN.WS_LOSS_USE_ADAPTIVE_SCALE_FACTOR:
+        return 1.0 - 0.99 * (0.9 ** (int(global_step) // 2000))       # exponential_decay, staircase
+    return cfg.TRAIN.WS_LOSS_SCALE_FACTOR
 
 
 _prior_cache = {}
@@ -138,6 +141,65 @@ def supervised_loss(layers, params, n_sup=None):
     l['loss'] = (l['cross_entropy'] + l['loss_box'] + l['rpn_cross_entropy'] + l['rpn_loss_box']
                  + l['weight_decay'])
     return l
+
+
+# ------------------------------------------------------------- validation ---
+
+# the reference's test_loss vector (train_bus.py:519-520): the total first
+VAL_TERMS = ('total', 'rpn_cross_entropy', 'rpn_loss_box', 'cross_entropy', 'loss_box', 'mil_cross_entropy')
+
+
+def _mil_per_image(cls_score, image_column, mil_label, n_images, global_step, funcs):
+    """[n_images]: mil_loss of every image as ONE bag of its own rows (n_bags = 1 each)."""
+    scale = _mil_scale(global_step)
+    if cls_score.is_cuda and cfg.get('FUSED_LOSS', True) and 3 <= cls_score.shape[1] <= 8:
+        # one call of the fused op with bags = images; its per-bag output times the scale, rounded as the op's
+        # own finish rounds a mean over one bag: (f32)((f64)(f32)scale * bag_loss)
+        prior = [0.0, float(cfg.TRAIN.WS_MAL_PCT), 1.0 - float(cfg.TRAIN.WS_MAL_PCT)]
+        bag = mil_core.mil_bag_losses_device(cls_score, image_column, 0.0, mil_label, n_images, funcs, prior)
+        return (bag.double() * float(np.float32(scale))).float()
+    out = []
+    for i in range(n_images):
+        rows = (image_column == i).nonzero().reshape(-1)
+        if rows.numel() == 0:                          # an empty bag carries no loss (as in the fused op)
+            out.append(cls_score.new_zeros(()))
+            continue
+        out.append(mil_loss(cls_score[rows], cls_score.new_zeros((rows.numel(),)), mil_label[i:i + 1], 1, global_step,
+                            funcs, counts_host=[int(rows.numel())]))
+    return torch.stack(out).float()
+
+
+@torch.no_grad()
+def validation_losses(layers, im_info, n_images, global_step, alter):
+    """The loss half of the reference's validation pass (train_bus.py:427-534 alternating, :792-899 combined) for
+    the N = n_images images of ONE forward: a pure function of that forward's `layers` (run with
+    is_training=False, is_ws=False).  -> dict of [N] f32 tensors on the layers' device, nothing read back:
+
+      rpn_cross_entropy, rpn_loss_box, cross_entropy, loss_box
+                          image i's four supervised terms, as supervised_loss gives them for a batch holding that
+                          image alone (loss_op.multi_task_loss_per_image: one device launch for all images);
+      total               their sum, the reference's test_loss[0] (:519): no weight decay, no MIL term -- what the
+                          plateau schedule is fed;
+      mil_cross_entropy   mil_loss of image i as one bag of its own roi-data rows, bag label im_info[i, 3], class
+                          prior and scale factor of mil_loss at `global_step`, selectors [get_mass_max_logit,
+                          get_mal_max_logit] when `alter` else [get_mal_max_logit, get_mal_max_logit].
+
+    For the alternating wiring the MIL slot is the reference's value (:239-260 under the feed of :436-438).  For the
+    combined wiring it is UNPINNED: the reference's graph slices the rows past len(label) (:650-653), of which a
+    validation batch has none, and what TensorFlow then yields for an arg-max over no rows could not be observed;
+    the slot holds the per-image bag loss defined above instead."""
+    from .loss_op import multi_task_loss_per_image, TERMS
+    n = int(n_images)
+    losses, _ = multi_task_loss_per_image(layers['rpn_cls_score'], layers['rpn_bbox_pred'], layers['cls_score'],
+                                          layers['bbox_pred'], layers['rpn-data'], layers['roi-data'], n)
+    out = {name: losses[:, i] for i, name in enumerate(TERMS)}
+    out['total'] = out['rpn_cross_entropy'] + out['rpn_loss_box'] + out['cross_entropy'] + out['loss_box']   # :519
+    rois = layers['roi-data'][0]
+    funcs = [mil_core.get_mass_max_logit, mil_core.get_mal_max_logit] if alter \
+        else [mil_core.get_mal_max_logit, mil_core.get_mal_max_logit]
+    out['mil_cross_entropy'] = _mil_per_image(layers['cls_score'][:rois.shape[0]], rois[:, 0],
+                                              im_info[:n, 3].to(torch.int32), n, global_step, funcs)
+    return out
 
 
 # ------------------------------------------------------------ train steps ---
@@ -220,6 +282,62 @@ class SolverWrapper(object):
         """After a validation pass: feeds the 'rop' schedule (train_bus.py:70-91); nothing under the others."""
         if self.rop is not None:
             self.rop.on_val_end(val_loss)
+
+    def validate(self, blobs_iter, feed_schedule=True):
+        """The loss half of the reference's validation pass (train_bus.py:427-534 / :792-899): the training wiring
+        on validation images with is_training=False, their six loss values averaged over the set and the total
+        handed to the plateau schedule (:519-534).  The reference runs one image per step; here every element of
+        `blobs_iter` -- a blob dict as the train steps take them: data [n,H,W,3], im_info [n,4], gt_boxes,
+        num_gt_boxes, any n >= 1, not the same for every element -- is ONE forward in eval mode under no_grad, and
+        validation_losses gives the per-image values of its n images.  They stay on the device; the single
+        read-back comes at the end of the pass.
+
+        -> dict: the means over all images under VAL_TERMS' names ('total' first, the order of :519-520),
+        'n_images', and 'per_image', a [n_images, 6] numpy array in that column order.  With feed_schedule the
+        mean total goes to on_val_end: under 'rop' the next current_lr() follows the plateau rule, under the
+        other schedules nothing happens.
+
+        Nothing else moves: optimisers, parameters, running statistics, renorm state and global_step are as
+        before (eval mode updates no buffer), the network's training flag is restored, and so is
+        cfg.TRAIN.IMS_PER_BATCH, which the combined wiring's target layers read and which is therefore set to
+        each element's n during its forward -- both also when a forward raises.  Under cfg.SAMPLING_RNG =
+        'reference' the target layers draw from the global NumPy stream exactly as the reference's own
+        validation forward does (they sample under is_training=False too): per forward all anchor subsamples,
+        image by image, then all RoI samples; a caller who needs the training draws unchanged saves and
+        restores np.random's state around the pass.  The deferred device flags are polled at the end, as after a
+        train step.
+
+        The reference scores CorLoc on the sampled RoIs of the same forward; that half is not here:
+        eval_batch.evaluate_images scores detections on the test protocol, and the two together are the
+        reference's validation pass.  The MIL column of the combined wiring is UNPINNED (validation_losses)."""
+        alter = bool(getattr(self.net, 'alter', False))
+        chunks = []
+        was_training = self.net.training
+        ims_per_batch = cfg.TRAIN.IMS_PER_BATCH
+        try:
+            self.net.eval()
+            with torch.no_grad():
+                for blobs in blobs_iter:
+                    n = int(blobs['data'].shape[0])
+                    cfg.TRAIN.IMS_PER_BATCH = n
+                    layers = self.net(blobs['data'], blobs['im_info'], blobs['gt_boxes'], blobs['num_gt_boxes'],
+                                      is_training=False, is_ws=False)
+                    v = validation_losses(layers, blobs['im_info'], n, self.global_step, alter)
+                    chunks.append(torch.stack([v[name] for name in VAL_TERMS], dim=1))
+        finally:
+            cfg.TRAIN.IMS_PER_BATCH = ims_per_batch
+            self.net.train(was_training)
+        if not chunks:
+            raise ValueError("validate: no validation images")
+        per_image = torch.cat(chunks, dim=0).cpu().numpy()             # the one read-back of the pass
+        roi_pooling_op.poll_flags()
+        means = per_image.astype(np.float64).mean(axis=0)
+        out = {name: float(means[i]) for i, name in enumerate(VAL_TERMS)}
+        out['n_images'] = int(per_image.shape[0])
+        out['per_image'] = per_image
+        if feed_schedule:
+            self.on_val_end(out['total'])
+        return out
 
     def _apply(self, optimizer=None, count_step=True):
         optimizer = optimizer or self.optimizer

@@ -56,6 +56,16 @@ def get_bag_logit(instance_logits, batch_inds, num_classes, bag_labels, batch_si
 _SELECTORS = {get_mal_max_logit: 0, get_ben_max_logit: 1, get_mass_max_logit: 2}
 
 
+def _bag_column(bag_column, R):
+    """(f32 column, element stride) as the ops take it: a strided 1-d view such as rois[:, 0] is passed as it is"""
+    col = bag_column if bag_column.dtype == torch.float32 else bag_column.to(torch.float32)
+    stride = col.stride(0) if col.dim() == 1 and R > 1 else 1
+    if col.dim() != 1 or (R > 1 and stride < 1):
+        col = col.reshape(-1).contiguous()
+        stride = 1
+    return col, stride
+
+
 def get_bag_logit_device(instance_logits, bag_column, bag_offset, bag_labels, batch_size, funcs,
                          return_valid=False):
     """get_bag_logit as ONE kernel launch + one gather, with no host round trip: the HIP op
@@ -74,11 +84,7 @@ def get_bag_logit_device(instance_logits, bag_column, bag_offset, bag_labels, ba
     R, K = logits.shape
     if R == 0 and batch_size > 0:
         raise ValueError("get_bag_logit: no instances for %d bag(s)" % batch_size)
-    col = bag_column if bag_column.dtype == torch.float32 else bag_column.to(torch.float32)
-    stride = col.stride(0) if col.dim() == 1 and R > 1 else 1
-    if col.dim() != 1 or (R > 1 and stride < 1):
-        col = col.reshape(-1).contiguous()
-        stride = 1
+    col, stride = _bag_column(bag_column, R)
     labels = bag_labels.reshape(-1).to(torch.int32).contiguous()
     rows = torch.empty((batch_size,), dtype=torch.int32, device=logits.device)
     with torch.cuda.device(logits.device):
@@ -104,11 +110,7 @@ class _MilLoss(torch.autograd.Function):
         from .. import _lib
         logits = instance_logits.contiguous()
         R, K = logits.shape
-        col = bag_column if bag_column.dtype == torch.float32 else bag_column.to(torch.float32)
-        stride = col.stride(0) if col.dim() == 1 and R > 1 else 1
-        if col.dim() != 1 or (R > 1 and stride < 1):
-            col = col.reshape(-1).contiguous()
-            stride = 1
+        col, stride = _bag_column(bag_column, R)
         labels = bag_labels.reshape(-1).to(torch.int32).contiguous()
         dev = logits.device
         rows = torch.empty((n_bags,), dtype=torch.int32, device=dev)
@@ -136,6 +138,32 @@ class _MilLoss(torch.autograd.Function):
                 _lib.ptr(logits), R, K, _lib.ptr(col), stride, bag_offset, _lib.ptr(labels), n_bags, _lib.ptr(rows),
                 _lib.host_ptr(cw), scale, _lib.ptr(gl), _lib.ptr(g), _lib.stream()), "wssdl_mil_loss_backward")
         return (g,) + (None,) * 8
+
+
+@torch.no_grad()
+def mil_bag_losses_device(instance_logits, bag_column, bag_offset, bag_labels, n_bags, funcs, class_weights):
+    """[n_bags] f32: class_weights[label] * CE(selected instance's logits, label) of every bag, 0 for an empty bag --
+    the per-bag output of the fused op (wssdl_mil_loss_forward's bag_loss) in one call, forward only.  The op's own
+    loss is mean(bag_loss) * scale; a bag on its own (n_bags = 1) has the loss (f32)((f64)scale * bag_loss)."""
+    import numpy as np
+    from .. import _lib
+    if instance_logits.shape[0] == 0 and n_bags > 0:
+        raise ValueError("get_bag_logit: no instances for %d bag(s)" % n_bags)
+    logits = instance_logits.detach().contiguous()
+    R, K = logits.shape
+    col, stride = _bag_column(bag_column, R)
+    labels = bag_labels.reshape(-1).to(torch.int32).contiguous()
+    dev = logits.device
+    rows = torch.empty((n_bags,), dtype=torch.int32, device=dev)
+    bag_loss = torch.empty((n_bags,), dtype=torch.float32, device=dev)
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    cw = np.ascontiguousarray(np.asarray(class_weights, np.float32))
+    with torch.cuda.device(dev), _lib.timed("mil_bag_losses", dict(R=R, bags=int(n_bags))):
+        _lib.check(_lib.lib().wssdl_mil_loss_forward(
+            _lib.ptr(logits), R, K, _lib.ptr(col), int(stride), float(bag_offset), _lib.ptr(labels), int(n_bags),
+            _SELECTORS[funcs[0]], _SELECTORS[funcs[1]], _lib.host_ptr(cw), 1.0, _lib.ptr(loss), _lib.ptr(rows),
+            _lib.ptr(bag_loss), _lib.stream()), "wssdl_mil_loss_forward")
+    return bag_loss
 
 
 def mil_loss_device(instance_logits, bag_column, bag_offset, bag_labels, n_bags, funcs, class_weights, scale):
