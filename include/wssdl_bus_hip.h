@@ -667,6 +667,34 @@ WSSDL_API int wssdl_post_detections_agnostic_batched(const float *rois, const fl
                      int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
                      wssdl_stream_t stream);
 
+/* Decode and clip of the head's class-wise boxes: the step between a forward's layers and the post-detection ops
+ * above, as the reference's validation loop does it on the sampled RoIs (fast_rcnn/train_bus.py:456-457 / :821-822:
+ * boxes = rois[:, 1:5] / scale; clip_boxes(bbox_transform_inv(boxes, bbox_pred), im.shape)), for all images of a batch
+ * in ONE launch.
+ *   rois   [R, 5] f32 (batch index, x1, y1, x2, y2) in the scaled image's pixels; deltas [R, 4 * num_classes] f32;
+ *   im_info [n_images, info_stride >= 3] f32 rows (h, w, scale, ...);
+ *   bounds [n_images, 2] f32 (xmax, ymax) per image, or NULL;
+ *   boxes  [R, 4 * num_classes] f32, the layout the post-detection ops read.  Class 0's four columns are written like
+ *          the others, as the reference does.
+ * Per (row r, class k), in this order, every operation rounded to f32 on its own (no contraction):
+ *   1. i = (int)rois[r, 0].  A row whose index is outside [0, n_images) (NaN included) is a dead row: its
+ *      4 * num_classes outputs are zeros and nothing else is read for it, so the blob is fully initialised.
+ *   2. s = im_info[i, 2]; b = rois[r, 1..4] / s by IEEE f32 division (not a multiplication by a reciprocal).
+ *   3. bbox_transform_inv (fast_rcnn/bbox_transform.py:30-61) with d = deltas[r, 4k .. 4k+3]:
+ *        w = (b.x2 - b.x1) + 1;  cx = b.x1 + 0.5f * w;  pcx = d.x * w, then pcx + cx;
+ *        pw = (float)exp((double)d.z) * w;  x1 = pcx - 0.5f * pw;  x2 = pcx + 0.5f * pw;  the same for y with d.y, d.w.
+ *   4. clip_boxes (:63-77): max(min(v, xmax), 0) on x1 and x2, with ymax on y1 and y2, where
+ *        (xmax, ymax) = bounds[i] when bounds is given (the reference clips to the original image: (W - 1, H - 1)),
+ *        else xmax = (float)((double)w_i / (double)s - 1.0), ymax likewise from h_i, (h_i, w_i) = im_info[i, 0..1]
+ *        (the rule of the batched test-time path).
+ * No workspace, no allocation, no read-back: capturable like the other entry points.  R == 0 returns WSSDL_OK and
+ * launches nothing.  WSSDL_ERR_INVALID_ARGUMENT, without a launch: R < 0, num_classes < 2 or > 65, n_images < 1,
+ * info_stride < 3, and with R > 0 a NULL rois, deltas, im_info or boxes, or deltas / boxes not 16-byte aligned (a pair's
+ * four values move as one vector).  Behaviour on non-finite coordinates, deltas and scales is unspecified. */
+WSSDL_API int wssdl_decode_detections(const float *rois, const float *deltas, int R, int num_classes,
+                     const float *im_info, int info_stride, int n_images, const float *bounds, float *boxes,
+                     wssdl_stream_t stream);
+
 /* ---------------------------------------------------------------- evaluation ---
  * Detection evaluation, datasets/voc_eval_bus.py + the 44 calls of datasets/bus.py:_do_python_eval in one pass:
  * for every class j = 1 .. n_classes-1 the PASCAL VOC precision / recall curve and AP (11-point and area), and for

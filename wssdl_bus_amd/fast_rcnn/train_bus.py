@@ -283,7 +283,8 @@ class SolverWrapper(object):
         if self.rop is not None:
             self.rop.on_val_end(val_loss)
 
-    def validate(self, blobs_iter, feed_schedule=True):
+    def validate(self, blobs_iter, feed_schedule=True, *, gt_roidb=None, classes=None, im_shapes=None, thresh=0.05,
+                 max_per_image=300, ovthresh=0.5, score_thresh=0.5):
         """The loss half of the reference's validation pass (train_bus.py:427-534 / :792-899): the training wiring
         on validation images with is_training=False, their six loss values averaged over the set and the total
         handed to the plateau schedule (:519-534).  The reference runs one image per step; here every element of
@@ -307,11 +308,28 @@ class SolverWrapper(object):
         restores np.random's state around the pass.  The deferred device flags are polled at the end, as after a
         train step.
 
-        The reference scores CorLoc on the sampled RoIs of the same forward; that half is not here:
-        eval_batch.evaluate_images scores detections on the test protocol, and the two together are the
-        reference's validation pass.  The MIL column of the combined wiring is UNPINNED (validation_losses)."""
+        The reference also scores CorLoc on the sampled RoIs of the same forward (:445-527 / :810-892).  With
+        gt_roidb=None (the default) that half does not run: arguments, return value, launches and RNG draws are
+        those of the loss half alone.  With a gt_roidb -- one entry per validation image in pass order, in
+        original-image pixels, in datasets.voc_eval_bus.pack_gt's format -- every forward's layers also go through
+        val_detect.validation_detections (decode and clip of the sampled RoIs in one launch, then the batched
+        post-detection op under `thresh`, cfg.TEST.NMS, cfg.TEST.CLS_AGNOSTIC_NMS and `max_per_image`), the result is
+        added to a DetectionAccumulator at the running image index, and after the loss read-back ONE
+        evaluate_detections call (ovthresh, score_thresh; classes: the names, '__background__' first, default
+        numbered) scores the whole pass: two read-backs in total.  The dict then also holds 'corloc_list', 'aps',
+        'mean_ap', 'froc_curve_pts' (evaluate_detections) and 'detections', the accumulator.  im_shapes: the
+        original (H, W) of every image in pass order, to clip to as the reference does (im.shape); without it boxes
+        are clipped to (w / scale - 1, h / scale - 1) of im_info.  A gt_roidb or im_shapes whose length is not the
+        pass's image count raises ValueError.  The detection half draws nothing from any RNG and changes no state.
+        eval_batch.evaluate_images remains the test protocol (a forward of its own, 300 proposals).
+        The MIL column of the combined wiring is UNPINNED (validation_losses)."""
         alter = bool(getattr(self.net, 'alter', False))
         chunks = []
+        detect = gt_roidb is not None
+        acc, seen = None, 0
+        if detect:
+            from ..datasets.voc_eval_bus import DetectionAccumulator, evaluate_detections
+            from .val_detect import validation_detections
         was_training = self.net.training
         ims_per_batch = cfg.TRAIN.IMS_PER_BATCH
         try:
@@ -324,6 +342,17 @@ class SolverWrapper(object):
                                       is_training=False, is_ws=False)
                     v = validation_losses(layers, blobs['im_info'], n, self.global_step, alter)
                     chunks.append(torch.stack([v[name] for name in VAL_TERMS], dim=1))
+                    if detect:
+                        shapes = None
+                        if im_shapes is not None:
+                            shapes = im_shapes[seen:seen + n]
+                            if len(shapes) != n:
+                                raise ValueError("validate: im_shapes names %d images, the pass holds more" % len(im_shapes))
+                        dets, counts = validation_detections(layers, blobs['im_info'], n, thresh, max_per_image, shapes)
+                        if acc is None:
+                            acc = DetectionAccumulator(int(dets.shape[1]) + 1)
+                        acc.add(dets, counts, seen)
+                    seen += n
         finally:
             cfg.TRAIN.IMS_PER_BATCH = ims_per_batch
             self.net.train(was_training)
@@ -335,6 +364,19 @@ class SolverWrapper(object):
         out = {name: float(means[i]) for i, name in enumerate(VAL_TERMS)}
         out['n_images'] = int(per_image.shape[0])
         out['per_image'] = per_image
+        if detect:
+            if len(gt_roidb) != seen:
+                raise ValueError("validate: gt_roidb has %d entries, the pass held %d images" % (len(gt_roidb), seen))
+            if im_shapes is not None and len(im_shapes) != seen:
+                raise ValueError("validate: im_shapes names %d images, the pass held %d" % (len(im_shapes), seen))
+            if classes is None:
+                classes = ['__background__'] + ['class_%d' % j for j in range(1, acc.num_classes)]
+            if len(classes) != acc.num_classes:
+                raise ValueError("the network scores %d classes, `classes` names %d" % (acc.num_classes, len(classes)))
+            ev = evaluate_detections(acc, gt_roidb, classes, ovthresh, score_thresh)
+            for name in ('corloc_list', 'aps', 'mean_ap', 'froc_curve_pts'):
+                out[name] = ev[name]
+            out['detections'] = acc
         if feed_schedule:
             self.on_val_end(out['total'])
         return out
