@@ -603,6 +603,49 @@ WSSDL_API int wssdl_image_to_blob(const void *im, int im_is_f64, int h, int w, d
                      float *blob, int index, int n_images, int Hmax, int Wmax, wssdl_stream_t stream);
 WSSDL_API int wssdl_flip_boxes(float *boxes, int n, int stride, float width, wssdl_stream_t stream);
 
+/* The same image path for a whole mini-batch in one op (roi_data_layer/minibatch_bus.py:259-318: every image of the
+ * batch through prep_im_for_blob, then im_list_to_blob), csrc/image_batch.hip.  AT MOST 3 LAUNCHES per batch whatever
+ * n_images is (2 when no item is rotated): a statistics pass over the u8 planes, a second one that rotates the weak
+ * images' planes, and the pass that writes the blob.  No host synchronise, no read-back, no allocation; no 3-channel
+ * intermediate (the only temporary is the rotated, cropped plane of a rotated item: ONE f64 channel in the workspace).
+ *   arena       all decoded grey planes, u8, one device buffer of arena_bytes bytes
+ *   items_host  the table below, n_images items, in HOST memory: validated before anything is launched
+ *   items_dev   the caller's device copy of the same table (what the kernels read)
+ *   blob        [n_images, Hmax, Wmax, 3] f32: every element is written, the zero padding included
+ * Item i: the plane is arena[offset + y * row_stride + x], y < h, x < w.  `flipped` mirrors it (minibatch_bus.py:271).
+ * use_rotation: skimage.transform.rotate of the flipped plane / 255 with inv_map (row-major 3x3 inverse map, as
+ * wssdl_image_warp takes it) and cval; f64 from there on (blob.py:39-41).  use_crop: the slice [crop_u : h - crop_d,
+ * crop_l : w - crop_r] of the (flipped, rotated) image (:43-47).  use_brightness / use_contrast with the caller's draws
+ * (:49-58; f32 arithmetic for an unrotated item, f64 for a rotated one), - pixel_mean / 255 (:60), resize to
+ * [rows, cols] (:74, wssdl_image_resize), then x / scale (divide != 0) or x * scale (:75-77).
+ * rot_offset (rotated items only): where the item's rotated plane starts in the workspace, in f64 elements = the sum
+ * of (h - crop_u - crop_d) * (w - crop_l - crop_r) over the rotated items before it.
+ * Every image of the blob is bit for bit what wssdl_image_prep / _warp / _adjust_f64 / _resize / _to_blob give for it:
+ * the same operations in the same order, the two reductions in their partial-sum order (grid of 256 x n_images blocks);
+ * the resize's clip range is taken from the extremes of the plane (every step up to the resize's input is monotone).
+ * Every gather is bounded: a tap outside the view reads cval.
+ * WSSDL_ERR_INVALID_ARGUMENT, nothing launched: n_images < 1 or > 65535, a null pointer, h / w / rows / cols < 1,
+ * row_stride < w, a view that leaves the arena, crop offsets that leave no pixel, rows > Hmax or cols > Wmax, scale == 0,
+ * a non-finite inv_map / cval / delta / factor, a wrong rot_offset.  WSSDL_ERR_WORKSPACE: workspace_bytes below
+ * wssdl_image_batch_workspace_bytes(n_images, rotated_pixels), rotated_pixels = the sum named above over all items. */
+typedef struct wssdl_image_batch_item {
+    int64_t offset;                  /* bytes into the arena */
+    int64_t rot_offset;              /* f64 elements into the workspace's plane area (rotated items) */
+    double inv_map[9];
+    double cval;
+    double brightness_delta, contrast_factor;
+    double pixel_mean;               /* 0 .. 255 scale (cfg.PIXEL_MEANS) */
+    double scale;
+    int32_t h, w, row_stride, flipped;
+    int32_t crop_u, crop_d, crop_l, crop_r;
+    int32_t use_crop, use_rotation, use_brightness, use_contrast;
+    int32_t rows, cols, divide, reserved;
+} wssdl_image_batch_item;
+WSSDL_API size_t wssdl_image_batch_workspace_bytes(int n_images, int64_t rotated_pixels);
+WSSDL_API int wssdl_image_batch_blob(const uint8_t *arena, size_t arena_bytes, const wssdl_image_batch_item *items_host,
+                     const wssdl_image_batch_item *items_dev, int n_images, int Hmax, int Wmax, float *blob,
+                     void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
+
 /* ---------------------------------------------------------------------- f3 ---
  * The post-detection step of the test path, fast_rcnn/test_bus.py:360-401, batched over the classes:
  * for every class j = 1 .. num_classes-1 the rows with scores[r, j] > score_thresh, greedy NMS at

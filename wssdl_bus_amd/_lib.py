@@ -99,6 +99,8 @@ SYMBOLS = {
     "wssdl_image_warp": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _d, _i, _vp, _vp, _sz, _vp]),
     "wssdl_image_resize": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "wssdl_flip_boxes": (_i, [_vp, _i, _i, _f, _vp]),
+    "wssdl_image_batch_workspace_bytes": (_sz, [_i, _i64]),
+    "wssdl_image_batch_blob": (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "wssdl_post_detections_workspace_bytes": (_sz, [_i, _i]),
     "wssdl_post_detections": (_i, [_vp, _vp, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_post_detections_batched_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -54,6 +54,8 @@ __C.TRAIN.USE_CONTRAST_ADJUSTMENT = True            # :148
 __C.TRAIN.CONTRAST_ADJUSTMENT_LOWER_FACTOR = 0.2    # :149
 __C.TRAIN.CONTRAST_ADJUSTMENT_UPPER_FACTOR = 1.8    # :150
 __C.TRAIN.IMS_PER_BATCH = 1                         # :115
+__C.TRAIN.USE_FLIPPED = True                        # :133  get_training_roidb appends the mirrored entries
+__C.TRAIN.HAS_RPN = True                            # :194  the data layers' only supported branch
 __C.TRAIN.BATCH_SIZE = 128                          # :118
 __C.TRAIN.FG_FRACTION = 0.25                        # :121
 __C.TRAIN.FG_THRESH = 0.5                           # :124
@@ -90,7 +92,11 @@ __C.TEST.RPN_PRE_NMS_TOP_N = 6000                   # :259
 __C.TEST.RPN_POST_NMS_TOP_N = 300                   # :262
 __C.TEST.RPN_MIN_SIZE = 16                          # :265
 
+__C.IS_MULTISCALE = False                           # :45   True: NotImplementedError, as in the reference
 __C.RNG_SEED = 3                                    # :290
+# :299; where datasets.factory_bus.get_imdb looks for Annotations/, TIFFImages/ and ImageSets/Main/ (the reference:
+# <repository>/../SNUBH_BUS; here the working directory's, since the package ships no data)
+__C.DATA_DIR = "SNUBH_BUS"
 __C.EPS = 1e-14                                     # :293
 __C.USE_GPU_NMS = False                             # :321.  True: nms_wrapper.nms and the proposal layer apply the CUDA
                                                     #  kernel's rule (iou > (float)thresh, nms_kernel.cu:71) instead of

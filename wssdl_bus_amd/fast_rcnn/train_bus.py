@@ -460,3 +460,28 @@ class SolverWrapper(object):
             self.optimizer_ws = self._make_optimizer()
         self._apply(self.optimizer_ws, count_step=True)            # train_op_ws counts the step
         return losses
+
+
+def get_training_roidb(imdb):
+    """imdb.roidb made ready for the data layers: the mirrored twins appended when cfg.TRAIN.USE_FLIPPED, then the keys
+    of roi_data_layer.roidb.prepare_roidb."""
+    from ..roi_data_layer import roidb as rdl_roidb
+    if cfg.TRAIN.USE_FLIPPED:
+        imdb.append_flipped_images()
+    if cfg.TRAIN.HAS_RPN and cfg.IS_MULTISCALE:
+        raise NotImplementedError
+    rdl_roidb.prepare_roidb(imdb)
+    return imdb.roidb
+
+
+def get_data_layer(roidbs, net_name, num_classes, is_training, is_ws=False, is_joint=False):
+    """RoIDataLayerJoint over roidbs = (roidb_s, roidb_ws) when is_joint, else RoIDataLayer over the one roidb."""
+    from ..roi_data_layer.layer_bus import RoIDataLayer
+    from ..roi_data_layer.layer_bus_joint import RoIDataLayerJoint
+    if not cfg.TRAIN.HAS_RPN:
+        raise NotImplementedError("only the cfg.TRAIN.HAS_RPN branch of the data layers exists")
+    if cfg.IS_MULTISCALE:
+        raise NotImplementedError
+    if is_joint:
+        return RoIDataLayerJoint(roidbs[0], roidbs[1], net_name, num_classes, is_training)
+    return RoIDataLayer(roidbs, net_name, num_classes, is_training, is_ws)

@@ -179,6 +179,14 @@ def prep_im_for_blob(gray, net_name, pixel_means, pixel_stds, target_size, max_s
     (np.random.random_integers, :43-46), then -- when training -- brightness (:50) and contrast (:55).
     A rotated image is float64 from skimage.transform.rotate on, like in the reference (the f32 plane goes
     through wssdl_image_warp, the crop is a view, the remaining steps run in wssdl_image_adjust_f64)."""
+    angle, crop, delta, factor = draw_prep_params(gray.shape, is_training, is_ws, rng)
+    return prep_im_with_params(gray, net_name, pixel_means, pixel_stds, target_size, max_size, flipped, angle, crop,
+                               delta, factor, resize=resize)
+
+
+def draw_prep_params(shape, is_training, is_ws=False, rng=None):
+    """The random draws of blob.py:34-58 for one image of `shape` [h, w], in the reference's order (see
+    prep_im_for_blob): (angle, crop, brightness delta, contrast factor), None = that step is off."""
     rng = np.random if rng is None else rng
     crop = delta = factor = angle = None
     if is_ws:
@@ -186,7 +194,7 @@ def prep_im_for_blob(gray, net_name, pixel_means, pixel_stds, target_size, max_s
             a = cfg.TRAIN.ROTATION_MAX_ANGLE
             angle = rng.uniform(-a, a)
         if cfg.TRAIN.USE_CROPPING:
-            h0, w0 = (int(v) for v in gray.shape)
+            h0, w0 = (int(v) for v in shape[:2])
             m = cfg.TRAIN.CROPPING_MAX_MARGIN
             # random_integers(lo, hi) with a float hi == randint(lo, int(hi) + 1) of the legacy stream
             crop = (int(rng.randint(0, int(m * h0) + 1)), int(rng.randint(1, int(m * h0) + 1)),
@@ -198,22 +206,36 @@ def prep_im_for_blob(gray, net_name, pixel_means, pixel_stds, target_size, max_s
         if cfg.TRAIN.USE_CONTRAST_ADJUSTMENT:
             factor = rng.uniform(cfg.TRAIN.CONTRAST_ADJUSTMENT_LOWER_FACTOR,
                                  cfg.TRAIN.CONTRAST_ADJUSTMENT_UPPER_FACTOR)
+    return angle, crop, delta, factor
+
+
+def prep_im_scale(pre_shape, target_size, max_size):
+    """blob.py:61-67,75: (im_scale, the shape asked of the resize) for a pre-resize image [h, w]."""
+    h, w = int(pre_shape[0]), int(pre_shape[1])
+    im_scale = float(target_size) / float(min(h, w))
+    if np.round(im_scale * max(h, w)) > max_size:
+        im_scale = float(max_size) / float(max(h, w))
+    return im_scale, (int(np.round(h * im_scale)), int(np.round(w * im_scale)))
+
+
+def final_scale(net_name, pixel_stds=PIXEL_STDS):
+    """blob.py:75-77 as (scale, divide): x / (std / 255) for the ResNets, x * 255 otherwise."""
+    if net_name[:6] == 'Resnet':
+        return float(np.asarray(pixel_stds).reshape(-1)[0]) / 255.0, True
+    return 255.0, False
+
+
+def prep_im_with_params(gray, net_name, pixel_means, pixel_stds, target_size, max_size, flipped, angle, crop, delta,
+                        factor, resize=None):
+    """prep_im_for_blob with the draws given (draw_prep_params): the chain of single-image launches."""
     if angle is None:
         pre = prep_im_pre_resize(gray, flipped, delta, factor, pixel_means, crop=crop)
     else:
         pre = prep_im_pre_resize_rotated(gray, flipped, angle, delta, factor, pixel_means, crop=crop)
-    h, w = pre.shape[:2]
-    im_scale = float(target_size) / float(min(h, w))
-    if np.round(im_scale * max(h, w)) > max_size:
-        im_scale = float(max_size) / float(max(h, w))
-    shape = (int(np.round(h * im_scale)), int(np.round(w * im_scale)))
+    im_scale, shape = prep_im_scale(pre.shape, target_size, max_size)
     resized = (resize or skimage_resize)(pre, shape)
-    std = float(np.asarray(pixel_stds).reshape(-1)[0])
-    if net_name[:6] == 'Resnet':
-        im = _scale_image(resized, std / 255.0, True)
-    else:
-        im = _scale_image(resized, 255.0, False)
-    return im, im_scale
+    scale, divide = final_scale(net_name, pixel_stds)
+    return _scale_image(resized, scale, divide), im_scale
 
 
 def _scale_image(resized, scale, divide):
@@ -303,6 +325,99 @@ def _get_image_blob_joint(planes_s, flipped_s, planes_ws, flipped_ws, net_name, 
             scales.append(s)
             k += 1
     return im_list_to_blob(ims), scales
+
+
+class _BatchItem(ctypes.Structure):
+    """wssdl_image_batch_item (include/wssdl_bus_hip.h)."""
+    _fields_ = [("offset", ctypes.c_int64), ("rot_offset", ctypes.c_int64), ("inv_map", ctypes.c_double * 9),
+                ("cval", ctypes.c_double), ("brightness_delta", ctypes.c_double), ("contrast_factor", ctypes.c_double),
+                ("pixel_mean", ctypes.c_double), ("scale", ctypes.c_double)] + \
+               [(k, ctypes.c_int32) for k in ("h", "w", "row_stride", "flipped", "crop_u", "crop_d", "crop_l", "crop_r",
+                                              "use_crop", "use_rotation", "use_brightness", "use_contrast", "rows",
+                                              "cols", "divide", "reserved")]
+
+
+def image_batch_table(plan, shapes, offsets):
+    """The item table of wssdl_image_batch_blob for `plan` (roi_data_layer.minibatch_bus.plan_minibatch[_joint]) and
+    planes of `shapes` [h, w] packed row by row at byte `offsets` of one arena -> (ctypes array, rotated pixels)."""
+    items = (_BatchItem * len(plan.images))()
+    scale, divide = final_scale(plan.net_name)
+    rotated = 0
+    for it, im, (h, w), off in zip(items, plan.images, shapes, offsets):
+        h, w = int(h), int(w)
+        it.offset, it.h, it.w, it.row_stride, it.flipped = int(off), h, w, w, int(bool(im.flipped))
+        vh, vw = h, w
+        if im.crop is not None:
+            it.use_crop = 1
+            it.crop_u, it.crop_d, it.crop_l, it.crop_r = (int(v) for v in im.crop)
+            vh, vw = h - it.crop_u - it.crop_d, w - it.crop_l - it.crop_r
+        if (vh, vw) != tuple(im.pre_shape):
+            raise ValueError("plane of shape %s does not belong to this plan (pre-resize shape %s)" % ((h, w), im.pre_shape))
+        it.pixel_mean = float(np.asarray(PIXEL_MEANS).reshape(-1)[0])
+        if im.angle is not None:
+            it.use_rotation = 1
+            it.inv_map[:] = [float(v) for v in skimage_rotate_matrix((h, w), im.angle).reshape(-1)]
+            it.cval = it.pixel_mean / 255.
+            it.rot_offset = rotated
+            rotated += vh * vw
+        if im.delta is not None:
+            it.use_brightness, it.brightness_delta = 1, float(im.delta)
+        it.contrast_factor = 1.0
+        if im.factor is not None:
+            it.use_contrast, it.contrast_factor = 1, float(im.factor)
+        it.rows, it.cols = (int(v) for v in im.resize_shape)
+        it.scale, it.divide = scale, int(divide)
+    return items, rotated
+
+
+def image_batch_blob(plan, planes, device=None):
+    """The zero-padded image blob [N, Hmax, Wmax, 3] f32 of a planned mini-batch in ONE device op
+    (wssdl_image_batch_blob: at most three launches whatever N is), bit for bit what image_blob_per_image -- the chain
+    prep_im_for_blob runs image by image -- gives for the same plan.  `planes`: the N decoded grey planes [h, w] u8
+    (numpy), supervised first.  Per batch: the planes packed into one pinned buffer and copied once, the item table
+    copied once, no read-back."""
+    if len(planes) != len(plan.images) or not planes:
+        raise ValueError("expected one plane per planned image")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    planes = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
+    if any(p.ndim != 2 for p in planes):
+        raise ValueError("expected grey planes [h, w]")
+    sizes = [p.size for p in planes]
+    offsets = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+    total = int(sum(sizes))
+    items, rotated = image_batch_table(plan, [p.shape for p in planes], offsets)
+    host = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+    hv = host.numpy()
+    for p, o in zip(planes, offsets):
+        hv[int(o):int(o) + p.size] = p.reshape(-1)
+    nb = ctypes.sizeof(items)
+    table = torch.empty((nb,), dtype=torch.uint8, pin_memory=True)
+    ctypes.memmove(table.data_ptr(), ctypes.addressof(items), nb)
+    N, Hm, Wm = len(planes), int(plan.blob_shape[0]), int(plan.blob_shape[1])
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        arena = host.to(dev, non_blocking=True)
+        table_d = table.to(dev, non_blocking=True)
+        n = L.wssdl_image_batch_workspace_bytes(N, rotated)
+        ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+        blob = torch.empty((N, Hm, Wm, 3), dtype=torch.float32, device=dev)
+        _lib.check(L.wssdl_image_batch_blob(_lib.ptr(arena), total, ctypes.cast(items, ctypes.c_void_p), _lib.ptr(table_d),
+                                            N, Hm, Wm, _lib.ptr(blob), _lib.ptr(ws), n, _lib.stream()),
+                   "wssdl_image_batch_blob")
+    return blob
+
+
+def image_blob_per_image(plan, planes, device=None):
+    """The same blob through the per-image functions (prep_im_with_params for every image, then im_list_to_blob):
+    the path _get_image_blob[_joint] take, with the plan's draws instead of fresh ones."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    ims = []
+    for im, g in zip(plan.images, planes):
+        g = _lib.to_device(g, torch.uint8, dev)
+        out, _ = prep_im_with_params(g, plan.net_name, PIXEL_MEANS, PIXEL_STDS, im.target_size, im.max_size,
+                                     im.flipped, im.angle, im.crop, im.delta, im.factor)
+        ims.append(out)
+    return im_list_to_blob(ims)
 
 
 def flip_boxes(boxes, width):
