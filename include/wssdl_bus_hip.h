@@ -795,6 +795,56 @@ WSSDL_API int wssdl_eval_detections(int flags, const float *det_boxes, const flo
                      int32_t *ni, int32_t *nok, int32_t *num_all_fps, uint8_t *arr_ok, int32_t *num_fp_per_img,
                      void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
 
+/* ------------------------------------------------------------ proposal recall ---
+ * RPN proposal recall, datasets/imdb.py:125-213 (evaluate_recall) for every (area range a, limit l) cell of the
+ * recall table in one call: the f64 IoU matrix of every image is computed once (the operation order of
+ * utils/bbox.pyx, bit-identical), the cells mask its columns (area) and cut its rows (limit) and run the reference's
+ * greedy matching on it.  No allocation, no read-back, no host synchronisation.
+ *
+ * Candidate boxes, exactly one of
+ *   boxes_f32   padded f32: the first coordinate of row 0 of image 0; row p of image i starts at
+ *               boxes_f32 + (i * P + p) * row_stride and holds x1, y1, x2, y2 (for the proposal layer's
+ *               rois [N, P, 5]: rois + 1, row_stride 5).  With scale [N] f32 (may be NULL) every coordinate is
+ *               divided by scale[i] in f32 (IEEE, round to nearest) and then widened to f64: im_proposals' boxes.
+ *   boxes_f64   padded f64 [N, P, row_stride >= 4], used as they are (the reference's boxes.astype(np.float)).
+ * counts [N] i32: image i has rows 0 .. counts[i]-1 (read as clamped to 0 .. P).
+ * Ground truth, already filtered to gt_classes > 0 and max gt_overlaps == 1: gt_boxes [Gtot, 4] f64, gt_areas [Gtot]
+ * f64 (the roidb's seg_areas), gt_image_offsets [N + 1] i32 in HOST memory (validated before anything is launched,
+ * then copied to the workspace on the stream: keep it valid until the stream has passed the call); image i owns rows
+ * gt_image_offsets[i] .. gt_image_offsets[i+1]-1, at most WSSDL_RECALL_MAX_GT of them.
+ * area_ranges [A, 2] f64, limits [L] i32 (<= 0: no limit, otherwise the first `limit` boxes), thresholds [T] f64:
+ * device memory.
+ *
+ * Per cell and image: the valid gts are those with lo <= area <= hi; num_pos counts them over ALL images (the
+ * reference adds before its `continue`); an image with no boxes contributes nothing else.  Otherwise G_valid rounds:
+ * column maximum per unused gt over the unused boxes (lowest box index among equal maxima, argmax(axis=0)), the gt
+ * with the largest column maximum (lowest gt index among equal maxima), one record, gt and box marked used.  An
+ * overlap of 0 is a legal match and takes the first unused box.  When the boxes run out before the gts (the
+ * reference's assert(gt_ovr >= 0) fires) the remaining rounds record the lowest unused gt with box -1 and overlap -1
+ * and add 1 to the cell's flag word; nothing is read or written out of range.
+ *
+ * Outputs (device; hits, num_pos and flags are zeroed by the call):
+ *   hits [A, L, T] i32       records with overlap >= thresholds[t]
+ *   num_pos [A, L] i32
+ *   flags [A, L] i32         rounds that found no box, 0 for a clean cell
+ *   match_gt, match_box [A, L, Gtot] i32, match_ov [A, L, Gtot] f64 (each may be NULL): image i's records of cell
+ *          (a, l) in ROUND order from slot gt_image_offsets[i] on: the gt's index within the image's rows, the box's
+ *          row, the overlap; the slots of the image that the rounds do not fill hold -1, -1, -1.0.
+ * N == 0, P == 0 and Gtot == 0 are valid.  WSSDL_ERR_INVALID_ARGUMENT: negative sizes, P > WSSDL_RECALL_MAX_BOXES,
+ * A, L or T < 1, row_stride < 4, both or neither box form, a scale without boxes_f32, gt_image_offsets that do not
+ * start at 0, decrease, give an image more than WSSDL_RECALL_MAX_GT rows or do not end at Gtot, a missing pointer,
+ * a workspace smaller than wssdl_proposal_recall_workspace_bytes(N, P, Gtot) (pure host; 0 for sizes the op
+ * rejects).  Behaviour on non-finite coordinates is unspecified. */
+#define WSSDL_RECALL_MAX_GT 1024
+#define WSSDL_RECALL_MAX_BOXES 65536
+WSSDL_API size_t wssdl_proposal_recall_workspace_bytes(int N, int P, int Gtot);
+WSSDL_API int wssdl_proposal_recall(const float *boxes_f32, const float *scale, const double *boxes_f64, int row_stride,
+                     const int32_t *counts, int N, int P, const double *gt_boxes, const double *gt_areas,
+                     const int32_t *gt_image_offsets_host, int Gtot, const double *area_ranges, int A,
+                     const int32_t *limits, int L, const double *thresholds, int T, int32_t *hits, int32_t *num_pos,
+                     int32_t *flags, int32_t *match_gt, int32_t *match_box, double *match_ov, void *workspace,
+                     size_t workspace_bytes, wssdl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,36 +11,11 @@
 // K outputs as one contiguous row (K*8 bytes), rows of consecutive lanes are
 // adjacent, so stores coalesce.  Launch-latency bound at hot-path sizes
 // (8 151 x 3 doubles): see DESIGN.md.
-#include "common.hip.h"
+#include "box_iou.hip.h"
 
 namespace wssdl {
 
 constexpr int QTILE = 256;   // query boxes staged per pass
-
-__device__ __forceinline__ double iou_pair(double bx1, double by1, double bx2, double by2,
-                                           double qx1, double qy1, double qx2, double qy2,
-                                           double qarea) {
-    double iw = fmin(bx2, qx2) - fmax(bx1, qx1) + 1;
-    if (iw > 0) {
-        double ih = fmin(by2, qy2) - fmax(by1, qy1) + 1;
-        if (ih > 0) {
-            double ua = (bx2 - bx1 + 1) * (by2 - by1 + 1) + qarea - iw * ih;
-            return iw * ih / ua;
-        }
-    }
-    return 0.0;
-}
-
-__device__ __forceinline__ double ui_pair(double bx1, double by1, double bx2, double by2,
-                                          double barea, double qx1, double qy1, double qx2,
-                                          double qy2) {
-    double iw = fmin(bx2, qx2) - fmax(bx1, qx1) + 1;
-    if (iw > 0) {
-        double ih = fmin(by2, qy2) - fmax(by1, qy1) + 1;
-        if (ih > 0) return iw * ih / barea;
-    }
-    return 0.0;
-}
 
 template <bool UI>
 __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const double *__restrict__ boxes,

@@ -96,3 +96,18 @@ class bus(object):
                       boxes=mirror_boxes(e['boxes'], self._width(i))) for i, e in enumerate(self.roidb)]
         self.roidb.extend(twins)
         self._names = self._names + self._names
+
+    def evaluate_recall(self, candidate_boxes=None, thresholds=None, area='all', limit=None):
+        """imdb.py:125-213 with the reference's signature and return dict ('ar', 'recalls', 'thresholds',
+        'gt_overlaps'): one cell of recall.evaluate_recall_table -- the device op where a GPU is present, otherwise
+        recall.evaluate_recall_host, the same arithmetic in NumPy.  candidate_boxes=None evaluates the roidb's
+        gt_classes == 0 rows.  A flipped roidb raises KeyError ('seg_areas'), as in the reference."""
+        import torch
+        from . import recall
+        assert area in recall.AREAS, 'unknown area range: {}'.format(area)
+        roidb = self.roidb[:self.num_images]
+        gt = recall.pack_recall_gt(roidb)
+        boxes = recall.non_gt_boxes(roidb) if candidate_boxes is None else [candidate_boxes[i] for i in range(self.num_images)]
+        table = recall.evaluate_recall_table if torch.cuda.is_available() else recall.evaluate_recall_host
+        cell = table(boxes, gt, areas=(area,), limits=(limit,), thresholds=thresholds)[(area, limit)]
+        return {k: cell[k] for k in ('ar', 'recalls', 'thresholds', 'gt_overlaps')}
