@@ -845,6 +845,81 @@ WSSDL_API int wssdl_proposal_recall(const float *boxes_f32, const float *scale, 
                      int32_t *flags, int32_t *match_gt, int32_t *match_box, double *match_ov, void *workspace,
                      size_t workspace_bytes, wssdl_stream_t stream);
 
+/* ---------------------------------------------------------------------- f7 ---
+ * Qualitative results: the ground truth and the detections of all N images of a pass drawn over their grey planes in
+ * one op (what fast_rcnn/test_bus.py:337-390 and fast_rcnn/train_bus.py:824-870 do per image with matplotlib),
+ * csrc/draw_detect.hip.  TWO LAUNCHES whatever N is (one builds the per-image item records, one paints); no
+ * read-back, no allocation on the device, capturable.  The semantics are this project's own and exact; matplotlib's
+ * anti-aliased rendering is NOT reproduced and parity with its pictures is unpinned.
+ *
+ * Inputs (device memory unless said otherwise)
+ *   arena        all grey planes, u8, one buffer of arena_bytes bytes
+ *   items_host   N items of the table below in HOST memory (validated before anything is launched); items_dev: the
+ *                caller's device copy of it.  Plane i is arena[offset + y * row_stride + x], y < h, x < w; its picture
+ *                is the tight [h, w, 3] u8 array at out[out_offset ...].
+ *   gt_boxes [G, 4] f32 in the plane's pixels, gt_classes [G] i32, gt_image_offsets [N + 1] i32 (a host copy that is
+ *                validated and a device copy that the kernels read): image i owns rows offsets[i] .. offsets[i+1]-1,
+ *                at most WSSDL_DRAW_MAX_GT of them.  A row whose class is outside 0 .. K-1 is not drawn.
+ *   dets [N, K-1, P, 5] f32 (x1, y1, x2, y2, score), counts [N, K-1] i32, as the batched post-detection op or a
+ *                DetectionAccumulator leave them.  Rows at and beyond counts are never read.
+ *   colours [K, 3] u8 (r, g, b) per class; glyphs [n_glyphs, 7] u8: 5x7 bitmaps, one byte per row from the top, bit 4
+ *                the left column, in this fixed order: index 0 space, 1 '.', 2 '-', 3 '_', 4..13 '0'..'9', further
+ *                ones (14..39 'a'..'z') as the caller likes; labels [K, WSSDL_DRAW_LABEL_LEN] u8 glyph indices per
+ *                class, terminated by 255 (an index >= n_glyphs paints nothing).
+ *   style        HOST pointer, read during the call.  line_width odd 1..15 (default 3), dash_on 1..255 (11), dash_off
+ *                0..255 (5), glyph_scale 1..4 (2), tag_pad 0..15 (3), tag_dy 0..64 (4), max_draw 0..192 (10),
+ *                vis_thresh not NaN (0.5).
+ * Output: out, u8, out_bytes bytes.  Bytes outside every image are not written.
+ *
+ * Per image, in this painting order (later items go over earlier ones):
+ *   1. every pixel starts as (g, g, g);
+ *   2. the image's ground-truth boxes in table order: a solid outline in the class colour, no tag;
+ *   3. detections class by class j = 1 .. K-1 and within a class by row: rows p = 0 .. min(max_draw, counts[i, j-1],
+ *      P) - 1 are candidates; a row is drawn only if its score > vis_thresh (f32 compare, strict, false for NaN);
+ *      counts[i, 0] == -1 (the batched op's overflow flag) draws no detection of image i.  A drawn row gets a dashed
+ *      outline in the class colour, then its tag, then its text.
+ * Outline: corners X1 = rint(x1) and so on (round half to even of the f32).  A box with a non-finite coordinate or one
+ * of |v| >= 2^24, or with X2 < X1 or Y2 < Y1, is skipped.  With hw = (line_width - 1) / 2 pixel (x, y) is on the outline
+ * when X1-hw <= x <= X2+hw and Y1-hw <= y <= Y2+hw and not (X1+hw < x < X2-hw and Y1+hw < y < Y2-hw).  Dashed: a
+ * pixel of a horizontal band (|y-Y1| <= hw or |y-Y2| <= hw; the corners count as horizontal) is on when
+ * (x - (X1-hw)) mod (dash_on + dash_off) < dash_on, every other outline pixel when (y - (Y1-hw)) mod (dash_on +
+ * dash_off) < dash_on.  An on pixel becomes the class colour; pixels outside the image are dropped.
+ * Text: the class label, a space, the score as d.ddd ('{:s} {:.3f}').  The decimals come from the f32's bits: with
+ * score = m * 2^-s (m the 24-bit significand, or the subnormal one) n = round-half-even(m * 1000 / 2^s) in 64-bit
+ * integers, n = 0 once s > 40, and the text is n / 1000 '.' n % 1000 (three digits).  Outside [0, 1] the text is
+ * unspecified (one leading digit, sign dropped); no access leaves its arrays.
+ * A glyph cell is 5x7 bits times glyph_scale, the advance 6 * glyph_scale: Wt = n_chars * 6 * glyph_scale -
+ * glyph_scale, Ht = 7 * glyph_scale.  The tag is [X1, X1 + Wt + 2*tag_pad) x [Y1 + tag_dy, Y1 + tag_dy + Ht +
+ * 2*tag_pad): every pixel of it inside the image becomes (o + colour + 1) >> 1 per channel, then every set glyph bit
+ * inside the image (255, 255, 255); the text's origin is the tag's top-left plus tag_pad.
+ *
+ * WSSDL_ERR_INVALID_ARGUMENT, nothing launched: N < 1 or > 65535, K < 2 or > 65, G or P < 0, n_glyphs <
+ * WSSDL_DRAW_MIN_GLYPHS or > 254, a null pointer where data is needed, h / w < 1, row_stride < w, a plane or an output
+ * image that leaves its arena, output images that overlap, more than WSSDL_DRAW_MAX_GT boxes in one image, (K-1) *
+ * max_draw > WSSDL_DRAW_MAX_DETS, a style value outside its range, gt_image_offsets (host) that are not non-decreasing
+ * from 0 to G.  WSSDL_ERR_WORKSPACE: a workspace below the workspace query's size for N (pure host; 0 for an N the
+ * op rejects). */
+#define WSSDL_DRAW_MAX_GT 64
+#define WSSDL_DRAW_MAX_DETS 192
+#define WSSDL_DRAW_LABEL_LEN 24
+#define WSSDL_DRAW_MIN_GLYPHS 14
+typedef struct wssdl_draw_item {
+    int64_t offset;                  /* bytes into the arena */
+    int64_t out_offset;              /* bytes into out */
+    int32_t h, w, row_stride, reserved;
+} wssdl_draw_item;
+typedef struct wssdl_draw_style {
+    int32_t line_width, dash_on, dash_off, glyph_scale, tag_pad, tag_dy, max_draw;
+    float vis_thresh;
+} wssdl_draw_style;
+WSSDL_API size_t wssdl_draw_workspace_bytes(int N);
+WSSDL_API int wssdl_draw_detections(const uint8_t *arena, size_t arena_bytes, const wssdl_draw_item *items_host,
+                     const wssdl_draw_item *items_dev, int N, const float *gt_boxes, const int32_t *gt_classes,
+                     const int32_t *gt_image_offsets_host, const int32_t *gt_image_offsets_dev, int G,
+                     const float *dets, const int32_t *counts, int K, int P, const uint8_t *colours,
+                     const uint8_t *glyphs, int n_glyphs, const uint8_t *labels, const wssdl_draw_style *style,
+                     uint8_t *out, size_t out_bytes, void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

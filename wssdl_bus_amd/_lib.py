@@ -19,6 +19,7 @@ DATASET_SNUBH, DATASET_SNUBH_FG, DATASET_FG_ONLY = 0, 1, 2
 MAX_ANCHORS, MAX_GT = 32, 64
 EVAL_QUANTISE, EVAL_BATCHED = 1, 2
 RECALL_MAX_GT, RECALL_MAX_BOXES = 1024, 65536         # WSSDL_RECALL_MAX_GT, WSSDL_RECALL_MAX_BOXES
+DRAW_MAX_GT, DRAW_MAX_DETS, DRAW_LABEL_LEN, DRAW_MIN_GLYPHS = 64, 192, 24, 14     # WSSDL_DRAW_*
 POST_AGNOSTIC_MAX_UNION = 12000         # WSSDL_POST_AGNOSTIC_MAX_UNION: (K-1) * rows per image of the class-agnostic op
 
 # every symbol include/wssdl_bus_hip.h declares: (restype, argtypes)
@@ -118,6 +119,9 @@ SYMBOLS = {
     "wssdl_proposal_recall_workspace_bytes": (_sz, [_i, _i, _i]),
     "wssdl_proposal_recall": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wssdl_draw_workspace_bytes": (_sz, [_i]),
+    "wssdl_draw_detections": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp,
+                                   _vp, _sz, _vp, _sz, _vp]),
     "wssdl_mil_select": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "wssdl_mil_loss_forward": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp]),
     "wssdl_mil_loss_backward": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp]),

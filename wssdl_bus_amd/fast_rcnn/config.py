@@ -26,6 +26,7 @@ cfg = __C
 __C.TRAIN = AttrDict()
 __C.TRAIN.LEARNING_RATE = 0.0005                    # config.py:40
 __C.TRAIN.MOMENTUM = 0.9                            # config.py:41  SolverWrapper(opt='sgd'): Nesterov momentum
+__C.TRAIN.DISPLAY = 10                              # config.py:44  iterations between the training loop's status lines
 __C.TRAIN.WEIGHT_DECAY = 0.0005                     # config.py:46
 # batch renormalisation at every 'BN' site (network.py:123,160,342,384,507,519: renorm=cfg.TRAIN.USE_BRN).  The reference's
 # default is True (:54); here it is False, so that 'BN' stays the plain batch norm every golden and the benchmark
@@ -34,6 +35,7 @@ __C.TRAIN.USE_BRN = False                           # :54 (reference: True)
 __C.TRAIN.GN_MIN_NUM_G = 8                        # :55  group norm: G = min(this, C // GN_MIN_CHS_PER_G)
 __C.TRAIN.GN_MIN_CHS_PER_G = 4                      # :56
 __C.TRAIN.WS_IMS_PER_BATCH = 2                      # :49
+__C.TRAIN.WS_TRAIN_INTERVAL = 1                     # :50  alternating loop: the weak half runs when (iter+1) % this == 0
 __C.TRAIN.WS_LOSS_USE_ADAPTIVE_SCALE_FACTOR = True  # :51
 __C.TRAIN.WS_LOSS_SCALE_FACTOR = 0.5                # :52
 __C.TRAIN.WS_MAL_PCT = 0.2209                       # :60
@@ -61,6 +63,9 @@ __C.TRAIN.FG_FRACTION = 0.25                        # :121
 __C.TRAIN.FG_THRESH = 0.5                           # :124
 __C.TRAIN.BG_THRESH_HI = 0.5                        # :128
 __C.TRAIN.BG_THRESH_LO = 0.0                        # :130
+__C.TRAIN.SNAPSHOT_ITERS = 10                       # :160  iterations between snapshots (fast_rcnn/snapshot.py)
+__C.TRAIN.TEST_ITERS = 10                           # :163  iterations between validation passes
+__C.TRAIN.SNAPSHOT_INFIX = ''                       # :168  <net>_fast_rcnn[_<infix>]_iter_<n>.pt
 __C.TRAIN.BBOX_INSIDE_WEIGHTS = (1.0, 1.0, 1.0, 1.0)   # :178
 __C.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED = False   # :181 (read by proposal_target_layer_tf_bus.py:221-224)
 __C.TRAIN.BBOX_NORMALIZE_MEANS = (0.0, 0.0, 0.0, 0.0)  # :182

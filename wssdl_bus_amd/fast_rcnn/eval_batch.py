@@ -26,9 +26,13 @@ def accumulate_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_
 
 
 def evaluate_images(net, planes, gt_roidb, net_name, batch_size=8, classes=None, thresh=0.05, max_per_image=300,
-                    ovthresh=0.5, score_thresh=0.5, use_07_metric=True):
+                    ovthresh=0.5, score_thresh=0.5, use_07_metric=True, vis_dir=None, image_paths=None):
     """evaluate_detections (datasets/voc_eval_bus.py) of the network's detections on `planes` against gt_roidb
-    (one entry per plane).  classes: the class names, '__background__' first (default: numbered)."""
+    (one entry per plane).  classes: the class names, '__background__' first (default: numbered).
+    vis_dir: also draw ground truth and detections over every plane on the device (fast_rcnn/vis.py: one op for all
+    images, one read-back) and write <vis_dir>/<image basename>.png -- the reference's test_net(vis=True),
+    test_bus.py:337-390; image_paths names the images (default: their index, six digits).  None (the default) draws
+    nothing and changes nothing."""
     if len(planes) != len(gt_roidb):
         raise ValueError("one gt_roidb entry per image")
     acc = accumulate_images(net, planes, net_name, batch_size, thresh, max_per_image)
@@ -38,4 +42,10 @@ def evaluate_images(net, planes, gt_roidb, net_name, batch_size=8, classes=None,
         classes = ['__background__'] + ['class_%d' % j for j in range(1, acc.num_classes)]
     if len(classes) != acc.num_classes:
         raise ValueError("the network scores %d classes, `classes` names %d" % (acc.num_classes, len(classes)))
+    if vis_dir is not None:
+        from . import vis
+        names = image_paths if image_paths is not None else ['%06d' % i for i in range(len(planes))]
+        if len(names) != len(planes):
+            raise ValueError("one image path per plane")
+        vis.save_qualitative(vis.draw_detections(planes, gt_roidb, acc, classes), vis.qualitative_paths(vis_dir, names))
     return evaluate_detections(acc, gt_roidb, classes, ovthresh, score_thresh, use_07_metric)

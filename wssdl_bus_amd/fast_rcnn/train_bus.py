@@ -4,7 +4,10 @@ Reference: code/lib/fast_rcnn/train_bus.py:184-270 (alternating losses), :603-67
 losses), :286-301 / :694-705 (optimisers and the per-variable sum of the two gradient sets),
 :334-394 (one alternating iteration = a supervised step then a weak step).  Only what drives
 the hot path's backward is restated here, with the optimisers and
-learning-rate schedules of fast_rcnn/optim.py; data loading, snapshots and logging are out of scope.
+learning-rate schedules of fast_rcnn/optim.py.  The program around the steps -- train_net / train_net_alter
+(:1055-1087) -- is at the end of this module: thin entry points over fast_rcnn/train_loop.py (the loops, log.txt,
+summary.jsonl), fast_rcnn/snapshot.py (snapshots and resume) and fast_rcnn/vis.py (qualitative results drawn on the
+device); the data layers are roi_data_layer/.
 """
 import os
 
@@ -399,8 +402,9 @@ class SolverWrapper(object):
     def check_flags(self):
         """Synchronising look at the deferred device flags (RoI-pool overflow, NMS time-out).  The poll in
         _apply runs one step late -- by the time it raises, the optimiser has already applied the step before
-        it, so the parameters of that step are tainted -- and it never sees the last step: call this before
-        saving parameters (the reference's snapshot, train_bus.py:66-101) and at the end of training."""
+        it, so the parameters of that step are tainted -- and it never sees the last step.  The package calls this
+        before every snapshot (snapshot.save_snapshot: a raised flag means no file is written) and at the end of
+        training (train_loop); a caller who saves parameters by other means calls it first."""
         roi_pooling_op.check_flags()
 
     def joint_backward(self, blobs):
@@ -474,6 +478,16 @@ def get_training_roidb(imdb):
     return imdb.roidb
 
 
+def get_test_roidb(imdb):
+    """imdb.roidb for the validation / test pass (reference fast_rcnn/test_bus.py:416-430): prepare_roidb's keys, no
+    mirrored twins."""
+    from ..roi_data_layer import roidb as rdl_roidb
+    if cfg.TRAIN.HAS_RPN and cfg.IS_MULTISCALE:
+        raise NotImplementedError
+    rdl_roidb.prepare_roidb(imdb)
+    return imdb.roidb
+
+
 def get_data_layer(roidbs, net_name, num_classes, is_training, is_ws=False, is_joint=False):
     """RoIDataLayerJoint over roidbs = (roidb_s, roidb_ws) when is_joint, else RoIDataLayer over the one roidb."""
     from ..roi_data_layer.layer_bus import RoIDataLayer
@@ -485,3 +499,33 @@ def get_data_layer(roidbs, net_name, num_classes, is_training, is_ws=False, is_j
     if is_joint:
         return RoIDataLayerJoint(roidbs[0], roidbs[1], net_name, num_classes, is_training)
     return RoIDataLayer(roidbs, net_name, num_classes, is_training, is_ws)
+
+
+def train_net(network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test, output_dir,
+              pretrained_model=None, max_iters=80000, s_start_iter=0, s_end_iter=80000, ws_start_iter=0, ws_end_iter=80000,
+              opt='adam', lr=5e-4, lr_scheduling='const', vis=False, *, resume=None, dist_ctx=None, val_ims_per_batch=1,
+              max_per_image=300, thresh=0.05):
+    """Train a Faster R-CNN using combined mini-batches from supervised and weakly supervised sets (train_bus.py:1073-1087,
+    without the TensorFlow session): SolverWrapper(network, lr, dist_ctx, opt, lr_scheduling, max_iters), then
+    train_loop.train_model.  opt='adam' is the reference's TF-form Adam, as its command line has it (SolverWrapper's own
+    default opt=None is another optimiser).  pretrained_model: a snapshot written by this package or a torch state_dict
+    file, loaded non-strictly before the first step, the missing names printed; the reference's .npy layout of
+    TensorFlow variables is out of scope.  resume: a snapshot to continue from (fast_rcnn/snapshot.py).  vis: the
+    validation pass's pictures go to <output_dir>/test (fast_rcnn/vis.py).  val_ims_per_batch: images per validation
+    forward.  Returns train_loop's history dict."""
+    from . import train_loop
+    return train_loop._train(False, network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test,
+                             output_dir, pretrained_model, max_iters, (s_start_iter, s_end_iter, ws_start_iter, ws_end_iter), opt, lr,
+                             lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh)
+
+
+def train_net_alter(network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test, output_dir,
+                    pretrained_model=None, max_iters=80000, s_start_iter=0, s_end_iter=80000, ws_start_iter=0, ws_end_iter=80000,
+                    opt='adam', lr=5e-4, lr_scheduling='const', vis=False, *, resume=None, dist_ctx=None, val_ims_per_batch=1,
+                    max_per_image=300, thresh=0.05):
+    """Train a Faster R-CNN using alternating mini-batches each from supervised and weakly supervised sets
+    (train_bus.py:1055-1069): as train_net, over train_loop.train_model_alter."""
+    from . import train_loop
+    return train_loop._train(True, network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test,
+                             output_dir, pretrained_model, max_iters, (s_start_iter, s_end_iter, ws_start_iter, ws_end_iter), opt, lr,
+                             lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh)

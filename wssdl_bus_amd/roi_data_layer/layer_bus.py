@@ -37,6 +37,16 @@ class RoIDataLayer(object):
         start, self._cur = self._cur, self._cur + n
         return self._perm[start:start + n]
 
+    def state_dict(self):
+        """The permutation and the cursor: what the next index draws depend on (besides the RNG stream's own state)."""
+        return dict(perm=np.array(self._perm, dtype=np.int64), cur=int(self._cur))
+
+    def load_state_dict(self, state):
+        perm = np.array(state["perm"], dtype=np.int64)
+        if perm.shape != (len(self._roidb),):
+            raise ValueError("data-layer state of %d entries, this roidb has %d" % (perm.size, len(self._roidb)))
+        self._perm, self._cur = perm, int(state["cur"])
+
     def forward(self):
         picked = self._get_next_minibatch_inds()
         return get_minibatch([self._roidb[i] for i in picked], self._net_name, self._num_classes, self._is_training,

@@ -40,6 +40,19 @@ class RoIDataLayerJoint(object):
         self._cur_ws += nw
         return db_inds_s, db_inds_ws
 
+    def state_dict(self):
+        """Both permutations and cursors: what the next index draws depend on (besides the RNG stream's own state)."""
+        return dict(perm_s=np.array(self._perm_s, dtype=np.int64), cur_s=int(self._cur_s),
+                    perm_ws=np.array(self._perm_ws, dtype=np.int64), cur_ws=int(self._cur_ws))
+
+    def load_state_dict(self, state):
+        perm_s, perm_ws = np.array(state["perm_s"], dtype=np.int64), np.array(state["perm_ws"], dtype=np.int64)
+        if perm_s.shape != (len(self._roidb_s),) or perm_ws.shape != (len(self._roidb_ws),):
+            raise ValueError("data-layer state of %d + %d entries, these roidbs have %d + %d"
+                             % (perm_s.size, perm_ws.size, len(self._roidb_s), len(self._roidb_ws)))
+        self._perm_s, self._cur_s = perm_s, int(state["cur_s"])
+        self._perm_ws, self._cur_ws = perm_ws, int(state["cur_ws"])
+
     def forward(self):
         picked_s, picked_ws = self._get_next_minibatch_inds()
         return get_minibatch_joint([self._roidb_s[i] for i in picked_s], [self._roidb_ws[i] for i in picked_ws],

@@ -209,8 +209,9 @@ def poll_flags():
 def check_flags():
     """Synchronising check: raises HipCallError if any compact RoI-pool call raised a flag, or if an earlier sync-free
     poll swallowed an NMS time-out (a step that was applied with an image's proposals missing: tainted_steps()).  The
-    caller must call it -- before it writes a snapshot or reports a result; the package's own training loop does not
-    (it polls with poll_flags())."""
+    train steps only poll (poll_flags()); the package's training loop calls this before every snapshot
+    (fast_rcnn/snapshot.save_snapshot) and at the end of training, and a caller who drives the steps by hand calls it
+    before saving parameters or reporting a result."""
     for f in list(_device_flags.values()):
         _DeviceFlags._raise(f.read_and_clear())
     if _tainted["steps"]:

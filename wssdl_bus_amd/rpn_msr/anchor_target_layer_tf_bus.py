@@ -29,6 +29,16 @@ _DATASETS = {"SNUBH": _lib.DATASET_SNUBH, "SNUBH_FG": _lib.DATASET_SNUBH_FG}
 _device_calls = [0]
 
 
+def get_device_calls():
+    """How many device-sampler calls have been folded into the anchor subsample's seeds (saved by fast_rcnn/snapshot.py)."""
+    return int(_device_calls[0])
+
+
+def set_device_calls(n):
+    """Restores the call counter, so that a resumed run draws what the uninterrupted one would have drawn."""
+    _device_calls[0] = int(n)
+
+
 def _shape_hw(rpn_cls_score):
     shp = rpn_cls_score.shape if hasattr(rpn_cls_score, "shape") else tuple(rpn_cls_score)
     return int(shp[0]), int(shp[1]), int(shp[2])

@@ -25,6 +25,16 @@ DEBUG = False
 _device_calls = [0]
 
 
+def get_device_calls():
+    """How many device-sampler calls have been folded into the RoI sampler's seeds (saved by fast_rcnn/snapshot.py)."""
+    return int(_device_calls[0])
+
+
+def set_device_calls(n):
+    """Restores the call counter, so that a resumed run draws what the uninterrupted one would have drawn."""
+    _device_calls[0] = int(n)
+
+
 def tag_counts(rois, counts):
     """Remember the per-image row counts of a proposal blob (rows are grouped by image,
     ascending) so that the layers below need not read the batch column back."""
