@@ -518,14 +518,22 @@ WSSDL_API int wssdl_multi_task_loss_per_image(
 WSSDL_API int wssdl_loss_libm_probe(const float *x, int64_t n, int which, float *y, wssdl_stream_t stream);
 
 /* ---------------------------------------------------------------------- f1 ---
- * MIL bag-instance selection: mil/core.py:11-46 (get_bag_logit) with the selectors
- * get_mal_max_logit :60-69, get_ben_max_logit :49-57, get_mass_max_logit :88-96.
+ * MIL bag functions: mil/core.py:11-46 (get_bag_logit) with its five bag functions.  Four SELECT one row of the bag:
+ * get_mal_max_logit :60-69 (largest class-2 logit), get_ben_max_logit :49-57 (largest class-1 logit),
+ * get_mass_max_logit :88-96 (smallest class-0 logit), get_disc_max_logit :77-85 (largest logit over the classes
+ * 1..num_classes-1).  Scanning keeps a row only on a strict improvement, and among equal keys the lowest row index
+ * wins (tf.arg_max / tf.arg_min: first extremum).  get_mean_ben_logit :71-74 POOLS: the bag's logit row is
+ * [0, m, 0, ...] (every class but 1 is 0, for num_classes > 3 too), m = mean of the bag's class-1 logits -- summed in
+ * f64 (per-thread partials, then a fixed tree: the same bits on every run), divided by the count in f64, rounded to
+ * f32 once.
  * instance_logits [R,num_classes] f32; the bag of row r is (int)(bag_of_row[r*bag_stride] -
  * bag_offset) (e.g. the batch-index column of the rois blob minus IMS_PER_BATCH,
  * fast_rcnn/train_bus.py:653); bag_labels [n_bags] i32.  Bags labelled 1 use selector_label1,
  * the others selector_other (train_bus.py:241,655).  row_out [n_bags] i32 receives the row to
- * gather (first extremum; -1 for an empty bag), count_out (optional) the instances per bag. */
-enum wssdl_mil_selector { WSSDL_MIL_MAL_MAX = 0, WSSDL_MIL_BEN_MAX = 1, WSSDL_MIL_MASS_MAX = 2 };
+ * gather (first extremum; the bag's first row for a mean-ben bag; -1 for an empty bag, whatever the selector, so
+ * "row >= 0" means "not empty"), count_out (optional) the instances per bag. */
+enum wssdl_mil_selector { WSSDL_MIL_MAL_MAX = 0, WSSDL_MIL_BEN_MAX = 1, WSSDL_MIL_MASS_MAX = 2,
+                          WSSDL_MIL_DISC_MAX = 3, WSSDL_MIL_MEAN_BEN = 4 };
 WSSDL_API int wssdl_mil_select(const float *instance_logits, int R, int num_classes,
                      const float *bag_of_row, int bag_stride, float bag_offset,
                      const int32_t *bag_labels, int n_bags, int selector_label1,
@@ -533,13 +541,29 @@ WSSDL_API int wssdl_mil_select(const float *instance_logits, int R, int num_clas
                      wssdl_stream_t stream);
 
 /* The MIL term as one op: selection as above, then fast_rcnn/train_bus.py:246-260 / :657-671 --
- * softmax CE of the selected instance against the bag label, weighted by class_weights_host[label]
- * ([0, WS_MAL_PCT, 1 - WS_MAL_PCT], :252,:664; host array [num_classes]) and by `scale`
+ * softmax CE of the bag's logit row against the bag label, weighted by class_weights_host[label]
+ * ([0, WS_MAL_PCT, 1 - WS_MAL_PCT], :252,:664; host array [num_classes], 3 <= num_classes <= 8) and by `scale`
  * (1 - 0.99 * 0.9^floor(step/2000) or the constant, :248,:659), mean over the n_bags bags.  An empty
- * bag contributes 0 and still counts in the mean.  loss [1] f32; row_out [n_bags] i32 and bag_loss
- * [n_bags] f32 are outputs the backward (row_out) and the caller may read.  The backward writes the
- * gradient of the whole [R,num_classes] logits block (zeros except the selected rows);
- * grad_loss [1] f32 on the device. */
+ * bag contributes 0, gets no gradient and still counts in the mean, whatever its selector.  loss [1] f32; row_out
+ * [n_bags] i32 and bag_loss [n_bags] f32 are outputs the backward (row_out) and the caller may read.  The backward
+ * writes the gradient of the whole [R,num_classes] logits block; grad_loss [1] f32 on the device.  With c =
+ * grad_loss * scale * class_weights[label] / n_bags:
+ *   a selecting bag   its selected row gets c * (softmax - onehot(label)), the label's component formed as minus the
+ *                     sum of the others; every other row of the bag zeros;
+ *   a mean-ben bag    every row r of the bag gets g[r,1] = c * d / count and zeros in the other columns, d the class-1
+ *                     component of (softmax - onehot(label)) of the pooled row: p_1 when label != 1, minus the sum of
+ *                     the other probabilities when label == 1;
+ *   rows of no bag    zeros.
+ * Forward: three launches (select, bag term, finish), backward: one, whatever the selector pair.
+ *
+ * wssdl_mil_loss_forward / _backward carry no per-bag count and no pooled row: they take the selecting functions
+ * only, selectors 0..3 (WSSDL_MIL_DISC_MAX included), with the results they always had for 0..2, and return
+ * WSSDL_ERR_INVALID_ARGUMENT for WSSDL_MIL_MEAN_BEN.  wssdl_mil_loss_backward takes no selectors: it puts the
+ * gradient on the rows named by `rows`, whichever selecting pair found them.
+ * wssdl_mil_pool_forward / _backward take all of 0..4 through the same kernels (for 0..2 bit for bit the results of
+ * the pair above) and add bag_count [n_bags] i32 (instances per bag) and bag_logits [n_bags,num_classes] f32 (the
+ * logit row each bag's term is taken of: the selected row's, [0, m, 0, ...] for a mean-ben bag, zeros for an empty
+ * bag), which the backward reads. */
 WSSDL_API int wssdl_mil_loss_forward(const float *instance_logits, int R, int num_classes,
                            const float *bag_of_row, int bag_stride, float bag_offset,
                            const int32_t *bag_labels, int n_bags, int selector_label1,
@@ -550,6 +574,18 @@ WSSDL_API int wssdl_mil_loss_backward(const float *instance_logits, int R, int n
                             const int32_t *bag_labels, int n_bags, const int32_t *rows,
                             const float *class_weights_host, float scale, const float *grad_loss,
                             float *grad_logits, wssdl_stream_t stream);
+WSSDL_API int wssdl_mil_pool_forward(const float *instance_logits, int R, int num_classes,
+                           const float *bag_of_row, int bag_stride, float bag_offset,
+                           const int32_t *bag_labels, int n_bags, int selector_label1,
+                           int selector_other, const float *class_weights_host, float scale,
+                           float *loss, int32_t *row_out, int32_t *bag_count, float *bag_logits,
+                           float *bag_loss, wssdl_stream_t stream);
+WSSDL_API int wssdl_mil_pool_backward(const float *instance_logits, int R, int num_classes,
+                            const float *bag_of_row, int bag_stride, float bag_offset,
+                            const int32_t *bag_labels, int n_bags, int selector_label1,
+                            int selector_other, const int32_t *rows, const int32_t *bag_count,
+                            const float *bag_logits, const float *class_weights_host, float scale,
+                            const float *grad_loss, float *grad_logits, wssdl_stream_t stream);
 
 /* ---------------------------------------------------------------------- f4 ---
  * The pinnable half of the host image path, on the device.  utils/blob.py:34-79

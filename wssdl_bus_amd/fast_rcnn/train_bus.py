@@ -172,8 +172,15 @@ def _mil_per_image(cls_score, image_column, mil_label, n_images, global_step, fu
     return torch.stack(out).float()
 
 
+def default_mil_funcs(alter):
+    """The reference's own pair (for bags labelled 1, for the others): [mass-max, mal-max] in the alternating wiring
+    (train_bus.py:241), [mal-max, mal-max] in the combined one (:655)."""
+    return [mil_core.get_mass_max_logit, mil_core.get_mal_max_logit] if alter \
+        else [mil_core.get_mal_max_logit, mil_core.get_mal_max_logit]
+
+
 @torch.no_grad()
-def validation_losses(layers, im_info, n_images, global_step, alter):
+def validation_losses(layers, im_info, n_images, global_step, alter, funcs=None):
     """The loss half of the reference's validation pass (train_bus.py:427-534 alternating, :792-899 combined) for
     the N = n_images images of ONE forward: a pure function of that forward's `layers` (run with
     is_training=False, is_ws=False).  -> dict of [N] f32 tensors on the layers' device, nothing read back:
@@ -185,7 +192,8 @@ def validation_losses(layers, im_info, n_images, global_step, alter):
                           plateau schedule is fed;
       mil_cross_entropy   mil_loss of image i as one bag of its own roi-data rows, bag label im_info[i, 3], class
                           prior and scale factor of mil_loss at `global_step`, selectors [get_mass_max_logit,
-                          get_mal_max_logit] when `alter` else [get_mal_max_logit, get_mal_max_logit].
+                          get_mal_max_logit] when `alter` else [get_mal_max_logit, get_mal_max_logit] -- or the
+                          pair `funcs` (for bags labelled 1, for the others) of mil.core's bag functions.
 
     For the alternating wiring the MIL slot is the reference's value (:239-260 under the feed of :436-438).  For the
     combined wiring it is UNPINNED: the reference's graph slices the rows past len(label) (:650-653), of which a
@@ -198,8 +206,8 @@ def validation_losses(layers, im_info, n_images, global_step, alter):
     out = {name: losses[:, i] for i, name in enumerate(TERMS)}
     out['total'] = out['rpn_cross_entropy'] + out['rpn_loss_box'] + out['cross_entropy'] + out['loss_box']   # :519
     rois = layers['roi-data'][0]
-    funcs = [mil_core.get_mass_max_logit, mil_core.get_mal_max_logit] if alter \
-        else [mil_core.get_mal_max_logit, mil_core.get_mal_max_logit]
+    if funcs is None:
+        funcs = default_mil_funcs(alter)
     out['mil_cross_entropy'] = _mil_per_image(layers['cls_score'][:rois.shape[0]], rois[:, 0],
                                               im_info[:n, 3].to(torch.int32), n, global_step, funcs)
     return out
@@ -226,18 +234,27 @@ class SolverWrapper(object):
     Alternating mode under 'sgd': the reference's supervised op is minimize(loss, global_step=global_step) (:293),
     so BOTH halves of an iteration count the global step (two per iteration); under the other optimisers only the
     weak half does.  The MIL scale factor 1 - 0.99 * 0.9^floor(step / 2000) and the 'pc' schedule read that count,
-    so this is reproduced."""
+    so this is reproduced.
+
+    mil_funcs: the bag functions of the MIL term, a pair (for bags labelled 1, for the others) like the reference's
+    `funcs` (:241, :655), each one of mil.core's five functions or its name in mil.core.MIL_FUNCS ('mal_max',
+    'ben_max', 'mass_max', 'disc_max', 'mean_ben').  None keeps the reference's wiring-specific pairs: [mass_max,
+    mal_max] in the weak half of an alternating iteration, [mal_max, mal_max] in a combined step, and the matching
+    one in validate.  A given pair is used by joint_backward, weak_backward and validate alike.  It is a constructor
+    argument like `opt`: snapshots do not store it, a resumed run passes it again."""
 
     OPTS = (None, 'adam', 'amsgrad', 'sgd')
     SCHEDULES = ('const', 'pc', 'rop')
 
-    def __init__(self, network, lr=None, dist_ctx=None, opt=None, lr_scheduling='const', max_iters=None):
+    def __init__(self, network, lr=None, dist_ctx=None, opt=None, lr_scheduling='const', max_iters=None, *,
+                 mil_funcs=None):
         if opt not in self.OPTS:
             raise ValueError("opt=%r: one of %r" % (opt, self.OPTS))
         if lr_scheduling not in self.SCHEDULES:
             raise ValueError("lr_scheduling=%r: one of %r" % (lr_scheduling, self.SCHEDULES))
         if lr_scheduling == 'pc' and max_iters is None:
             raise ValueError("lr_scheduling='pc' needs max_iters")
+        self.mil_funcs = None if mil_funcs is None else mil_core.resolve_funcs(mil_funcs)
         self.net = network
         self.lr = cfg.TRAIN.get('LEARNING_RATE', 0.0005) if lr is None else lr
         self.opt, self.lr_scheduling, self.max_iters = opt, lr_scheduling, max_iters
@@ -343,7 +360,7 @@ class SolverWrapper(object):
                     cfg.TRAIN.IMS_PER_BATCH = n
                     layers = self.net(blobs['data'], blobs['im_info'], blobs['gt_boxes'], blobs['num_gt_boxes'],
                                       is_training=False, is_ws=False)
-                    v = validation_losses(layers, blobs['im_info'], n, self.global_step, alter)
+                    v = validation_losses(layers, blobs['im_info'], n, self.global_step, alter, self.mil_funcs)
                     chunks.append(torch.stack([v[name] for name in VAL_TERMS], dim=1))
                     if detect:
                         shapes = None
@@ -421,7 +438,7 @@ class SolverWrapper(object):
         cls_ws = layers['cls_score'][n_valid:]
         batch_inds = layers['roi-data'][0][n_valid:, 0] - n_s         # :653
         mil_label = blobs['im_info'][n_s:, 3].to(torch.int32)         # image-level labels, :654
-        funcs = [mil_core.get_mal_max_logit, mil_core.get_mal_max_logit]     # :655
+        funcs = self.mil_funcs or default_mil_funcs(False)            # :655
         losses['mil_cross_entropy'] = mil_loss(cls_ws, batch_inds, mil_label, n_ws,
                                                self.global_step, funcs)
         (losses['loss'] + losses['mil_cross_entropy']).backward()
@@ -447,7 +464,7 @@ class SolverWrapper(object):
                           blobs_ws['num_gt_boxes'], is_training=True, is_ws=True)
         batch_inds = layers['roi-data'][0][:, 0]                      # :239
         mil_label = blobs_ws['im_info'][:, 3].to(torch.int32)         # :240
-        funcs = [mil_core.get_mass_max_logit, mil_core.get_mal_max_logit]    # :241
+        funcs = self.mil_funcs or default_mil_funcs(True)             # :241
         mil = mil_loss(layers['cls_score'], batch_inds, mil_label, blobs_ws['data'].shape[0],
                        self.global_step, funcs)
         mil.backward()
@@ -504,7 +521,7 @@ def get_data_layer(roidbs, net_name, num_classes, is_training, is_ws=False, is_j
 def train_net(network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test, output_dir,
               pretrained_model=None, max_iters=80000, s_start_iter=0, s_end_iter=80000, ws_start_iter=0, ws_end_iter=80000,
               opt='adam', lr=5e-4, lr_scheduling='const', vis=False, *, resume=None, dist_ctx=None, val_ims_per_batch=1,
-              max_per_image=300, thresh=0.05):
+              max_per_image=300, thresh=0.05, mil_funcs=None):
     """Train a Faster R-CNN using combined mini-batches from supervised and weakly supervised sets (train_bus.py:1073-1087,
     without the TensorFlow session): SolverWrapper(network, lr, dist_ctx, opt, lr_scheduling, max_iters), then
     train_loop.train_model.  opt='adam' is the reference's TF-form Adam, as its command line has it (SolverWrapper's own
@@ -512,20 +529,21 @@ def train_net(network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_w
     file, loaded non-strictly before the first step, the missing names printed; the reference's .npy layout of
     TensorFlow variables is out of scope.  resume: a snapshot to continue from (fast_rcnn/snapshot.py).  vis: the
     validation pass's pictures go to <output_dir>/test (fast_rcnn/vis.py).  val_ims_per_batch: images per validation
-    forward.  Returns train_loop's history dict."""
+    forward.  mil_funcs: the MIL term's pair of bag functions or names (SolverWrapper; None: the reference's pair; not
+    stored in snapshots).  Returns train_loop's history dict."""
     from . import train_loop
     return train_loop._train(False, network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test,
                              output_dir, pretrained_model, max_iters, (s_start_iter, s_end_iter, ws_start_iter, ws_end_iter), opt, lr,
-                             lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh)
+                             lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh, mil_funcs)
 
 
 def train_net_alter(network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test, output_dir,
                     pretrained_model=None, max_iters=80000, s_start_iter=0, s_end_iter=80000, ws_start_iter=0, ws_end_iter=80000,
                     opt='adam', lr=5e-4, lr_scheduling='const', vis=False, *, resume=None, dist_ctx=None, val_ims_per_batch=1,
-                    max_per_image=300, thresh=0.05):
+                    max_per_image=300, thresh=0.05, mil_funcs=None):
     """Train a Faster R-CNN using alternating mini-batches each from supervised and weakly supervised sets
     (train_bus.py:1055-1069): as train_net, over train_loop.train_model_alter."""
     from . import train_loop
     return train_loop._train(True, network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test,
                              output_dir, pretrained_model, max_iters, (s_start_iter, s_end_iter, ws_start_iter, ws_end_iter), opt, lr,
-                             lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh)
+                             lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh, mil_funcs)

@@ -309,9 +309,10 @@ def train_model_alter(solver, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_
 
 
 def _train(alter, network, imdb_train_s, roidb_train_s, imdb_train_ws, roidb_train_ws, imdb_test, roidb_test, output_dir,
-           pretrained_model, max_iters, windows, opt, lr, lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh):
+           pretrained_model, max_iters, windows, opt, lr, lr_scheduling, vis, resume, dist_ctx, val_ims_per_batch, max_per_image, thresh,
+           mil_funcs=None):
     from .train_bus import SolverWrapper
-    solver = SolverWrapper(network, lr, dist_ctx, opt, lr_scheduling, max_iters)
+    solver = SolverWrapper(network, lr, dist_ctx, opt, lr_scheduling, max_iters, mil_funcs=mil_funcs)
     if pretrained_model is not None:
         snap.load_pretrained(network, pretrained_model)                              # before the first step (:308-311)
     print('Solving...')

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from ..fast_rcnn.config import cfg, cfg_from_list
+from ..mil.core import MIL_FUNCS, parse_funcs
 
 
 def train_parser(description, default_network):
@@ -26,6 +27,9 @@ def train_parser(description, default_network):
     p.add_argument('--opt', help='optimizer', default='adam', type=str)
     p.add_argument('--lr', help='initial learning rate', default=5e-04, type=float)
     p.add_argument('--lr_scheduling', help='how to change the learning rate during training', default='const', type=str)
+    p.add_argument('--mil_funcs', metavar='NAME,NAME', default=None, type=parse_funcs,
+                   help='bag functions of the MIL term: for bags labelled 1, for the others; each one of %s '
+                        '(default: the wiring\'s own pair)' % ', '.join(MIL_FUNCS))
     p.add_argument('--imdb_train_s', help='supervised training set', default='bus_test', type=str)
     p.add_argument('--imdb_train_ws', help='weakly supervised training set', default='bus_test', type=str)
     p.add_argument('--imdb_test', help='test set', default='bus_test', type=str)
@@ -70,4 +74,4 @@ def run_training(args, train_fn):
                     pretrained_model=args.pretrained_model, max_iters=args.max_iters, s_start_iter=args.s_start_iter,
                     s_end_iter=args.s_end_iter, ws_start_iter=args.ws_start_iter, ws_end_iter=args.ws_end_iter, opt=args.opt,
                     lr=args.lr, lr_scheduling=args.lr_scheduling, vis=args.qual_res_off, resume=args.resume,
-                    val_ims_per_batch=args.val_ims_per_batch)
+                    val_ims_per_batch=args.val_ims_per_batch, mil_funcs=args.mil_funcs)

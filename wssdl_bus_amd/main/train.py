@@ -4,8 +4,12 @@ from ..fast_rcnn.train_bus import train_net
 from ._common import run_training, train_parser
 
 
+def parser():
+    return train_parser('Train a Faster R-CNN network on combined mini-batches', 'Resnet_train')
+
+
 def main(argv=None):
-    args = train_parser('Train a Faster R-CNN network on combined mini-batches', 'Resnet_train').parse_args(argv)
+    args = parser().parse_args(argv)
     return run_training(args, train_net)
 
 
