@@ -459,6 +459,50 @@ WSSDL_API int wssdl_roi_argmax_expand(const uint8_t *argmax8, const float *rois,
                             int C, int pooled_h, int pooled_w, float spatial_scale, int rounding,
                             int32_t *argmax, wssdl_stream_t stream);
 
+/* ---------------------------------------------------------------- RoIAlign ---
+ * Not in the reference: bilinear sampling of the RoI bins, no rounding of the RoI or of the bin edges
+ * (cfg.ROI_POOL_MODE = 'align'; DESIGN.md "RoIAlign").  Layouts are the RoI-pool op's: bottom [N,H,W,C] f32, rois [R,5]
+ * f32 (batch index, x1, y1, x2, y2), top [R,pooled_h,pooled_w,C] f32.  sampling (S) in 1..4 samples per bin and axis,
+ * aligned in {0, 1} (the half-pixel offset), pooled_h / pooled_w in 1..16.
+ *
+ * All of a RoI's geometry lives in per-axis tables that wssdl_roi_align_tables writes and the other calls read.  One
+ * buffer of wssdl_roi_align_tables_bytes, nine arrays back to back, no padding, 4-byte elements:
+ *     ylo, yhi  i32 [R,pooled_h,S]     the two cells a sample reads along y
+ *     yh,  yl   f32 [R,pooled_h,S]     their weights (yh for ylo, yl for yhi)
+ *     xlo, xhi  i32 [R,pooled_w,S]     xh, xl  f32 [R,pooled_w,S]      the same along x
+ *     win       i32 [R,5]              (image, first row, last row, first column, last column) of the cells the RoI
+ *                                      reads; image = -1 for a dead row, first > last when every sample is void
+ * Per axis, with RoI coordinates a1, a2, map length L and P bins, in f32 and exactly this order:
+ *     off = aligned ? 0.5f : 0.0f;  s = a1*scale - off;  e = a2*scale - off;  len = e - s;
+ *     if (!aligned) len = max(len, 1.0f);  bin = len / (float)P;
+ *     y = (s + (float)p*bin) + (((float)i + 0.5f)*bin) / (float)S          for bin p, sample i
+ *     y < -1 or y > L: void (indices 0, weights 0).  Else y = max(y, 0); lo = (int)y; lo >= L-1: lo = hi = L-1,
+ *     y = (float)lo; else hi = lo+1.  l = y - (float)lo, h = 1.0f - l; the entry is (lo, hi, h, l).
+ * A row is dead -- all void, a zero top row, no gradient -- when its batch index is < 0 (the padded blob's rows) or
+ * >= N, or when any of its five numbers is not finite.  No kernel reads outside the map for any input.
+ *
+ * forward : top = sum over the S x S samples and their four cells of wy * wx * v, divided by S*S.
+ * backward: bottom_diff, written in full.  wssdl_roi_align_backward_prepare builds, per (image, 4 x 4 tile of cells), the
+ *           list of the RoIs whose window touches the tile, ascending; the backward is a gather: one wave owns a row of
+ *           four cells and a slice of channels, walks its tile's list and stores each cell once, summed over RoI, bin row,
+ *           bin column, all ascending.  No atomics: the same bits on every run.
+ * R = 0 is valid: nothing is launched by the forward, the backward fills bottom_diff with zeros.  Every call below
+ * clears the thread's last error on entry; an invalid argument sets it and returns WSSDL_ERR_INVALID_ARGUMENT, a buffer
+ * that is too small WSSDL_ERR_INVALID_ARGUMENT as well, before anything is launched. */
+WSSDL_API size_t wssdl_roi_align_tables_bytes(int R, int pooled_h, int pooled_w, int sampling);
+WSSDL_API int wssdl_roi_align_tables(const float *rois, int R, int N, int H, int W, int pooled_h, int pooled_w,
+                            float spatial_scale, int sampling, int aligned, void *tables, size_t tables_bytes,
+                            wssdl_stream_t stream);
+WSSDL_API int wssdl_roi_align_forward(const float *bottom, int N, int H, int W, int C, int R, int pooled_h, int pooled_w,
+                            int sampling, const void *tables, size_t tables_bytes, float *top, wssdl_stream_t stream);
+WSSDL_API size_t wssdl_roi_align_backward_workspace_bytes(int R, int N, int H, int W);
+WSSDL_API int wssdl_roi_align_backward_prepare(int R, int N, int H, int W, int pooled_h, int pooled_w, int sampling,
+                            const void *tables, size_t tables_bytes, void *workspace, size_t workspace_bytes,
+                            wssdl_stream_t stream);
+WSSDL_API int wssdl_roi_align_backward(const float *top_diff, int R, int N, int H, int W, int C, int pooled_h, int pooled_w,
+                            int sampling, const void *tables, size_t tables_bytes, const void *workspace,
+                            size_t workspace_bytes, float *bottom_diff, wssdl_stream_t stream);
+
 /* --------------------------------------------------------------------- a13 ---
  * Multi-task loss of the supervised images and its gradients: fast_rcnn/train_bus.py:186-192 /
  * :605-610 (rpn_cross_entropy), :203-210 / :613-620 (rpn_loss_box, threshold |d| < 1 with the

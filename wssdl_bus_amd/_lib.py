@@ -93,6 +93,12 @@ SYMBOLS = {
     "wssdl_roi_pool_backward_compact_owner_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _sz, _i, _i, _vp, _sz, _vp]),
     "wssdl_roi_pool_backward_owner_i32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "wssdl_roi_argmax_expand": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+    "wssdl_roi_align_tables_bytes": (_sz, [_i, _i, _i, _i]),
+    "wssdl_roi_align_tables": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
+    "wssdl_roi_align_forward": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "wssdl_roi_align_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wssdl_roi_align_backward_prepare": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "wssdl_roi_align_backward": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "wssdl_image_prep_workspace_bytes": (_sz, []),
     "wssdl_image_prep": (_i, [_vp, _i, _i, _i, _i, _i, _f, _i, _f, _d, _vp, _vp, _sz, _vp]),
     "wssdl_image_to_blob": (_i, [_vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _i, _vp]),

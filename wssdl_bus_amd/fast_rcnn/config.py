@@ -167,6 +167,14 @@ __C.ROI_POOL_BWD_EXACT = False
 # the first backward of each launch class (images x channels x form) prints the form it takes to stderr
 __C.ROI_POOL_ANNOUNCE_BWD_FORM = True
 __C.PADDED_ROIS = False
+# what the 'roi_pool' layer of both networks computes: 'max' = the reference's RoI max pooling (everything above), 'align'
+# = RoIAlign (roi_pooling_layer/roi_align_op.py: bilinear sampling, no rounding of the RoI or of its bin edges; not in the
+# reference).  Anything else raises ValueError where the layer reads it.  ROI_ALIGN_SAMPLING = samples per bin and axis
+# (1..4; the adaptive setting 0 is not supported), ROI_ALIGN_ALIGNED = the half-pixel offset.  A snapshot records the
+# three values and refuses to resume under different ones.
+__C.ROI_POOL_MODE = 'max'
+__C.ROI_ALIGN_SAMPLING = 2
+__C.ROI_ALIGN_ALIGNED = True
 # a13: the four supervised loss terms and their gradients as one device op (csrc/loss.hip) when the
 # layers are on the GPU; False = the chain of torch ops in fast_rcnn/train_bus.py
 __C.FUSED_LOSS = True

@@ -9,6 +9,9 @@ One file (torch.save) holds everything the next iteration reads:
   optimizer, optimizer_ws       both optimisers' state_dict() (optimizer_ws: None until the first alternating iteration)
   global_step                   the solver's step count (MIL scale factor, 'pc' schedule)
   opt, lr, lr_scheduling, max_iters    the solver's settings; a mismatch at restore raises ValueError
+  roi_pool                      cfg.ROI_POOL_MODE, ROI_ALIGN_SAMPLING, ROI_ALIGN_ALIGNED as dict(mode, sampling, aligned): the
+                                head was trained on that pooling, so a mismatch at restore raises ValueError; a file without
+                                the key was written under 'max'
   rop                           the plateau handler's state (cur_lr, best, wait, cooldown_counter) or None
   loop                          the training loop's own state: iteration, running loss sums, the previous interval's
                                 means (the alternating loop's stand-ins), ...
@@ -26,6 +29,7 @@ import os
 import numpy as np
 import torch
 
+from ..roi_pooling_layer import roi_align_op
 from ..rpn_msr import anchor_target_layer_tf_bus, proposal_target_layer_tf_bus
 from .config import cfg
 
@@ -75,7 +79,8 @@ def save_snapshot(solver, output_dir, net_name, iteration, loop_state=None, data
     path = snapshot_path(output_dir, net_name, iteration)
     state = solver_state(solver)
     state.update(format=FORMAT, iteration=int(iteration), net_name=net_name, loop=dict(loop_state or {}),
-                 data_layers={k: v.state_dict() for k, v in (data_layers or {}).items()}, rng=rng_state())
+                 data_layers={k: v.state_dict() for k, v in (data_layers or {}).items()}, rng=rng_state(),
+                 roi_pool=roi_align_op.settings())
     os.makedirs(output_dir, exist_ok=True)
     tmp = "%s.%d.tmp" % (path, os.getpid())
     try:
@@ -115,6 +120,13 @@ def restore(path, solver, data_layers=None, rank_local=True):
         if state[key] != getattr(solver, key):
             raise ValueError("resume: the snapshot was written with %s=%r, this run has %s=%r"
                              % (key, state[key], key, getattr(solver, key)))
+    saved, now = state.get('roi_pool') or dict(mode='max'), roi_align_op.settings()
+    # (the two RoIAlign values only matter to a head that was trained on RoIAlign)
+    keys = ('mode', 'sampling', 'aligned') if saved['mode'] == 'align' else ('mode',)
+    for key in keys:
+        if saved[key] != now[key]:
+            raise ValueError("resume: the snapshot was written with RoI pooling %s=%r, this run has %s=%r"
+                             % (key, saved[key], key, now[key]))
     solver.net.load_state_dict(state['model'])
     solver.optimizer.load_state_dict(state['optimizer'])
     if state['optimizer_ws'] is not None:

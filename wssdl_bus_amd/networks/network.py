@@ -8,6 +8,7 @@ kernels on the current stream.  All tensors are NHWC like the reference's.
 """
 import torch
 
+from ..roi_pooling_layer import roi_align_op
 from ..roi_pooling_layer import roi_pooling_op as roi_pool_op
 from ..rpn_msr.anchor_target_layer_tf_bus import (anchor_target_layer as anchor_target_layer_py,
                                                   anchor_target_layer_joint as anchor_target_layer_joint_py,
@@ -88,10 +89,20 @@ class Network(object):
     @layer
     def roi_pool(self, input, pooled_height, pooled_width, spatial_scale, name):
         """network.py:196-210: returns top_data only (element [0] of the op's outputs);
-        differentiable w.r.t. the feature map."""
+        differentiable w.r.t. the feature map.  cfg.ROI_POOL_MODE = 'align': the layer computes RoIAlign instead, read
+        at every call, so both networks' train and test wiring switch with the one key."""
         data, rois = _first(input[0]), _first(input[1])
+        if roi_align_op.pool_mode() == 'align':
+            return roi_align_op.roi_align_autograd(data, rois, pooled_height, pooled_width, spatial_scale)
         return roi_pool_op.roi_pool_autograd(data, rois, pooled_height, pooled_width,
                                              spatial_scale, return_argmax=False)[0]
+
+    @layer
+    def roi_align(self, input, pooled_height, pooled_width, spatial_scale, name, sampling_ratio=None, aligned=None):
+        """RoIAlign whatever cfg.ROI_POOL_MODE says (sampling_ratio / aligned: cfg.ROI_ALIGN_* unless given)."""
+        data, rois = _first(input[0]), _first(input[1])
+        return roi_align_op.roi_align_autograd(data, rois, pooled_height, pooled_width, spatial_scale,
+                                               sampling_ratio, aligned)
 
     @layer
     def proposal_layer(self, input, _feat_stride, anchor_scales, is_training, is_ws, name):
