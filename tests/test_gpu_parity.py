@@ -510,11 +510,20 @@ def test_proposal_layer_golden(torch_cuda, case):
     anchors = O.shifted_anchors(H, W, 16, O.generate_anchors(scales=SCALES))
     blob = proposal_layer(prob, pred, info, train, False, STRIDE, SCALES)
     assert blob.dtype == np.float32 and blob.shape[1] == 5
+    # the statement of the decode kernel's arithmetic (tests/boxcode_reference.py): bit for bit, under the precondition
+    # that no exp lies within 4 f64 ulps of an f32 rounding boundary
+    import boxcode_reference as B
+    assert bool(B.exp_is_safe(pred.reshape(-1, 4)[:, 2:4]).all())
+    stated = B.proposal_statement(prob, pred, info)
+    stated_order = B.candidate_order(stated["scores"], stated["valid"], pre)
     off = 0
     for i in range(N):
         st = O.proposal_stages_one_image(prob[i], pred[i], info[i], anchors, 9, pre, post, 0.7, 16)
         # a6: decoded + clipped boxes: exp-limited tolerance (np.exp is ~2.5 ulp accurate)
         assert np.allclose(dec[i], st["decoded"], rtol=2e-6, atol=2e-4)
+        # ... and the statement, bit for bit; its candidate order exactly
+        assert np.array_equal(dec[i].view(np.int32), stated["boxes"][i].view(np.int32))
+        assert np.array_equal(sidx[i, :int(scnt[i])], stated_order[i])
         # a7: identical candidate order (scores are pairwise distinct by construction)
         n = int(scnt[i])
         assert n == len(st["order"])
