@@ -21,7 +21,8 @@
 //   anchor_targets : final labels -> rpn_labels [n,1,A*H,W] and the three
 //                    [n,4A,H,W] blobs; lanes run along W so all 13 output planes
 //                    are written with coalesced stores (13*A*K*4 B per image).
-#include "common.hip.h"
+#include "box_code.hip.h"
+#include "box_iou.hip.h"
 #include "select.hip.h"
 
 namespace wssdl {
@@ -44,7 +45,7 @@ __device__ __forceinline__ void load_gt(GtShared &s, const float *__restrict__ g
     if (t < ng) {
         double x1 = g[t * 5 + 0], y1 = g[t * 5 + 1], x2 = g[t * 5 + 2], y2 = g[t * 5 + 3];
         s.x1[t] = x1; s.y1[t] = y1; s.x2[t] = x2; s.y2[t] = y2;
-        s.area[t] = (x2 - x1 + 1) * (y2 - y1 + 1);
+        s.area[t] = box_area_f64(x1, y1, x2, y2);
     }
     if (t == 0) {
         int np = 0;
@@ -72,26 +73,14 @@ __device__ __forceinline__ AnchorBox make_anchor(const BaseAnchors &base, int a,
     return b;
 }
 
+// anchor against gt box k of the image: box_iou.hip.h's pair arithmetic
 __device__ __forceinline__ double iou_f64(const AnchorBox &b, const GtShared &s, int k) {
-    double iw = fmin(b.x2, s.x2[k]) - fmax(b.x1, s.x1[k]) + 1;
-    if (iw > 0) {
-        double ih = fmin(b.y2, s.y2[k]) - fmax(b.y1, s.y1[k]) + 1;
-        if (ih > 0) {
-            double ua = (b.x2 - b.x1 + 1) * (b.y2 - b.y1 + 1) + s.area[k] - iw * ih;
-            return iw * ih / ua;
-        }
-    }
-    return 0.0;
+    return iou_pair(b.x1, b.y1, b.x2, b.y2, s.x1[k], s.y1[k], s.x2[k], s.y2[k], s.area[k]);
 }
 
 __device__ __forceinline__ double ui_f64(const AnchorBox &b, double barea, const GtShared &s,
                                          int k) {
-    double iw = fmin(b.x2, s.x2[k]) - fmax(b.x1, s.x1[k]) + 1;
-    if (iw > 0) {
-        double ih = fmin(b.y2, s.y2[k]) - fmax(b.y1, s.y1[k]) + 1;
-        if (ih > 0) return iw * ih / barea;
-    }
-    return 0.0;
+    return ui_pair(b.x1, b.y1, b.x2, b.y2, barea, s.x1[k], s.y1[k], s.x2[k], s.y2[k]);
 }
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(AT_BLOCK) void anchor_label_kernel(
             }
             if (dataset == WSSDL_DATASET_SNUBH) {
                 if (s.n_ui > 0 && !clobber) {
-                    const double barea = (b.x2 - b.x1 + 1) * (b.y2 - b.y1 + 1);
+                    const double barea = box_area_f64(b.x1, b.y1, b.x2, b.y2);
                     double mu = 0.0;
                     for (int k = 0; k < s.n_ui; ++k) {
                         double u = ui_f64(b, barea, s, s.n_ov + k);
@@ -354,24 +343,15 @@ __global__ __launch_bounds__(AT_BLOCK) void anchor_targets_kernel(
     const int l = lab[i];
     const int k = argmax_gt[(size_t)img * total + i];
     lab_o[e] = (float)l;                            // [1, A*H, W] at (a*H + h, w), :278-279
-    float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float4v t = {0.0f, 0.0f, 0.0f, 0.0f};
     if (k >= 0) {                                   // inside anchors only (_unmap fill 0, :259-262)
         const double ax1 = base.v[a][0] + (double)(stride * w);
         const double ay1 = base.v[a][1] + (double)(stride * h);
         const double ax2 = base.v[a][2] + (double)(stride * w);
         const double ay2 = base.v[a][3] + (double)(stride * h);
-        const double ew = ax2 - ax1 + 1.0, eh = ay2 - ay1 + 1.0;
-        const double ecx = ax1 + 0.5 * ew, ecy = ay1 + 0.5 * eh;
-        // gt side stays f32 until it meets the f64 anchors (bbox_transform.py:16-19)
+        // f64 anchors against the f32 gt box (box_code.hip.h)
         const float *g = gt_boxes + ((size_t)img * max_gt + k) * 5;
-        float gw = g[2] - g[0];  gw = gw + 1.0f;
-        float gh = g[3] - g[1];  gh = gh + 1.0f;
-        float hgw = 0.5f * gw, hgh = 0.5f * gh;
-        const float gcx = g[0] + hgw, gcy = g[1] + hgh;
-        t[0] = (float)(((double)gcx - ecx) / ew);
-        t[1] = (float)(((double)gcy - ecy) / eh);
-        t[2] = (float)log((double)gw / ew);
-        t[3] = (float)log((double)gh / eh);
+        t = encode_box<double>(ax1, ay1, ax2, ay2, g[0], g[1], g[2], g[3]);
     }
     const float iw[4] = {iw0, iw1, iw2, iw3};
     const float ow = (l == 1) ? pos_w : ((l == 0) ? neg_w : 0.0f);

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const double *__rest
     if (n < N) {
         const double *b = boxes + n * bstride;
         bx1 = b[0]; by1 = b[1]; bx2 = b[2]; by2 = b[3];
-        barea = (bx2 - bx1 + 1) * (by2 - by1 + 1);
+        barea = box_area_f64(bx1, by1, bx2, by2);
     }
     for (long long k0 = 0; k0 < K; k0 += QTILE) {
         int kt = (int)((K - k0 < QTILE) ? (K - k0) : QTILE);
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const double *__rest
         for (int i = threadIdx.x; i < kt; i += blockDim.x) {
             const double *qq = query + (k0 + i) * qstride;
             q[i][0] = qq[0]; q[i][1] = qq[1]; q[i][2] = qq[2]; q[i][3] = qq[3];
-            q[i][4] = (qq[2] - qq[0] + 1) * (qq[3] - qq[1] + 1);
+            q[i][4] = box_area_f64(qq[0], qq[1], qq[2], qq[3]);
         }
         __syncthreads();
         if (n < N) {

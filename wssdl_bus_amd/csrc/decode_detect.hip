@@ -12,14 +12,12 @@
 //
 // All arithmetic is f32 in NumPy's operation order, every operation rounded on its own (-ffp-contract=off): a true
 // IEEE division by the scale (the reference divides; PyTorch's GPU division by a scalar multiplies by a reciprocal),
-// separate multiply and add, and exp evaluated in f64 and rounded once to f32 as in proposal.hip's decode.  That
-// makes the output derivable bit for bit from the inputs (tests/decode_reference.py) wherever the f64 exp is not
+// separate multiply and add, and exp evaluated in f64 and rounded once to f32 -- the decode and the clip are
+// box_code.hip.h's, the proposal layer's own.  That makes the output derivable bit for bit from the inputs (tests/decode_reference.py) wherever the f64 exp is not
 // within a few ulps of an f32 rounding boundary.
-#include "common.hip.h"
+#include "box_code.hip.h"
 
 namespace wssdl {
-
-typedef float decode_float4v __attribute__((ext_vector_type(4)));
 
 constexpr int DECODE_BLOCK = 256;
 constexpr int DECODE_MAX_BLOCKS = 1024;        // 4 blocks per CU; beyond that the lanes stride
@@ -33,7 +31,7 @@ __global__ __launch_bounds__(DECODE_BLOCK) void decode_detections_kernel(
         const long long r = p / K;
         const float *roi = rois + (size_t)r * 5;
         const float fi = roi[0];
-        decode_float4v out = {0.0f, 0.0f, 0.0f, 0.0f};
+        float4v out = {0.0f, 0.0f, 0.0f, 0.0f};
         // (int)fi in [0, n_images), tested before the conversion: NaN and values no int holds are dead rows too
         if ((double)fi > -1.0 && (double)fi < (double)n_images) {
             const int i = (int)fi;
@@ -48,24 +46,11 @@ __global__ __launch_bounds__(DECODE_BLOCK) void decode_detections_kernel(
                 xmax = (float)((double)info[1] / (double)s - 1.0);
                 ymax = (float)((double)info[0] / (double)s - 1.0);
             }
-            const decode_float4v d = *reinterpret_cast<const decode_float4v *>(deltas + (size_t)p * 4);
-            // bbox_transform_inv (bbox_transform.py:30-61)
-            float w = bx2 - bx1;  w = w + 1.0f;
-            float h = by2 - by1;  h = h + 1.0f;
-            const float hx = 0.5f * w, hy = 0.5f * h;
-            const float cx = bx1 + hx, cy = by1 + hy;
-            float pcx = d.x * w;  pcx = pcx + cx;
-            float pcy = d.y * h;  pcy = pcy + cy;
-            const float pw = (float)exp((double)d.z) * w;
-            const float ph = (float)exp((double)d.w) * h;
-            const float hpw = 0.5f * pw, hph = 0.5f * ph;
-            // clip_boxes (bbox_transform.py:63-77): max(min(v, im - 1), 0)
-            out.x = fmaxf(fminf(pcx - hpw, xmax), 0.0f);
-            out.y = fmaxf(fminf(pcy - hph, ymax), 0.0f);
-            out.z = fmaxf(fminf(pcx + hpw, xmax), 0.0f);
-            out.w = fmaxf(fminf(pcy + hph, ymax), 0.0f);
+            const float4v d = *reinterpret_cast<const float4v *>(deltas + (size_t)p * 4);
+            // bbox_transform_inv + clip_boxes (box_code.hip.h)
+            out = clip_box_f32(decode_box_f32(bx1, by1, bx2, by2, d), xmax, ymax);
         }
-        *reinterpret_cast<decode_float4v *>(boxes + (size_t)p * 4) = out;
+        *reinterpret_cast<float4v *>(boxes + (size_t)p * 4) = out;
     }
 }
 

@@ -19,20 +19,9 @@
 // weak scalars), f64 for the mean / std steps, each rounded to f32 once.  The contrast step needs
 // the image mean: NumPy sums f32 pairwise; here the sum is exact-ish (f64, fixed order), so the
 // mean -- and with it the output -- can differ from NumPy's in the last bit (tests: 2e-7 abs).
-#include "common.hip.h"
+#include "image_math.hip.h"
 
 namespace wssdl {
-
-constexpr int IMG_PARTS = 256;      // partial sums of the mean
-
-__device__ __forceinline__ float prep_value(unsigned char u, int use_b, float delta) {
-    float v = (float)u / 255.0f;
-    if (use_b) {
-        v = v + delta;
-        v = fminf(fmaxf(v, 0.0f), 1.0f);
-    }
-    return v;
-}
 
 // partial f64 sums of the brightened plane: block b sums pixels b, b + IMG_PARTS*256, ... (fixed order)
 __global__ __launch_bounds__(256) void image_sum_kernel(const unsigned char *__restrict__ gray, int h, int w,
@@ -47,10 +36,7 @@ __global__ __launch_bounds__(256) void image_sum_kernel(const unsigned char *__r
     }
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
-        __syncthreads();
-    }
+    tree_sum256(s);
     if (threadIdx.x == 0) parts[blockIdx.x] = s[0];
 }
 
@@ -63,24 +49,14 @@ __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char *__
     if (use_c) {                       // every block re-reduces the partial sums in the same order
         s[threadIdx.x] = threadIdx.x < IMG_PARTS ? parts[threadIdx.x] : 0.0;
         __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
-            __syncthreads();
-        }
+        tree_sum256(s);
         mm = (float)(s[0] / (double)((long long)h * w));
     }
     const long long n = (long long)h * w;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int y = (int)(i / w), x = (int)(i - (long long)y * w);
         const int sx = flipped ? w - 1 - x : x;                 // im[:, ::-1, :]
-        float v = prep_value(gray[(size_t)y * row_stride + sx], use_b, delta);
-        if (use_c) {
-            v = v - mm;
-            v = v * factor;
-            v = v + mm;
-            v = fminf(fmaxf(v, 0.0f), 1.0f);
-        }
-        const float o = (float)((double)v - mean_sub);          // im -= pixel_means / 255.
+        const float o = prep_pixel(gray[(size_t)y * row_stride + sx], use_b, delta, use_c, factor, mm, mean_sub);
         float *p = out + (size_t)i * 3;
         p[0] = o;  p[1] = o;  p[2] = o;
     }
@@ -89,14 +65,6 @@ __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char *__
 // ---- blob.py:49-60 on the float64 image skimage.transform.rotate returns (weak images, :39-41): the
 // same steps as above, all in f64 (NumPy: a float64 array and Python-float scalars).  The input is a
 // strided view [h, w, C] (the crop :43-47 is a slice), elements (y, x, ch) at im[y*row_stride + x*C + ch].
-__device__ __forceinline__ double adjust_value(double v, int use_b, double delta) {
-    if (use_b) {
-        v = v + delta;
-        v = fmin(fmax(v, 0.0), 1.0);
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void image_sum_f64_kernel(const double *__restrict__ im, int h, int wc,
                                                             long long row_stride, int use_b, double delta,
                                                             double *__restrict__ parts) {
@@ -109,10 +77,7 @@ __global__ __launch_bounds__(256) void image_sum_f64_kernel(const double *__rest
     }
     s[threadIdx.x] = acc;
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
-        __syncthreads();
-    }
+    tree_sum256(s);
     if (threadIdx.x == 0) parts[blockIdx.x] = s[0];
 }
 
@@ -126,23 +91,13 @@ __global__ __launch_bounds__(256) void image_adjust_f64_kernel(const double *__r
     if (use_c) {
         s[threadIdx.x] = threadIdx.x < IMG_PARTS ? parts[threadIdx.x] : 0.0;
         __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
-            __syncthreads();
-        }
+        tree_sum256(s);
         mm = s[0] / (double)((long long)h * wc);
     }
     const long long n = (long long)h * wc;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int y = (int)(i / wc), x = (int)(i - (long long)y * wc);
-        double v = adjust_value(im[(size_t)y * row_stride + x], use_b, delta);
-        if (use_c) {
-            v = v - mm;
-            v = v * factor;
-            v = v + mm;
-            v = fmin(fmax(v, 0.0), 1.0);
-        }
-        out[i] = v - mean_sub;
+        out[i] = adjust_pixel(im[(size_t)y * row_stride + x], use_b, delta, use_c, factor, mm, mean_sub);
     }
 }
 
@@ -166,31 +121,24 @@ __global__ __launch_bounds__(256) void image_to_blob_kernel(const T *__restrict_
 
 // ---- skimage.transform.warp, order 1 (skimage/transform/_warps_cy.pyx `_warp_fast`, interpolation.pxd
 // `bilinear_interpolation` / `get_pixel2d`, _warps.py `_clip_warp_output`) -------------------------------
-constexpr int WARP_PARTS = 256;
 struct WarpMatrix { double m[9]; };
 
 // partial min / max of the input in f64 (np.min / np.max of the whole array, all channels): block b covers
-// elements b*256 + t, stride WARP_PARTS*256
+// elements b*256 + t, stride IMG_PARTS*256
 template <typename T>
 __global__ __launch_bounds__(256) void image_minmax_kernel(const T *__restrict__ im, long long n,
                                                            double *__restrict__ parts) {
     __shared__ double lo_s[256], hi_s[256];
     double lo = INFINITY, hi = -INFINITY;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)WARP_PARTS * 256) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)IMG_PARTS * 256) {
         const double v = (double)im[i];
         lo = fmin(lo, v);
         hi = fmax(hi, v);
     }
     lo_s[threadIdx.x] = lo;  hi_s[threadIdx.x] = hi;
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            lo_s[threadIdx.x] = fmin(lo_s[threadIdx.x], lo_s[threadIdx.x + st]);
-            hi_s[threadIdx.x] = fmax(hi_s[threadIdx.x], hi_s[threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { parts[blockIdx.x] = lo_s[0];  parts[WARP_PARTS + blockIdx.x] = hi_s[0]; }
+    tree_minmax256(lo_s, hi_s);
+    if (threadIdx.x == 0) { parts[blockIdx.x] = lo_s[0];  parts[IMG_PARTS + blockIdx.x] = hi_s[0]; }
 }
 
 template <typename T>
@@ -215,15 +163,9 @@ __global__ __launch_bounds__(256) void image_warp_kernel(const T *__restrict__ i
     bool keep_cval = false;
     if (clip) {                                                 // every block re-reduces the partials
         lo_s[threadIdx.x] = parts[threadIdx.x];
-        hi_s[threadIdx.x] = parts[WARP_PARTS + threadIdx.x];
+        hi_s[threadIdx.x] = parts[IMG_PARTS + threadIdx.x];
         __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) {
-                lo_s[threadIdx.x] = fmin(lo_s[threadIdx.x], lo_s[threadIdx.x + st]);
-                hi_s[threadIdx.x] = fmax(hi_s[threadIdx.x], hi_s[threadIdx.x + st]);
-            }
-            __syncthreads();
-        }
+        tree_minmax256(lo_s, hi_s);
         lo = lo_s[0];  hi = hi_s[0];
         keep_cval = mode == WSSDL_WARP_CONSTANT && !(lo <= cval && cval <= hi);
     }
@@ -235,21 +177,13 @@ __global__ __launch_bounds__(256) void image_warp_kernel(const T *__restrict__ i
         double xx = M.m[0] * x;  xx = xx + M.m[1] * y;  xx = xx + M.m[2];
         double yy = M.m[3] * x;  yy = yy + M.m[4] * y;  yy = yy + M.m[5];
         double zz = M.m[6] * x;  zz = zz + M.m[7] * y;  zz = zz + M.m[8];
-        const double c = xx / zz, r = yy / zz;
-        const double fr = floor(r), fc = floor(c);
-        // (a coordinate far outside any image: every neighbour is outside, clamp before the integer cast)
-        const double big = 4.0e9;
-        const long long minr = (long long)fmax(fmin(fr, big), -big), minc = (long long)fmax(fmin(fc, big), -big);
-        const long long maxr = (long long)fmax(fmin(ceil(r), big), -big), maxc = (long long)fmax(fmin(ceil(c), big), -big);
-        const double dr = r - fr, dc = c - fc;
+        const Cell q = warp_cell(xx / zz, yy / zz);
         for (int ch = 0; ch < C; ++ch) {
-            const double p00 = warp_pixel(im, h, w, C, ch, minr, minc, mode, cval);
-            const double p01 = warp_pixel(im, h, w, C, ch, minr, maxc, mode, cval);
-            const double p10 = warp_pixel(im, h, w, C, ch, maxr, minc, mode, cval);
-            const double p11 = warp_pixel(im, h, w, C, ch, maxr, maxc, mode, cval);
-            double top = (1.0 - dc) * p00;  top = top + dc * p01;
-            double bot = (1.0 - dc) * p10;  bot = bot + dc * p11;
-            double v = (1.0 - dr) * top;  v = v + dr * bot;
+            const double p00 = warp_pixel(im, h, w, C, ch, q.minr, q.minc, mode, cval);
+            const double p01 = warp_pixel(im, h, w, C, ch, q.minr, q.maxc, mode, cval);
+            const double p10 = warp_pixel(im, h, w, C, ch, q.maxr, q.minc, mode, cval);
+            const double p11 = warp_pixel(im, h, w, C, ch, q.maxr, q.maxc, mode, cval);
+            double v = warp_mix(q, p00, p01, p10, p11);
             if (clip && !(keep_cval && v == cval)) v = fmin(fmax(v, lo), hi);      // np.clip; cval pixels kept
             out[(size_t)i * C + ch] = v;
         }
@@ -329,13 +263,13 @@ extern "C" int wssdl_image_to_blob(const void *im, int im_is_f64, int h, int w, 
     return check_launch();
 }
 
-extern "C" size_t wssdl_image_warp_workspace_bytes(void) { return 2 * WARP_PARTS * sizeof(double); }
+extern "C" size_t wssdl_image_warp_workspace_bytes(void) { return 2 * IMG_PARTS * sizeof(double); }
 
 template <typename T>
 static int launch_warp(const T *im, int h, int w, int C, const WarpMatrix &M, int rows, int cols, int mode, double cval,
                        int clip, double *out, double *parts, hipStream_t st) {
     if (clip)
-        hipLaunchKernelGGL(image_minmax_kernel<T>, dim3(WARP_PARTS), dim3(256), 0, st, im, (long long)h * w * C, parts);
+        hipLaunchKernelGGL(image_minmax_kernel<T>, dim3(IMG_PARTS), dim3(256), 0, st, im, (long long)h * w * C, parts);
     const long long n = (long long)rows * cols;
     const int blocks = (int)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
     hipLaunchKernelGGL(image_warp_kernel<T>, dim3(blocks), dim3(256), 0, st, im, h, w, C, M, rows, cols, mode, cval, clip,

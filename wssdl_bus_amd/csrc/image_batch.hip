@@ -10,23 +10,24 @@
 //                                    table of the whole pre-resize map, built per block in LDS) or from the rotated
 //                                    plane, scale, 12 B per pixel staged in LDS and streamed out element-contiguous,
 //                                    zero padding included
-// and the result is bit for bit image.hip's: the same operations in the same order (-ffp-contract=off).
-//   * The mean's reduction order is image.hip's: 256 partials, block b takes elements b*256 + t with stride 65536,
-//     then the LDS tree; blockIdx.x plays the part of the single-image launch's block index.  For a rotated item the
+// and the result is bit for bit image.hip's: both take the value maps, the bilinear cell and the reduction trees from
+// image_math.hip.h (-ffp-contract=off).
+//   * The mean's reduction order is image.hip's: IMG_PARTS partials, block b takes elements b*256 + t with stride
+//     65536, then the LDS tree; blockIdx.x plays the part of the single-image launch's block index.  For a rotated item the
 //     index space is h' * w' * 3 with the channel innermost, as wssdl_image_adjust_f64 sees it.
 //   * min / max are exact in any order.  The clip range of a warp is the min / max of its input; every step from the
 //     u8 value (or from the rotated value) to the resize's input is monotone -- /255, +delta, clip, -mean, *factor
 //     (non-increasing for a factor < 0), +mean, clip, -pixel_mean/255, each rounding included -- so the extremes of the
 //     resize's input are the images of the extremes of the plane, whichever way round.
-//   * Every gather is bounded: a tap outside the view takes cval (warp_pixel of image.hip, mode 'constant').
-#include "common.hip.h"
+//   * Every gather is bounded: a tap outside the view takes cval (get_pixel2d, mode 'constant'; the taps here read
+//     u8 or the rotated plane, so they are not image.hip's warp_pixel).
+#include "image_math.hip.h"
 
 namespace wssdl {
 
-constexpr int IB_PARTS = 256;                   // = IMG_PARTS = WARP_PARTS of image.hip
 constexpr int IB_CHUNK_PIXELS = 86;            // pixels that 256 consecutive channel-innermost elements can touch
-constexpr size_t IB_STATS1 = IB_PARTS * (sizeof(double) + 2 * sizeof(int));      // per image: sums, (min, max) u8
-constexpr size_t IB_STATS2 = IB_PARTS * 3 * sizeof(double);                      // per image: sums, min, max f64
+constexpr size_t IB_STATS1 = IMG_PARTS * (sizeof(double) + 2 * sizeof(int));      // per image: sums, (min, max) u8
+constexpr size_t IB_STATS2 = IMG_PARTS * 3 * sizeof(double);                      // per image: sums, min, max f64
 
 typedef wssdl_image_batch_item Item;
 
@@ -44,69 +45,15 @@ __device__ __forceinline__ View crop_view(const unsigned char *arena, const Item
     return v;
 }
 
-__device__ __forceinline__ float ib_prep_value(unsigned char u, int use_b, float delta) {
-    float v = (float)u / 255.0f;
-    if (use_b) {
-        v = v + delta;
-        v = fminf(fmaxf(v, 0.0f), 1.0f);
-    }
-    return v;
-}
-
 // image_prep_kernel's map of one u8 value, as the double the resize reads
-__device__ __forceinline__ double ib_pre_u8(int u, const Item &it, float mm, double mean_sub) {
-    float v = ib_prep_value((unsigned char)u, it.use_brightness, (float)it.brightness_delta);
-    if (it.use_contrast) {
-        const float factor = (float)it.contrast_factor;
-        v = v - mm;
-        v = v * factor;
-        v = v + mm;
-        v = fminf(fmaxf(v, 0.0f), 1.0f);
-    }
-    return (double)(float)((double)v - mean_sub);
-}
-
-__device__ __forceinline__ double ib_adjust_value(double v, int use_b, double delta) {
-    if (use_b) {
-        v = v + delta;
-        v = fmin(fmax(v, 0.0), 1.0);
-    }
-    return v;
+__device__ __forceinline__ double pre_u8(int u, const Item &it, float mm, double mean_sub) {
+    return (double)prep_pixel((unsigned char)u, it.use_brightness, (float)it.brightness_delta, it.use_contrast,
+                              (float)it.contrast_factor, mm, mean_sub);
 }
 
 // image_adjust_f64_kernel's map of one rotated value
-__device__ __forceinline__ double ib_pre_f64(double v, const Item &it, double mm, double mean_sub) {
-    v = ib_adjust_value(v, it.use_brightness, it.brightness_delta);
-    if (it.use_contrast) {
-        v = v - mm;
-        v = v * it.contrast_factor;
-        v = v + mm;
-        v = fmin(fmax(v, 0.0), 1.0);
-    }
-    return v - mean_sub;
-}
-
-// image_warp_kernel's bilinear cell of the input coordinate (c, r): the four neighbours and the two weights
-struct Cell { long long minr, minc, maxr, maxc; double dr, dc; };
-
-__device__ __forceinline__ Cell warp_cell(double c, double r) {
-    Cell q;
-    const double fr = floor(r), fc = floor(c);
-    const double big = 4.0e9;
-    q.minr = (long long)fmax(fmin(fr, big), -big);
-    q.minc = (long long)fmax(fmin(fc, big), -big);
-    q.maxr = (long long)fmax(fmin(ceil(r), big), -big);
-    q.maxc = (long long)fmax(fmin(ceil(c), big), -big);
-    q.dr = r - fr;
-    q.dc = c - fc;
-    return q;
-}
-
-__device__ __forceinline__ double warp_mix(const Cell &q, double p00, double p01, double p10, double p11) {
-    double top = (1.0 - q.dc) * p00;  top = top + q.dc * p01;
-    double bot = (1.0 - q.dc) * p10;  bot = bot + q.dc * p11;
-    double v = (1.0 - q.dr) * top;  v = v + q.dr * bot;
-    return v;
+__device__ __forceinline__ double pre_f64(double v, const Item &it, double mm, double mean_sub) {
+    return adjust_pixel(v, it.use_brightness, it.brightness_delta, it.use_contrast, it.contrast_factor, mm, mean_sub);
 }
 
 // ---- pass 1 ------------------------------------------------------------------------------------------------------
@@ -122,25 +69,18 @@ __global__ __launch_bounds__(256) void image_batch_stats_kernel(const unsigned c
     const long long n = (long long)v.h * v.w;
     double acc = 0.0;
     int lo = 255, hi = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)IB_PARTS * 256) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)IMG_PARTS * 256) {
         const int y = (int)(i / v.w), x = (int)(i - (long long)y * v.w);
         const unsigned char u = v.p[(size_t)y * it.row_stride + x];
-        acc += (double)ib_prep_value(u, use_b, delta);
+        acc += (double)prep_value(u, use_b, delta);
         lo = min(lo, (int)u);
         hi = max(hi, (int)u);
     }
     s[threadIdx.x] = acc;  lo_s[threadIdx.x] = lo;  hi_s[threadIdx.x] = hi;
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            s[threadIdx.x] += s[threadIdx.x + st];
-            lo_s[threadIdx.x] = min(lo_s[threadIdx.x], lo_s[threadIdx.x + st]);
-            hi_s[threadIdx.x] = max(hi_s[threadIdx.x], hi_s[threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
+    tree_sum_minmax256(s, lo_s, hi_s);
     if (threadIdx.x == 0) {
-        const size_t k = (size_t)blockIdx.y * IB_PARTS + blockIdx.x;
+        const size_t k = (size_t)blockIdx.y * IMG_PARTS + blockIdx.x;
         sums[k] = s[0];
         ext[2 * k] = lo_s[0];
         ext[2 * k + 1] = hi_s[0];
@@ -149,17 +89,11 @@ __global__ __launch_bounds__(256) void image_batch_stats_kernel(const unsigned c
 
 // the u8 extremes of image `img` from pass 1's partials (every thread gets them)
 __device__ __forceinline__ void reduce_ext(const int *__restrict__ ext, int img, int *lo_s, int *hi_s, int &lo, int &hi) {
-    const size_t k = (size_t)img * IB_PARTS + threadIdx.x;
+    const size_t k = (size_t)img * IMG_PARTS + threadIdx.x;
     lo_s[threadIdx.x] = ext[2 * k];
     hi_s[threadIdx.x] = ext[2 * k + 1];
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            lo_s[threadIdx.x] = min(lo_s[threadIdx.x], lo_s[threadIdx.x + st]);
-            hi_s[threadIdx.x] = max(hi_s[threadIdx.x], hi_s[threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
+    tree_minmax256(lo_s, hi_s);
     lo = lo_s[0];  hi = hi_s[0];
     __syncthreads();
 }
@@ -176,7 +110,7 @@ __global__ __launch_bounds__(256) void image_batch_rotate_kernel(const unsigned 
     int ulo, uhi;
     reduce_ext(ext, blockIdx.y, lo_s, hi_s, ulo, uhi);
     // rotate()'s clip range: the extremes of the f32 plane u / 255
-    const double clo = (double)((float)ulo / 255.0f), chi = (double)((float)uhi / 255.0f);
+    const double clo = (double)u8_unit((unsigned char)ulo), chi = (double)u8_unit((unsigned char)uhi);
     const double cval = it.cval;
     const bool keep_cval = !(clo <= cval && cval <= chi);
     const unsigned char *g = arena + it.offset;
@@ -192,7 +126,7 @@ __global__ __launch_bounds__(256) void image_batch_rotate_kernel(const unsigned 
     // belongs to pixel e / 3.  The <= 86 pixels of a chunk are rotated ONCE each (threads 0 .. 85) and handed to the
     // threads that own their elements through LDS, so every thread adds the addends image_sum_f64_kernel gives it, in
     // its order.
-    for (long long e0 = (long long)blockIdx.x * 256; e0 < n; e0 += (long long)IB_PARTS * 256) {
+    for (long long e0 = (long long)blockIdx.x * 256; e0 < n; e0 += (long long)IMG_PARTS * 256) {
         const long long P0 = e0 / 3, P = P0 + threadIdx.x;
         if (threadIdx.x < IB_CHUNK_PIXELS && P < npix) {
             const int y = (int)(P / vw), px = (int)(P - (long long)y * vw);
@@ -208,7 +142,7 @@ __global__ __launch_bounds__(256) void image_batch_rotate_kernel(const unsigned 
                 double tv = cval;
                 if (r >= 0 && r < H0 && c >= 0 && c < W0) {
                     const int sx = it.flipped ? W0 - 1 - (int)c : (int)c;
-                    tv = (double)((float)g[(size_t)r * it.row_stride + sx] / 255.0f);
+                    tv = (double)u8_unit(g[(size_t)r * it.row_stride + sx]);
                 }
                 p[k] = tv;
             }
@@ -221,7 +155,7 @@ __global__ __launch_bounds__(256) void image_batch_rotate_kernel(const unsigned 
         const long long i = e0 + threadIdx.x;
         if (i < n) {
             const double v = pix_s[(int)(i / 3 - P0)];
-            acc += ib_adjust_value(v, it.use_brightness, it.brightness_delta);
+            acc += adjust_value(v, it.use_brightness, it.brightness_delta);
             lo = fmin(lo, v);
             hi = fmax(hi, v);
         }
@@ -229,19 +163,12 @@ __global__ __launch_bounds__(256) void image_batch_rotate_kernel(const unsigned 
     }
     s[threadIdx.x] = acc;  dlo_s[threadIdx.x] = lo;  dhi_s[threadIdx.x] = hi;
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            s[threadIdx.x] += s[threadIdx.x + st];
-            dlo_s[threadIdx.x] = fmin(dlo_s[threadIdx.x], dlo_s[threadIdx.x + st]);
-            dhi_s[threadIdx.x] = fmax(dhi_s[threadIdx.x], dhi_s[threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
+    tree_sum_minmax256(s, dlo_s, dhi_s);
     if (threadIdx.x == 0) {
-        double *o = sums2 + (size_t)blockIdx.y * 3 * IB_PARTS;
+        double *o = sums2 + (size_t)blockIdx.y * 3 * IMG_PARTS;
         o[blockIdx.x] = s[0];
-        o[IB_PARTS + blockIdx.x] = dlo_s[0];
-        o[2 * IB_PARTS + blockIdx.x] = dhi_s[0];
+        o[IMG_PARTS + blockIdx.x] = dlo_s[0];
+        o[2 * IMG_PARTS + blockIdx.x] = dhi_s[0];
     }
 }
 
@@ -267,34 +194,24 @@ __global__ __launch_bounds__(256) void image_batch_blob_kernel(const unsigned ch
     double lo, hi, mm64 = 0.0;
     if (!rot) {
         // every block re-reduces the partials in image.hip's order, then tabulates the pre-resize map of a u8 value
-        s[threadIdx.x] = sums[(size_t)blockIdx.y * IB_PARTS + threadIdx.x];
+        s[threadIdx.x] = sums[(size_t)blockIdx.y * IMG_PARTS + threadIdx.x];
         int ulo, uhi;
         reduce_ext(ext, blockIdx.y, lo_s, hi_s, ulo, uhi);      // (its first barrier publishes s[] too)
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
-            __syncthreads();
-        }
+        tree_sum256(s);
         const float mm = it.use_contrast ? (float)(s[0] / (double)((long long)vh * vw)) : 0.0f;
-        table[threadIdx.x] = ib_pre_u8((int)threadIdx.x, it, mm, mean_sub);
+        table[threadIdx.x] = pre_u8((int)threadIdx.x, it, mm, mean_sub);
         __syncthreads();
         const double a = table[ulo], b = table[uhi];
         lo = fmin(a, b);  hi = fmax(a, b);
     } else {
-        const double *p2 = sums2 + (size_t)blockIdx.y * 3 * IB_PARTS;
+        const double *p2 = sums2 + (size_t)blockIdx.y * 3 * IMG_PARTS;
         s[threadIdx.x] = p2[threadIdx.x];
-        dlo_s[threadIdx.x] = p2[IB_PARTS + threadIdx.x];
-        dhi_s[threadIdx.x] = p2[2 * IB_PARTS + threadIdx.x];
+        dlo_s[threadIdx.x] = p2[IMG_PARTS + threadIdx.x];
+        dhi_s[threadIdx.x] = p2[2 * IMG_PARTS + threadIdx.x];
         __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) {
-                s[threadIdx.x] += s[threadIdx.x + st];
-                dlo_s[threadIdx.x] = fmin(dlo_s[threadIdx.x], dlo_s[threadIdx.x + st]);
-                dhi_s[threadIdx.x] = fmax(dhi_s[threadIdx.x], dhi_s[threadIdx.x + st]);
-            }
-            __syncthreads();
-        }
+        tree_sum_minmax256(s, dlo_s, dhi_s);
         if (it.use_contrast) mm64 = s[0] / (double)((long long)vh * (vw * 3));
-        const double a = ib_pre_f64(dlo_s[0], it, mm64, mean_sub), b = ib_pre_f64(dhi_s[0], it, mm64, mean_sub);
+        const double a = pre_f64(dlo_s[0], it, mm64, mean_sub), b = pre_f64(dhi_s[0], it, mm64, mean_sub);
         lo = fmin(a, b);  hi = fmax(a, b);
     }
     const bool keep_cval = !(lo <= 0.0 && 0.0 <= hi);            // resize(): mode 'constant', cval 0
@@ -330,7 +247,7 @@ __global__ __launch_bounds__(256) void image_batch_blob_kernel(const unsigned ch
                 double t = 0.0;
                 if (r >= 0 && r < vh && c >= 0 && c < vw) {
                     if (rot) {
-                        t = ib_pre_f64(plane[(size_t)r * vw + (size_t)c], it, mm64, mean_sub);
+                        t = pre_f64(plane[(size_t)r * vw + (size_t)c], it, mm64, mean_sub);
                     } else {
                         const int sx = flipped ? vw - 1 - (int)c : (int)c;
                         t = table[v.p[(size_t)r * stride + sx]];
@@ -402,12 +319,12 @@ extern "C" int wssdl_image_batch_blob(const uint8_t *arena, size_t arena_bytes, 
     hipStream_t st = as_stream(stream);
     char *ws = static_cast<char *>(workspace);
     double *sums = reinterpret_cast<double *>(ws);
-    int *ext = reinterpret_cast<int *>(ws + (size_t)n_images * IB_PARTS * sizeof(double));
+    int *ext = reinterpret_cast<int *>(ws + (size_t)n_images * IMG_PARTS * sizeof(double));
     double *sums2 = reinterpret_cast<double *>(ws + (size_t)n_images * IB_STATS1);
     double *planes = reinterpret_cast<double *>(ws + (size_t)n_images * (IB_STATS1 + IB_STATS2));
-    hipLaunchKernelGGL(image_batch_stats_kernel, dim3(IB_PARTS, n_images), dim3(256), 0, st, arena, items_dev, sums, ext);
+    hipLaunchKernelGGL(image_batch_stats_kernel, dim3(IMG_PARTS, n_images), dim3(256), 0, st, arena, items_dev, sums, ext);
     if (rotated > 0)
-        hipLaunchKernelGGL(image_batch_rotate_kernel, dim3(IB_PARTS, n_images), dim3(256), 0, st, arena, items_dev, ext,
+        hipLaunchKernelGGL(image_batch_rotate_kernel, dim3(IMG_PARTS, n_images), dim3(256), 0, st, arena, items_dev, ext,
                            sums2, planes);
     const long long n = (long long)Hmax * Wmax;
     const int blocks = (int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);

@@ -13,13 +13,12 @@
 // All arithmetic is f32 in NumPy's operation order (separate multiply and add);
 // exp is evaluated in f64 and rounded once to f32 (NumPy's own f32 exp is only
 // accurate to ~2.5 ulp, so decoded boxes are tolerance-level by nature).
+#include "box_code.hip.h"
 #include "order_sort.hip.h"
 
 #include <stdlib.h>
 
 namespace wssdl {
-
-typedef float float4v __attribute__((ext_vector_type(4)));
 
 struct DecodeArgs {
     const float *prob, *pred, *im_info;
@@ -68,28 +67,13 @@ __device__ __forceinline__ unsigned long long decode_anchor(const DecodeArgs &g,
     const float ay1 = (float)(g.base.v[a][1] + (double)(stride * h));
     const float ax2 = (float)(g.base.v[a][2] + (double)(stride * w));
     const float ay2 = (float)(g.base.v[a][3] + (double)(stride * h));
-    float aw = ax2 - ax1;  aw = aw + 1.0f;
-    float ah = ay2 - ay1;  ah = ah + 1.0f;
-    float hx = 0.5f * aw, hy = 0.5f * ah;
-    const float cx = ax1 + hx, cy = ay1 + hy;
-    float pcx = d.x * aw;  pcx = pcx + cx;
-    float pcy = d.y * ah;  pcy = pcy + cy;
-    const float pw = (float)exp((double)d.z) * aw;
-    const float ph = (float)exp((double)d.w) * ah;
-    const float hpw = 0.5f * pw, hph = 0.5f * ph;
-    float x1 = pcx - hpw, y1 = pcy - hph, x2 = pcx + hpw, y2 = pcy + hph;
-    // clip_boxes (bbox_transform.py:63-77): max(min(v, im-1), 0)
-    const float xm = im_w - 1.0f, ym = im_h - 1.0f;
-    x1 = fmaxf(fminf(x1, xm), 0.0f);
-    y1 = fmaxf(fminf(y1, ym), 0.0f);
-    x2 = fmaxf(fminf(x2, xm), 0.0f);
-    y2 = fmaxf(fminf(y2, ym), 0.0f);
+    // bbox_transform_inv + clip_boxes (box_code.hip.h)
+    const float4v o = clip_box_f32(decode_box_f32(ax1, ay1, ax2, ay2, d), im_w - 1.0f, im_h - 1.0f);
     // _filter_boxes (proposal_layer_tf_bus.py:123,151-156)
     const float ms = g.min_size * im_scale;
-    float bw = x2 - x1;  bw = bw + 1.0f;
-    float bh = y2 - y1;  bh = bh + 1.0f;
+    float bw = o.z - o.x;  bw = bw + 1.0f;
+    float bh = o.w - o.y;  bh = bh + 1.0f;
     const bool valid = (bw >= ms) && (bh >= ms);
-    float4v o;  o.x = x1;  o.y = y1;  o.z = x2;  o.w = y2;
     const int M = g.H * W * A;
     *reinterpret_cast<float4v *>(g.boxes + ((size_t)n * M + i) * 4) = o;
     return valid ? score_key(score, (unsigned)i) : 0ull;

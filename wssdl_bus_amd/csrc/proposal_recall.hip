@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void recall_iou_kernel(Candidates cand, const 
     load_box(cand, i, p, P, b);
     for (int g = g0; g < g1; ++g) {
         const double *q = gt_boxes + (size_t)g * 4;
-        const double qarea = (q[2] - q[0] + 1) * (q[3] - q[1] + 1);
+        const double qarea = box_area_f64(q[0], q[1], q[2], q[3]);
         ov[(size_t)g * P + p] = iou_pair(b[0], b[1], b[2], b[3], q[0], q[1], q[2], q[3], qarea);
     }
 }

@@ -116,28 +116,10 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_sliced_kernel(
     const RoiGeom g = roi_geometry(rois + (size_t)r * 5, scale, PH, PW);
     const bool bad = g.batch < 0 || g.batch >= N;
     const float *img = bottom + (size_t)(bad ? 0 : g.batch) * H * W * C;
-    int hs, he;
-    if (rounding == WSSDL_ROI_ROUND_CPU) {
-        hs = (int)((float)ph * g.bin_h);
-        he = (int)((float)(ph + 1) * g.bin_h);
-    } else {
-        hs = (int)floorf((float)ph * g.bin_h);
-        he = (int)ceilf((float)(ph + 1) * g.bin_h);
-    }
-    hs = min(max(hs + g.sh, 0), H);
-    he = min(max(he + g.sh, 0), H);
+    const int hs = win_start(ph, g.bin_h, g.sh, H, rounding), he = win_end(ph, g.bin_h, g.sh, H, rounding);
     size_t o = ((size_t)row * PW) * C + c0;
     for (int pw = 0; pw < PW; ++pw, o += C) {
-        int ws, we;
-        if (rounding == WSSDL_ROI_ROUND_CPU) {
-            ws = (int)((float)pw * g.bin_w);
-            we = (int)((float)(pw + 1) * g.bin_w);
-        } else {
-            ws = (int)floorf((float)pw * g.bin_w);
-            we = (int)ceilf((float)(pw + 1) * g.bin_w);
-        }
-        ws = min(max(ws + g.sw, 0), W);
-        we = min(max(we + g.sw, 0), W);
+        const int ws = win_start(pw, g.bin_w, g.sw, W, rounding), we = win_end(pw, g.bin_w, g.sw, W, rounding);
         const bool empty = (he <= hs) || (we <= ws) || bad;
         float4v mv = empty ? (float4v)(0.0f) : (float4v)(-FLT_MAX);
         int4v mi = (int4v)(-1);

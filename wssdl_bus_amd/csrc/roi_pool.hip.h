@@ -1,5 +1,5 @@
 // Geometry shared by the RoI-pool kernels (roi_pool.hip: reference argmax layout;
-// roi_pool_compact.hip: training path with a 1-byte argmax).
+// roi_pool_compact.hip: training path with a 1-byte argmax; roi_pool_walk.hip: its list-driven backward).
 //
 // Reference: code/lib/roi_pooling_layer/roi_pooling_op_gpu.cu.cc:36-58 (RoI rounding, bin
 // windows, canonical rounding), roi_pooling_op.cc:152-170 (CPU rounding), :169-177 of the
@@ -32,23 +32,27 @@ __device__ __forceinline__ RoiGeom roi_geometry(const float *__restrict__ r, flo
     return g;
 }
 
+// clipped window [start, end) of bin p along one axis (bin size, RoI start rs, map size limit), both rounding modes:
+// roi_pooling_op_gpu.cu.cc:51-58,61-63 (floor / ceil) and roi_pooling_op.cc:167-170,173-175 (truncation).  One
+// definition: every RoI-pool kernel takes its windows from these two.
+__device__ __forceinline__ int win_start(int p, float bin, int rs, int limit, int rounding) {
+    const float v = (float)p * bin;
+    const int s = (rounding == WSSDL_ROI_ROUND_CPU) ? (int)v : (int)floorf(v);
+    return min(max(s + rs, 0), limit);
+}
+
+__device__ __forceinline__ int win_end(int p, float bin, int rs, int limit, int rounding) {
+    const float v = (float)(p + 1) * bin;
+    const int e = (rounding == WSSDL_ROI_ROUND_CPU) ? (int)v : (int)ceilf(v);
+    return min(max(e + rs, 0), limit);
+}
+
 __device__ __forceinline__ void bin_window(const RoiGeom &g, int ph, int pw, int H, int W,
                                            int rounding, int &hs, int &he, int &ws, int &we) {
-    if (rounding == WSSDL_ROI_ROUND_CPU) {          // roi_pooling_op.cc:167-170
-        hs = (int)((float)ph * g.bin_h);
-        ws = (int)((float)pw * g.bin_w);
-        he = (int)((float)(ph + 1) * g.bin_h);
-        we = (int)((float)(pw + 1) * g.bin_w);
-    } else {                                        // roi_pooling_op_gpu.cu.cc:51-58
-        hs = (int)floorf((float)ph * g.bin_h);
-        ws = (int)floorf((float)pw * g.bin_w);
-        he = (int)ceilf((float)(ph + 1) * g.bin_h);
-        we = (int)ceilf((float)(pw + 1) * g.bin_w);
-    }
-    hs = min(max(hs + g.sh, 0), H);
-    he = min(max(he + g.sh, 0), H);
-    ws = min(max(ws + g.sw, 0), W);
-    we = min(max(we + g.sw, 0), W);
+    hs = win_start(ph, g.bin_h, g.sh, H, rounding);
+    he = win_end(ph, g.bin_h, g.sh, H, rounding);
+    ws = win_start(pw, g.bin_w, g.sw, W, rounding);
+    we = win_end(pw, g.bin_w, g.sw, W, rounding);
 }
 
 // 1-byte arg-max of the training path (roi_pool_compact.hip): (h - hstart) << 4 | (w - wstart), 0xff = empty bin

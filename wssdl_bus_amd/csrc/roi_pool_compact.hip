@@ -32,20 +32,7 @@
 
 namespace wssdl {
 
-// (ARG8_EMPTY, ARG8_MAX_WIN_H / _W and the window-table layout: roi_pool.hip.h)
-
-// clipped window start of bin p: roi_pooling_op_gpu.cu.cc:51-52,61-63 / roi_pooling_op.cc:167-168,173-175
-__device__ __forceinline__ int win_start(int p, float bin, int rs, int limit, int rounding) {
-    const float v = (float)p * bin;
-    const int s = (rounding == WSSDL_ROI_ROUND_CPU) ? (int)v : (int)floorf(v);
-    return min(max(s + rs, 0), limit);
-}
-
-__device__ __forceinline__ int win_end(int p, float bin, int rs, int limit, int rounding) {
-    const float v = (float)(p + 1) * bin;
-    const int e = (rounding == WSSDL_ROI_ROUND_CPU) ? (int)v : (int)ceilf(v);
-    return min(max(e + rs, 0), limit);
-}
+// (win_start / win_end, ARG8_EMPTY, ARG8_MAX_WIN_H / _W and the window-table layout: roi_pool.hip.h)
 
 // ------------------------------------------------------------------ forward ---
 // Workgroup b serves channel slice b % 8 (one XCD's L2 then holds only its slice of the feature

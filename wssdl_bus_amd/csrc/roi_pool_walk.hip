@@ -44,15 +44,8 @@
 
 namespace wssdl {
 
-constexpr unsigned ARG8_EMPTY_W = 0xffu;
 constexpr int WALK_SLOTS = 8;            // slots per record (64 B)
 constexpr int WALK_MAX_SEGMENTS = 16;    // split form: segments a tile's stream may be cut into
-
-__device__ __forceinline__ int win_start_w(int p, float bin, int rs, int limit, int rounding) {
-    const float v = (float)p * bin;
-    const int s = (rounding == WSSDL_ROI_ROUND_CPU) ? (int)v : (int)floorf(v);
-    return min(max(s + rs, 0), limit);
-}
 
 struct WalkWs {
     int *tile_slots;    // [items] candidate bins of each (image, tile)
@@ -168,7 +161,7 @@ __device__ __forceinline__ AxisEntry axis_entry(int t0, int limit, int rs, int r
     if (pn <= 0 || re < rs) { e.mask = 0ull;  return e; }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int a = min(max(win_start_w(p0 + k, bin, rs, limit, rounding) - t0, -16), 15);
+        const int a = min(max(win_start(p0 + k, bin, rs, limit, rounding) - t0, -16), 15);
         e.info |= (unsigned long long)((unsigned)a & 31u) << (5 * k);
     }
     e.info |= ((unsigned long long)(unsigned)p0 << 40) | ((unsigned long long)(unsigned)pn << 48);
@@ -212,12 +205,6 @@ __global__ __launch_bounds__(256) void walk_axes_kernel(
 // (bin, cell) pair is applied once.  What lands outside the tile's own SN x SN cells goes to a halo buffer that
 // walk_merge_kernel adds to the owners in a fixed order: deterministic, NOT the reference's association
 // (roi_pooling_op_gpu.cu.cc:132-186 sums roi^, ph^, pw^ per cell) -- a separate entry point, like the split form.
-__device__ __forceinline__ int win_end_w(int p, float bin, int rs, int limit, int rounding) {
-    const float v = (float)(p + 1) * bin;
-    const int e = (rounding == WSSDL_ROI_ROUND_CPU) ? (int)v : (int)ceilf(v);        // roi_pooling_op.cc:169-170 / _gpu.cu.cc:53-58
-    return min(max(e + rs, 0), limit);
-}
-
 template <int RN, int SN>
 __device__ __forceinline__ AxisEntry axis_entry_own(int T, int limit, int rs, int re, float bin, int P, int rounding) {
     static_assert(SN >= 1 && SN <= RN && RN <= 8 && RN - SN <= SN, "halo no larger than the tile; 8-bit masks");
@@ -234,7 +221,7 @@ __device__ __forceinline__ AxisEntry axis_entry_own(int T, int limit, int rs, in
     for (int k = 0; k < 8; ++k) {
         unsigned bits = 0u;
         if (k < pn) {
-            const int s = win_start_w(p0 + k, bin, rs, limit, rounding), z = win_end_w(p0 + k, bin, rs, limit, rounding);
+            const int s = win_start(p0 + k, bin, rs, limit, rounding), z = win_end(p0 + k, bin, rs, limit, rounding);
             // the chain of listings of this window: u = first line not covered yet
             int u = s;
             for (int it = 0; it < 64 && u < z; ++it) {
@@ -258,7 +245,7 @@ __device__ __forceinline__ AxisEntry axis_entry_own(int T, int limit, int rs, in
     e.mask = m >> (8 * first);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int a = min(max(win_start_w(p0 + k, bin, rs, limit, rounding) - t0, -16), 15);
+        const int a = min(max(win_start(p0 + k, bin, rs, limit, rounding) - t0, -16), 15);
         e.info |= (unsigned long long)((unsigned)a & 31u) << (5 * k);
     }
     e.info |= ((unsigned long long)(unsigned)p0 << 40) | ((unsigned long long)(unsigned)pn << 48);
@@ -561,7 +548,7 @@ __device__ __forceinline__ void process_rec(const SlotData<CPL> &d, const SlotRe
                 const unsigned code = (a >> (8 * p)) & 0xffu;
                 th = hs + (int)(code >> 4);
                 tw = ws + (int)(code & 15u);
-                live = code != ARG8_EMPTY_W;
+                live = code != ARG8_EMPTY;
             }
             // tile, in_roi and candidate-bin tests: the masks have no bits where a cell outside the
             // tile would index (th, tw in [-16, 30]; shifts use the low 5 bits)

@@ -19,7 +19,8 @@
 // roi_targets   : one lane per sampled RoI: label (background clamped to 0, :265),
 //                 all-f32 bbox_transform (:220), expansion into the 4*num_classes
 //                 layout with inside / outside weights (:199-209, :89).
-#include "common.hip.h"
+#include "box_code.hip.h"
+#include "box_iou.hip.h"
 #include "select.hip.h"
 
 namespace wssdl {
@@ -36,16 +37,7 @@ __device__ __forceinline__ void roi_gt_assign_row(const float *b, const float *_
         const float *g = gt_boxes + (size_t)img * max_gt * 5;
         for (int k = 0; k < np; ++k) {
             const double qx1 = g[k * 5 + 0], qy1 = g[k * 5 + 1], qx2 = g[k * 5 + 2], qy2 = g[k * 5 + 3];
-            const double qarea = (qx2 - qx1 + 1) * (qy2 - qy1 + 1);
-            double ov = 0.0;
-            double iw = fmin(bx2, qx2) - fmax(bx1, qx1) + 1;
-            if (iw > 0) {
-                double ih = fmin(by2, qy2) - fmax(by1, qy1) + 1;
-                if (ih > 0) {
-                    double ua = (bx2 - bx1 + 1) * (by2 - by1 + 1) + qarea - iw * ih;
-                    ov = iw * ih / ua;
-                }
-            }
+            const double ov = iou_pair(bx1, by1, bx2, by2, qx1, qy1, qx2, qy2, box_area_f64(qx1, qy1, qx2, qy2));
             if (k == 0 || ov > best) { best = ov; arg = k; }   // numpy argmax: first maximum
         }
     }
@@ -106,19 +98,9 @@ __global__ __launch_bounds__(256) void roi_targets_kernel(
         label = g[4];
         const int cls = (int)label;
         if (label > 0.0f && cls < num_classes) {
-            // bbox_transform with f32 operands on both sides (:220)
-            float ew = b[3] - b[1];  ew = ew + 1.0f;
-            float eh = b[4] - b[2];  eh = eh + 1.0f;
-            float hew = 0.5f * ew, heh = 0.5f * eh;
-            const float ecx = b[1] + hew, ecy = b[2] + heh;
-            float gw = g[2] - g[0];  gw = gw + 1.0f;
-            float gh = g[3] - g[1];  gh = gh + 1.0f;
-            float hgw = 0.5f * gw, hgh = 0.5f * gh;
-            const float gcx = g[0] + hgw, gcy = g[1] + hgh;
-            float t0 = (gcx - ecx) / ew;
-            float t1 = (gcy - ecy) / eh;
-            float t2 = (float)log((double)(gw / ew));
-            float t3 = (float)log((double)(gh / eh));
+            // bbox_transform with f32 operands on both sides (:220, box_code.hip.h)
+            const float4v t = encode_box<float>(b[1], b[2], b[3], b[4], g[0], g[1], g[2], g[3]);
+            float t0 = t.x, t1 = t.y, t2 = t.z, t3 = t.w;
             if (norm.on) {
                 t0 = (float)(((double)t0 - norm.mean[0]) / norm.std[0]);
                 t1 = (float)(((double)t1 - norm.mean[1]) / norm.std[1]);
