@@ -735,6 +735,7 @@ WSSDL_API int wssdl_image_batch_blob(const uint8_t *arena, size_t arena_bytes, c
  *   scores [R, num_classes] f32, boxes [R, 4 * num_classes] f32 (class-wise decoded boxes);
  *   dets   [num_classes-1, R, 5] f32: row p of class j-1 = (x1, y1, x2, y2, score) of its p-th kept
  *          detection in descending score order; counts [num_classes-1] i32 = rows that survive the cap.
+ *          Rows of dets at and beyond a class's count are not written: they keep what the caller's buffer held.
  * One set of launches for all classes, no host read-back.  num_classes <= 65. */
 WSSDL_API size_t wssdl_post_detections_workspace_bytes(int R, int num_classes);
 WSSDL_API int wssdl_post_detections(const float *scores, const float *boxes, int R, int num_classes,
@@ -747,7 +748,8 @@ WSSDL_API int wssdl_post_detections(const float *scores, const float *boxes, int
  *          the proposal layer both are); rows with a batch index < 0 (or >= n_images) are ignored.
  *   scores [R, num_classes] f32, boxes [R, 4 * num_classes] f32: the blob's class scores and decoded boxes;
  *   dets   [n_images, num_classes-1, max_rows_per_image, 5] f32, counts [n_images, num_classes-1] i32:
- *          dets[i, j-1, :counts[i, j-1]] = image i's class-j detections, best first, after image i's own cap.
+ *          dets[i, j-1, :counts[i, j-1]] = image i's class-j detections, best first, after image i's own cap
+ *          (the rows at and beyond the count are not written, as in the single-image op).
  * Every image's output is bit for bit that of wssdl_post_detections on its rows alone.  An image with more
  * rows than max_rows_per_image is reported as counts[i, 0] = -1 (the other counts of the image 0).
  * num_classes <= 65, n_images * (num_classes-1) * max_rows_per_image <= 2^24 and

@@ -110,8 +110,9 @@ class ReferenceOptimizer(object):
             off += -(-p.numel() // ALIGN) * ALIGN
         if self._flat:
             self.buffers = {s: torch.zeros((off,), dtype=torch.float32, device=dev) for s in SLOTS[kind]}
-            self.views = {s: [b.as_strided(p.shape, p.stride(), o) for p, o in zip(self.params, self.offsets)]
-                          for s, b in self.buffers.items()}
+            # (as_strided's offset counts from the storage's start, not from b's own first element)
+            self.views = {s: [b.as_strided(p.shape, p.stride(), b.storage_offset() + o)
+                              for p, o in zip(self.params, self.offsets)] for s, b in self.buffers.items()}
         else:
             self.buffers = None
             self.views = {s: [torch.zeros_like(p, memory_format=torch.preserve_format) for p in self.params]

@@ -939,7 +939,8 @@ class _L2DecayFn(torch.autograd.Function):
         gout = gout.to(torch.float32).contiguous()
         flat = torch.empty((tab.total,), dtype=torch.float32, device=dev)
         _call("wsplumb_l2decay_backward", dev, _p(tab.table), tab.n_chunks, _p(gout), ctx.k, _p(flat))
-        return (None,) + tuple(flat.as_strided(p.shape, p.stride(), off) if need else None
+        # (as_strided's offset counts from the storage's start, not from flat's own first element)
+        return (None,) + tuple(flat.as_strided(p.shape, p.stride(), flat.storage_offset() + off) if need else None
                                for p, off, need in zip(params, tab.offsets, ctx.needs_input_grad[1:]))
 
 
