@@ -68,7 +68,8 @@ def hip_usable(params):
 class _Table:
     """Device tables of optim.hip for one parameter list.  `chunks`: row i = (parameter index, first float of chunk i
     inside that parameter's storage, its length, its element offset in the flat state buffers), the parameters
-    walked in storage order; `params`: the parameters' addresses."""
+    walked in storage order; `params`: the parameters' addresses.
+    Built once per parameter list, with two blocking copies from the host that synchronise it; a step has none."""
 
     def __init__(self, params, offsets):
         rows = []

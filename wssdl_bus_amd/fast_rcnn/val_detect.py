@@ -52,7 +52,8 @@ def validation_detections(layers, im_info, n_images, thresh=0.05, max_per_image=
     im_shapes: the original (H, W) of every image, to clip to as the reference does (im.shape); without it the bounds
     are (w / scale - 1, h / scale - 1) of im_info.  agnostic=None reads cfg.TEST.CLS_AGNOSTIC_NMS.
     -> (dets [N, K-1, P, 5] f32, counts [N, K-1] i32) on the GPU in post_detections_batched_device's layout, with
-    P = cfg.TRAIN.BATCH_SIZE (the sampler never emits more rows per image); nothing is read back."""
+    P = cfg.TRAIN.BATCH_SIZE (the sampler never emits more rows per image); nothing is read back.
+    With im_shapes the bounds go up in a blocking copy from the host, which synchronises it; without them nothing does."""
     n = int(n_images)
     rois = layers['roi-data'][0]
     R = int(rois.shape[0])

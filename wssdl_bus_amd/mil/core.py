@@ -150,7 +150,7 @@ def get_bag_logit_device(instance_logits, bag_column, bag_offset, bag_labels, ba
         sums = sums.index_add(0, bag.clamp(0, batch_size - 1), x1)
         mean = (sums / counts.clamp_min(1).double()).to(bag_logits.dtype)
         e1 = torch.zeros((1, K), dtype=bag_logits.dtype, device=logits.device)
-        e1[0, 1] = 1.0
+        e1[:, 1].fill_(1.0)                                         # (e1[0, 1] = 1.0 uploads a scalar: a host synchronisation)
         pooled = torch.ones_like(valid) if sel[0] == sel[1] else ((labels == 1) if sel[0] == _MEAN_BEN else (labels != 1))
         bag_logits = torch.where(pooled.unsqueeze(1), mean.unsqueeze(1) * e1, bag_logits)
     bag_logits = bag_logits * valid.unsqueeze(1).to(bag_logits.dtype)

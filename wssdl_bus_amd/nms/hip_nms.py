@@ -9,7 +9,8 @@ from .. import _lib
 def hip_nms(dets, thresh, max_keep=None, rule="nms"):
     """dets [n,5] (x1,y1,x2,y2,score).  Returns kept indices in score order:
     a python list for numpy input (like cpu_nms), an int64 GPU tensor otherwise.
-    rule "nms_new": the containment rule of utils/nms.pyx:70-123 on top of the IoU test."""
+    rule "nms_new": the containment rule of utils/nms.pyx:70-123 on top of the IoU test.
+    Synchronises the host: the number of kept boxes is read back to size the result."""
     as_np = _lib.wants_numpy(dets)
     d = _lib.to_device(dets, torch.float32)
     n = d.shape[0]

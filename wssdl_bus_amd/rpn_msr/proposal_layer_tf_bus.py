@@ -166,7 +166,9 @@ def proposal_layer(rpn_cls_prob_reshape, rpn_bbox_pred, im_info, is_training, is
                    _feat_stride=[16, ], anchor_scales=[8, 16, 32]):
     """Same contract as the reference: returns the rois blob [sum R_i, 5] f32 with
     rows (batch_idx, x1, y1, x2, y2).  `is_ws` is accepted and unused, as in the
-    reference.  numpy in -> numpy out; GPU tensors in -> GPU tensor out."""
+    reference.  numpy in -> numpy out; GPU tensors in -> GPU tensor out.
+    Without cfg.PADDED_ROIS the per-image counts are read back to compact the blob, which synchronises the host; the
+    padded form (padded_blob) never does."""
     return _run(rpn_cls_prob_reshape, rpn_bbox_pred, im_info, is_training, _feat_stride, anchor_scales, False)
 
 

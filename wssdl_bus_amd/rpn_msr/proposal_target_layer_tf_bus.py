@@ -258,7 +258,9 @@ def _weak_rois(rpn_rois, rois, images):
 def proposal_target_layer(rpn_rois, gt_boxes, num_gt_boxes, _num_classes, is_training, is_ws,
                           rng=None):
     """Alternating mode (:15-97).  Weak batches (is_training and is_ws) return every
-    RoI with zero labels / targets (:282-295)."""
+    RoI with zero labels / targets (:282-295).
+    With the reference's draw (an `rng`, or cfg.SAMPLING_RNG other than 'device') the overlaps are read back and the
+    rows are drawn on the host, which synchronises it; the device draw never does."""
     as_np = _lib.wants_numpy(rpn_rois)
     device_rng = _use_device_rng(rng)
     rng = npr if rng is None else rng

@@ -409,7 +409,8 @@ def image_batch_blob(plan, planes, device=None):
 
 def image_blob_per_image(plan, planes, device=None):
     """The same blob through the per-image functions (prep_im_with_params for every image, then im_list_to_blob):
-    the path _get_image_blob[_joint] take, with the plan's draws instead of fresh ones."""
+    the path _get_image_blob[_joint] take, with the plan's draws instead of fresh ones.
+    Every plane goes up in a blocking copy of its own, which synchronises the host once per image."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     ims = []
     for im, g in zip(plan.images, planes):
