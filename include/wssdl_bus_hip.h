@@ -792,6 +792,49 @@ WSSDL_API int wssdl_post_detections_agnostic_batched(const float *rois, const fl
                      int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
                      wssdl_stream_t stream);
 
+/* Test-time augmentation: the same step over the V views of every image (mirrored copies, cfg.TEST.FLIP_AUG) with
+ * optional box voting (cfg.TEST.BBOX_VOTE), one set of launches, no host read-back, capturable.
+ *   rois [R, 5], scores [R, num_classes], boxes [R, 4 * num_classes] f32: as in the batched op, the blob of a forward
+ *          over n_images * views SOURCE images.  Source image s is view s % views of output image s / views: the views
+ *          of an image are interleaved, so the rows of one output image are contiguous and the output images come in
+ *          ascending order.  Rows whose batch index is outside [0, n_images * views) are dead and ignored.
+ *   flip_width [n_images * views] f32 or NULL: an entry w >= 0 marks a mirrored source image of original width w; an
+ *          entry < 0 (or a NULL array) a source that is not mirrored.
+ * Per output image t:
+ *   1. Un-mirror.  For a row of a mirrored source every class's box becomes
+ *        x1' = max((w - x2) - 1, 0),   x2' = (w - x1) - 1,
+ *      every operation rounded to f32 on its own (the arithmetic of wssdl_flip_boxes, then the clamp: the clip bound
+ *      of the decode can exceed w - 1 by a fraction of a pixel); y is unchanged.  The inputs are not modified: the
+ *      un-mirrored boxes live in the workspace.
+ *   2. Candidates of class j >= 1: the rows of t with scores[r, j] > score_thresh in ascending row order, all views
+ *      together.
+ *   3. Greedy NMS at nms_thresh over them exactly as in the batched op (the cpu_nms rule, descending score, among equal
+ *      scores the later row first); with agnostic != 0 the union pass of wssdl_post_detections_agnostic_batched follows,
+ *      with its limit (num_classes-1) * max_rows_per_image <= WSSDL_POST_AGNOSTIC_MAX_UNION.
+ *   4. The cap max_per_image as in the batched op.
+ *   5. Voting, when vote_thresh > 0.  For each class-j detection d left by 3-4, over the class-j candidates c of step 2
+ *      (pre-NMS, un-mirrored, ascending row order): c votes when its overlap with d,
+ *        the f64 statement of the overlap op above -- utils/bbox.pyx, +1 pixel convention -- with c as the box and d as
+ *        the query, is >= vote_thresh
+ *      (d itself always votes: its overlap is exactly 1).  In f64, serially over the voters in ascending row order,
+ *        sw += (double)s_c;   sx[k] += (double)s_c * (double)c[k]      (k = x1, y1, x2, y2; the product is exact)
+ *      and d[k] = (float)(sx[k] / sw): one IEEE f64 division, one rounding to f32.  The score and the order of the
+ *      detections are unchanged; votes never cross classes, also under agnostic.
+ *   dets [n_images, num_classes-1, max_rows_per_image, 5] f32, counts [n_images, num_classes-1] i32: the batched op's
+ *          layout and conventions.  Rows of dets at and beyond a class's count are not written: they keep what the caller's buffer held.
+ *          An output image whose views together span more than max_rows_per_image rows (dead rows between its views
+ *          included) gets counts[t, 0] = -1 and zeros in its other counts.
+ * WSSDL_ERR_INVALID_ARGUMENT without a launch: views < 1 or views > 8; the batched op's limits (on n_images output
+ * images); vote_thresh > 1; vote_thresh > 0 with score_thresh < 0 (the weights must be positive); a NULL rois, scores,
+ * boxes, dets or workspace with R > 0.  R == 0: zero counts, nothing else launched.
+ * With views == 1, no mirrored source and vote_thresh <= 0 the output is bit for bit the batched op's. */
+WSSDL_API size_t wssdl_post_detections_views_workspace_bytes(int n_images, int views, int max_rows_per_image,
+                     int num_classes);
+WSSDL_API int wssdl_post_detections_views(const float *rois, const float *scores, const float *boxes, int R,
+                     int n_images, int views, const float *flip_width, int max_rows_per_image, int num_classes,
+                     float score_thresh, double nms_thresh, int agnostic, double vote_thresh, int max_per_image,
+                     float *dets, int32_t *counts, void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
+
 /* Decode and clip of the head's class-wise boxes: the step between a forward's layers and the post-detection ops
  * above, as the reference's validation loop does it on the sampled RoIs (fast_rcnn/train_bus.py:456-457 / :821-822:
  * boxes = rois[:, 1:5] / scale; clip_boxes(bbox_transform_inv(boxes, bbox_pred), im.shape)), for all images of a batch

@@ -117,7 +117,9 @@ SYMBOLS = {
     "wssdl_post_detections_agnostic": (_i, [_vp, _vp, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_post_detections_agnostic_batched_workspace_bytes": (_sz, [_i, _i, _i]),
     "wssdl_post_detections_agnostic_batched": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
-    "wssdl_decode_detections": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "wssdl_post_detections_views_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wssdl_post_detections_views": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _d, _i, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wssdl_decode_detections": (_i,[_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "wssdl_eval_detections_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wssdl_eval_detections": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _d,
                                    _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

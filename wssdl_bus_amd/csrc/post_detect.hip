@@ -28,6 +28,7 @@
 // compacted array, whatever P is: the batched and the single-image call agree bit for bit here too.  The same
 // ranking and mask + sweep launches run over the n_images union segments, and one workgroup per image takes the cap
 // from the union's kept list and splits that list by class (c = u / P) in order.
+#include "box_iou.hip.h"
 #include "nms.hip.h"
 #include "select.hip.h"
 
@@ -345,6 +346,147 @@ __global__ __launch_bounds__(CAP_BLOCK) void post_union_cap_kernel(const int *__
     if (t < nc && t < 64) counts[seg0 + t] = s_count[t];
 }
 
+// ------------------------------------------------------- views: flip augmentation and box voting at test time ---
+// wssdl_post_detections_views: the blob holds n_images * views SOURCE images, source s = view s % views of output
+// image s / views, so the rows of one output image are still one contiguous run.  The segment and key kernels below
+// are the two above with the output image in place of the batch index; the key kernel also brings the boxes of a
+// mirrored source back into the image's own frame while it copies them into the workspace (the inputs stay as they
+// are).  Ranking, sweep, union pass and cap then run unchanged on those copies.  Box voting follows the cap: one wave
+// per surviving detection, see post_vote_kernel.
+constexpr int POST_MAX_VIEWS = 8;
+
+// output image of RoI row r and its source image: the batch index b in [0, n_images * views) -> b / views, src = b;
+// -1 otherwise (dead padding rows, NaN, foreign images)
+__device__ __forceinline__ int roi_view_image(const float *__restrict__ rois, int r, int n_images, int views, int &src) {
+    const float b = rois[(size_t)r * 5];
+    if (!(b >= 0.0f && b < (float)(n_images * views))) {
+        src = -1;
+        return -1;
+    }
+    src = (int)b;
+    return src / views;
+}
+
+__global__ __launch_bounds__(SEG_BLOCK) void post_view_segments_kernel(const float *__restrict__ rois, int R, int n_images,
+                                                                        int views, int *__restrict__ lo,
+                                                                        int *__restrict__ hi) {
+    const int t = threadIdx.x;
+    for (int i = t; i < n_images; i += SEG_BLOCK) {
+        lo[i] = 0x7fffffff;
+        hi[i] = -1;
+    }
+    __syncthreads();
+    int src;
+    for (int r = t; r < R; r += SEG_BLOCK) {
+        const int b = roi_view_image(rois, r, n_images, views, src);
+        if (b < 0) continue;
+        if (r == 0 || roi_view_image(rois, r - 1, n_images, views, src) != b) atomicMin(&lo[b], r);
+        if (r == R - 1 || roi_view_image(rois, r + 1, n_images, views, src) != b) atomicMax(&hi[b], r);
+    }
+}
+
+// post_keys_kernel over the views of an image; a row of a mirrored source (flip_width[src] = w >= 0) is copied as
+//   x1' = max((w - x2) - 1, 0),  x2' = (w - x1) - 1     (wssdl_flip_boxes's two f32 steps, then the clamp)
+__global__ __launch_bounds__(256) void post_view_keys_kernel(const float *__restrict__ rois, const int *__restrict__ lo,
+                                                             const int *__restrict__ hi, const float *__restrict__ scores,
+                                                             const float *__restrict__ boxes,
+                                                             const float *__restrict__ flip_width, int R, int K, int n_images,
+                                                             int views, int P, float score_thresh,
+                                                             unsigned long long *__restrict__ keys, float *__restrict__ cboxes,
+                                                             int *__restrict__ sorted_index, int *__restrict__ n_sorted,
+                                                             int *__restrict__ cand_fill) {
+    const int nc = K - 1;
+    const long long nseg = (long long)n_images * nc;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nseg) { n_sorted[i] = 0;  cand_fill[i] = 0; }
+    if (i >= nseg * P) return;
+    const int seg = (int)(i / P), p = (int)(i - (long long)seg * P);
+    const int img = seg / nc, c = seg - img * nc;
+    int start, count, src = -1;
+    image_rows(lo, hi, img, R, start, count);
+    sorted_index[i] = -1;
+    const int r = start + p;
+    if (p >= count || roi_view_image(rois, r, n_images, views, src) != img) {
+        keys[i] = 0ull;
+        return;
+    }
+    const float s = scores[(size_t)r * K + c + 1];
+    keys[i] = (s > score_thresh) ? score_key(s, (unsigned)p) : 0ull;        // NaN fails the test like np.where
+    const float *b = boxes + (size_t)r * 4 * K + 4 * (c + 1);
+    float *o = cboxes + (size_t)i * 4;
+    float x1 = b[0], x2 = b[2];
+    const float w = flip_width ? flip_width[src] : -1.0f;
+    if (w >= 0.0f) {
+        float a = w - x2;  a = a - 1.0f;
+        float e = w - x1;  e = e - 1.0f;
+        x1 = fmaxf(a, 0.0f);
+        x2 = e;
+    }
+    o[0] = x1;  o[1] = b[1];  o[2] = x2;  o[3] = b[3];
+}
+
+// Box voting: one wave per detection d that survived NMS and the cap (segment = (image, class), position below the
+// segment's count).  The candidates are the segment's rows above the score threshold, pre-NMS and un-mirrored, as
+// post_view_keys_kernel left them in the workspace.  64 candidates at a time: every lane takes the f64 overlap of one
+// (box_iou.hip.h, the candidate as the box and d as the query), the wave ballots the members (overlap >= vote_thresh),
+// and the sums run over the set bits only, lowest first -- ascending row order, the statement's:
+//   sw += (double)s_c;  sx[k] += (double)s_c * (double)c[k]        (the product of two f32 is exact in f64)
+// d[k] = (float)(sx[k] / sw).  Every lane carries the same sums; lane 0 writes.  A wave reads its own detection and the
+// workspace and writes its own detection's four coordinates: no wave reads what another writes.
+constexpr int VOTE_BLOCK = 256;
+
+__global__ __launch_bounds__(VOTE_BLOCK) void post_vote_kernel(const float *__restrict__ rois, const int *__restrict__ lo,
+                                                               const int *__restrict__ hi, const float *__restrict__ scores,
+                                                               const float *__restrict__ cboxes,
+                                                               const int *__restrict__ counts, int R, int K, int n_images,
+                                                               int views, int P, float score_thresh, double vote_thresh,
+                                                               float *__restrict__ dets) {
+    const int nc = K - 1, lane = threadIdx.x & 63;
+    const long long wv = (long long)blockIdx.x * (VOTE_BLOCK / 64) + (threadIdx.x >> 6);
+    if (wv >= (long long)n_images * nc * P) return;
+    const int seg = (int)(wv / P), pos = (int)(wv - (long long)seg * P);
+    if (pos >= counts[seg]) return;                              // the same for the whole wave; -1 (overflow) has no rows
+    const int img = seg / nc, c = seg - img * nc;
+    int start, count;
+    image_rows(lo, hi, img, R, start, count);
+    if (count > P) return;
+    float *d = dets + ((size_t)seg * P + pos) * 5;
+    const double qx1 = d[0], qy1 = d[1], qx2 = d[2], qy2 = d[3];
+    const double qarea = box_area_f64(qx1, qy1, qx2, qy2);
+    double sw = 0.0, sx0 = 0.0, sx1 = 0.0, sx2 = 0.0, sx3 = 0.0;
+    for (int base = 0; base < count; base += 64) {               // count is the same for the whole wave
+        const int p = base + lane;
+        float s = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
+        bool member = false;
+        int src;
+        if (p < count && roi_view_image(rois, start + p, n_images, views, src) == img) {
+            s = scores[(size_t)(start + p) * K + c + 1];
+            if (s > score_thresh) {
+                const float *b = cboxes + ((size_t)seg * P + p) * 4;
+                b0 = b[0];  b1 = b[1];  b2 = b[2];  b3 = b[3];
+                member = iou_pair(b0, b1, b2, b3, qx1, qy1, qx2, qy2, qarea) >= vote_thresh;
+            }
+        }
+        unsigned long long m = __ballot(member);
+        while (m != 0ull) {
+            const int l = __ffsll((long long)m) - 1;
+            m &= m - 1ull;
+            const double ws = (double)__shfl(s, l);
+            sw += ws;
+            sx0 += ws * (double)__shfl(b0, l);
+            sx1 += ws * (double)__shfl(b1, l);
+            sx2 += ws * (double)__shfl(b2, l);
+            sx3 += ws * (double)__shfl(b3, l);
+        }
+    }
+    if (lane == 0 && sw > 0.0) {
+        d[0] = (float)(sx0 / sw);
+        d[1] = (float)(sx1 / sw);
+        d[2] = (float)(sx2 / sw);
+        d[3] = (float)(sx3 / sw);
+    }
+}
+
 // Limits of the batched form: the segments' rows are 32-bit item numbers of one select (<= 2^24), and the ranking
 // and mask grids put the segments on a grid dimension of at most 65535 blocks.
 constexpr long long POST_MAX_ITEMS = 1LL << 24;
@@ -358,7 +500,8 @@ static_assert(POST_MAX_UNION % 16 == 0, "the padded union pitch must not pass th
 
 static int post_detections_run(const float *rois, const float *scores, const float *boxes, int R, int n_images, int P,
                                int num_classes, float score_thresh, double nms_thresh, int max_per_image, float *dets,
-                               int32_t *counts, void *workspace, bool agnostic, hipStream_t st) {
+                               int32_t *counts, void *workspace, bool agnostic, hipStream_t st, int views = 0,
+                               const float *flip_width = nullptr) {
     const int nc = num_classes - 1;
     const int nseg = n_images * nc;
     PostWs w, uw;
@@ -368,18 +511,29 @@ static int post_detections_run(const float *rois, const float *scores, const flo
     else
         carve_post(workspace, n_images, P, nc, &w);
     const int *lo = nullptr, *hi = nullptr;
-    if (rois) {
-        hipLaunchKernelGGL(post_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, w.img_lo, w.img_hi);
-        int rc = check_launch();
-        if (rc) return rc;
+    const int blocks = cdiv((long long)nseg * P, 256);
+    int rc;
+    if (views > 0) {            // wssdl_post_detections_views: the output image of a row is its source image / views
+        hipLaunchKernelGGL(post_view_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, views, w.img_lo,
+                           w.img_hi);
+        if ((rc = check_launch())) return rc;
         lo = w.img_lo;
         hi = w.img_hi;
+        hipLaunchKernelGGL(post_view_keys_kernel, dim3(blocks), dim3(256), 0, st, rois, lo, hi, scores, boxes, flip_width, R,
+                           num_classes, n_images, views, P, score_thresh, w.keys, w.boxes, w.sorted_index, w.n_sorted,
+                           w.cand_fill);
+        if ((rc = check_launch())) return rc;
+    } else {
+        if (rois) {
+            hipLaunchKernelGGL(post_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, w.img_lo, w.img_hi);
+            if ((rc = check_launch())) return rc;
+            lo = w.img_lo;
+            hi = w.img_hi;
+        }
+        hipLaunchKernelGGL(post_keys_kernel, dim3(blocks), dim3(256), 0, st, rois, lo, hi, scores, boxes, R, num_classes,
+                           n_images, P, score_thresh, w.keys, w.boxes, w.sorted_index, w.n_sorted, w.cand_fill);
+        if ((rc = check_launch())) return rc;
     }
-    const int blocks = cdiv((long long)nseg * P, 256);
-    hipLaunchKernelGGL(post_keys_kernel, dim3(blocks), dim3(256), 0, st, rois, lo, hi, scores, boxes, R, num_classes, n_images,
-                       P, score_thresh, w.keys, w.boxes, w.sorted_index, w.n_sorted, w.cand_fill);
-    int rc = check_launch();
-    if (rc) return rc;
     if ((rc = launch_rank_topk(w.keys, P, nseg, P, w.cand, w.thresh, w.cand_fill, w.sorted_index, w.n_sorted, w.mask,
                                sizeof(unsigned long long) * (size_t)nseg * P * nms_mask_pitch(P), st)))
         return rc;
@@ -477,6 +631,51 @@ extern "C" int wssdl_post_detections_agnostic_batched(const float *rois, const f
                                                       wssdl_stream_t stream) {
     return post_detections_entry(rois, scores, boxes, R, n_images, max_rows_per_image, num_classes, score_thresh, nms_thresh,
                                  max_per_image, dets, counts, workspace, workspace_bytes, true, stream);
+}
+
+// The workspace is that of the batched op: the class-agnostic one where the shape admits a class-agnostic call, so
+// that one query serves both values of `agnostic`.  The un-mirrored boxes are its per-class box slice.
+extern "C" size_t wssdl_post_detections_views_workspace_bytes(int n_images, int views, int max_rows_per_image,
+                                                              int num_classes) {
+    if (n_images < 1 || views < 1 || max_rows_per_image < 1 || num_classes < 2) return 256;
+    if ((long long)(num_classes - 1) * max_rows_per_image > POST_MAX_UNION)      // no class-agnostic call at this shape
+        return carve_post(nullptr, n_images, max_rows_per_image, num_classes - 1, nullptr);
+    return carve_post_agnostic(nullptr, n_images, max_rows_per_image, num_classes - 1, nullptr, nullptr, nullptr);
+}
+
+extern "C" int wssdl_post_detections_views(const float *rois, const float *scores, const float *boxes, int R, int n_images,
+                                           int views, const float *flip_width, int max_rows_per_image, int num_classes,
+                                           float score_thresh, double nms_thresh, int agnostic, double vote_thresh,
+                                           int max_per_image, float *dets, int32_t *counts, void *workspace,
+                                           size_t workspace_bytes, wssdl_stream_t stream) {
+    const int nc = num_classes - 1;
+    const int P = max_rows_per_image;
+    if (views < 1 || views > POST_MAX_VIEWS) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (R < 0 || n_images < 0 || num_classes < 2 || nc > 64) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (R > 0 && (P < 1 || (long long)n_images * nc * P > POST_MAX_ITEMS || (long long)n_images * nc > POST_MAX_SEGMENTS))
+        return WSSDL_ERR_INVALID_ARGUMENT;
+    if (R > 0 && agnostic && (long long)nc * P > POST_MAX_UNION) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (vote_thresh > 1.0 || vote_thresh != vote_thresh) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (vote_thresh > 0.0 && !(score_thresh >= 0.0f)) return WSSDL_ERR_INVALID_ARGUMENT;    // the weights must be positive
+    if (n_images == 0) return WSSDL_OK;
+    if (!counts) return WSSDL_ERR_INVALID_ARGUMENT;
+    hipStream_t st = as_stream(stream);
+    if (R == 0) {
+        if (hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)n_images * nc, st) != hipSuccess) return WSSDL_ERR_LAUNCH;
+        return WSSDL_OK;
+    }
+    if (!rois || !scores || !boxes || !dets || !workspace) return WSSDL_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < wssdl_post_detections_views_workspace_bytes(n_images, views, P, num_classes))
+        return WSSDL_ERR_WORKSPACE;
+    int rc = post_detections_run(rois, scores, boxes, R, n_images, P, num_classes, score_thresh, nms_thresh, max_per_image,
+                                 dets, counts, workspace, agnostic != 0, st, views, flip_width);
+    if (rc || !(vote_thresh > 0.0)) return rc;
+    PostWs w;
+    carve_post(workspace, n_images, P, nc, &w);                  // the per-class slices come first in both layouts
+    const long long waves = (long long)n_images * nc * P;
+    hipLaunchKernelGGL(post_vote_kernel, dim3(cdiv(waves, VOTE_BLOCK / 64)), dim3(VOTE_BLOCK), 0, st, rois, w.img_lo, w.img_hi,
+                       scores, w.boxes, counts, R, num_classes, n_images, views, P, score_thresh, vote_thresh, dets);
+    return check_launch();
 }
 
 extern "C" int wssdl_post_detections(const float *scores, const float *boxes, int R, int num_classes,

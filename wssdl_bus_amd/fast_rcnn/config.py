@@ -92,6 +92,12 @@ __C.TEST.CLS_AGNOSTIC_NMS = False
 __C.TEST.BBOX_REG = True                            # :248
 # (addition) the post-detection step (test_bus.py:360-401) as one device op when the tensors are on the GPU
 __C.TEST.FUSED_POST_DETECTIONS = True
+# (addition) test-time augmentation, read at every call (fast_rcnn/detect_batch.py; wssdl_post_detections_views):
+# FLIP_AUG -- every image is also detected mirrored and the two views' rows go through one NMS in the image's own frame;
+# BBOX_VOTE -- every surviving box becomes the score-weighted mean of its class's candidates with IoU >= BBOX_VOTE_THRESH
+__C.TEST.FLIP_AUG = False
+__C.TEST.BBOX_VOTE = False
+__C.TEST.BBOX_VOTE_THRESH = 0.5
 __C.TEST.RPN_NMS_THRESH = 0.7                       # :257
 __C.TEST.RPN_PRE_NMS_TOP_N = 6000                   # :259
 __C.TEST.RPN_POST_NMS_TOP_N = 300                   # :262

@@ -3,24 +3,36 @@ reference code/lib/fast_rcnn/train_bus.py:485-534 / :850-899 and test_net's eval
 files): get_test_blobs -> im_detect_batch -> post_detections_batched_device -> DetectionAccumulator -> one
 evaluation op.  No detection is read back; the summary is."""
 from ..datasets.voc_eval_bus import DetectionAccumulator, evaluate_detections
-from .detect_batch import get_test_blobs, im_detect_batch, post_detections_batched_device
+from .config import cfg
+from .detect_batch import get_test_blobs, im_detect_batch, post_detections_batched_device, post_detections_views_device
 
 
 def accumulate_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_image=300):
     """The detections of `planes` at `batch_size` images per forward, kept on the GPU: a DetectionAccumulator.
     cfg.TEST.CLS_AGNOSTIC_NMS is honoured (post_detections_batched_device reads it); a class-agnostic union the
     device op does not take (post_detections_batched_device) raises -- per-class detections are never scored in its
-    place."""
+    place.  cfg.TEST.FLIP_AUG (every image also detected mirrored: the forward sees 2 * batch_size images) and
+    cfg.TEST.BBOX_VOTE / BBOX_VOTE_THRESH are honoured too: under either the batch goes through
+    post_detections_views_device, whose output the accumulator takes as it stands."""
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     acc = None
     for b0 in range(0, len(planes), batch_size):
-        data, info = get_test_blobs(planes[b0:b0 + batch_size], net_name)
+        chunk = planes[b0:b0 + batch_size]
+        flip_width = None
+        if cfg.TEST.FLIP_AUG:
+            data, info, flip_width = get_test_blobs(chunk, net_name, flip_aug=True)
+        else:
+            data, info = get_test_blobs(chunk, net_name)
         scores, boxes, rois = im_detect_batch(net, data, info)
         K = int(scores.shape[1])
         if acc is None:
             acc = DetectionAccumulator(K)
-        dets, counts = post_detections_batched_device(scores, boxes, rois, data.shape[0], K, thresh, max_per_image)
+        if flip_width is not None or cfg.TEST.BBOX_VOTE:
+            dets, counts = post_detections_views_device(scores, boxes, rois, len(chunk), 1 if flip_width is None else 2,
+                                                        flip_width, K, thresh, max_per_image)
+        else:
+            dets, counts = post_detections_batched_device(scores, boxes, rois, data.shape[0], K, thresh, max_per_image)
         acc.add(dets, counts, b0)
     return acc
 
