@@ -835,6 +835,56 @@ WSSDL_API int wssdl_post_detections_views(const float *rois, const float *scores
                      float score_thresh, double nms_thresh, int agnostic, double vote_thresh, int max_per_image,
                      float *dets, int32_t *counts, void *workspace, size_t workspace_bytes, wssdl_stream_t stream);
 
+/* Soft-NMS at test time (Bodla et al., 2017; cfg.TEST.SOFT_NMS; not in the reference): the views op above with a score
+ * decay in place of the deletion, one set of launches, no host read-back, no allocation.
+ * Inputs (rois, scores, boxes, R, n_images, views, flip_width), the views layout, dead rows, the un-mirror step
+ * (x1' = max((w - x2) - 1, 0), x2' = (w - x1) - 1 in f32, inputs not modified) and the output layout are exactly
+ * those of wssdl_post_detections_views: dets [n_images, num_classes-1, P, 5], counts [n_images, num_classes-1],
+ * P = max_rows_per_image; counts[t, 0] = -1 (zeros in t's other counts) for an image whose views span more than P rows;
+ * rows of dets at and beyond a count are not written.
+ * Per output image t and class j >= 1:
+ *   1. Candidates: the rows of t with scores[r, j] > score_thresh and scores[r, j] > min_score, in ascending row
+ *      order, all views together, with un-mirrored boxes.  Each carries its local row index (row minus the first row of
+ *      t, as in the batched op), a working score s (f32) and area = (x2 - x1 + 1) * (y2 - y1 + 1), every operation
+ *      rounded to f32 (the cpu_nms rule).  All candidates are live.
+ *   2. While a live candidate exists:
+ *      Pick    the live i with the largest s; among equal s the largest local row index (the tie-break of every
+ *              ranking here; it applies to scores that become equal through decay too).
+ *      Emit    (box_i, s_i) is the class's next detection; i is no longer live.
+ *      Overlap for every live j, the cpu_nms overlap in f32, every operation rounded on its own, no contraction:
+ *                w = max(0, min(x2_i, x2_j) - max(x1_i, x1_j) + 1), h likewise, inter = w * h,
+ *                ov = inter / ((area_i + area_j) - inter).
+ *      Weight  method 0 (hard):     wt = 0 if (double)ov >= nms_thresh, else 1;
+ *              method 1 (linear):   wt = 1.0f - ov if (double)ov >= nms_thresh, else 1;
+ *              method 2 (Gaussian): wt = (float)exp(-((double)ov * (double)ov) / sigma) -- the product is exact in f64,
+ *                                   then one f64 division, one f64 exp, one rounding to f32; ov == 0 gives exactly 1
+ *                                   (the exp may be skipped); nms_thresh is not read.
+ *      Decay   s_j = s_j * wt in f32; if not s_j > min_score, j stops being live for good.
+ *      The comparison is >=, as in the hard NMS of this library (Bodla et al. write >), so method 0 is the existing op.
+ *   3. Emitted scores never increase (every pick is the maximum of what is left, and decay only lowers), so a class's
+ *      detections are in descending score order and the cap keeps a prefix.
+ *   4. The cap max_per_image applies exactly as in the batched op, over the emitted (decayed) scores; ties stay.
+ * No class-agnostic pass and no voting in this op.
+ * WSSDL_POST_SOFT_MAX_ROWS: a segment's candidates live in the LDS of the one workgroup that runs its pick loop, at
+ * 24 bytes each (box 16, working score 4, area 4).  gfx950 gives a workgroup 160 KiB = 163840 bytes:
+ * 163840 / 24 = 6826 rows; 4096 rows take 98304 bytes (96 KiB) and leave room for the kernel's static part.
+ * WSSDL_ERR_INVALID_ARGUMENT without a launch: views outside 1..8; method outside 0..2; sigma <= 0 or non-finite under
+ * method 2; nms_thresh outside (0, 1] under methods 0 and 1; min_score outside [FLT_MIN, 1) -- with a floor at or above
+ * FLT_MIN a product that underflows is dropped whether or not the hardware flushes it, so the denormal mode cannot
+ * change a bit --; score_thresh < 0; num_classes outside 2..65; max_rows_per_image > WSSDL_POST_SOFT_MAX_ROWS (the
+ * workspace query returns 0 there); the batched op's grid limits; a NULL rois, scores, boxes, dets or workspace with
+ * R > 0.  R == 0 or n_images == 0: zero counts, nothing else launched.
+ * With method 0 the output is bit for bit that of wssdl_post_detections_views with agnostic = 0, vote_thresh = 0 on
+ * the same arguments, for candidates above min_score (pass min_score <= score_thresh). */
+#define WSSDL_POST_SOFT_MAX_ROWS 4096
+WSSDL_API size_t wssdl_post_detections_soft_workspace_bytes(int n_images, int views, int max_rows_per_image,
+                     int num_classes);
+WSSDL_API int wssdl_post_detections_soft(const float *rois, const float *scores, const float *boxes, int R,
+                     int n_images, int views, const float *flip_width, int max_rows_per_image, int num_classes,
+                     float score_thresh, int method, double nms_thresh, double sigma, float min_score,
+                     int max_per_image, float *dets, int32_t *counts, void *workspace, size_t workspace_bytes,
+                     wssdl_stream_t stream);
+
 /* Decode and clip of the head's class-wise boxes: the step between a forward's layers and the post-detection ops
  * above, as the reference's validation loop does it on the sampled RoIs (fast_rcnn/train_bus.py:456-457 / :821-822:
  * boxes = rois[:, 1:5] / scale; clip_boxes(bbox_transform_inv(boxes, bbox_pred), im.shape)), for all images of a batch

@@ -20,6 +20,7 @@ MAX_ANCHORS, MAX_GT = 32, 64
 EVAL_QUANTISE, EVAL_BATCHED = 1, 2
 RECALL_MAX_GT, RECALL_MAX_BOXES = 1024, 65536         # WSSDL_RECALL_MAX_GT, WSSDL_RECALL_MAX_BOXES
 DRAW_MAX_GT, DRAW_MAX_DETS, DRAW_LABEL_LEN, DRAW_MIN_GLYPHS = 64, 192, 24, 14     # WSSDL_DRAW_*
+POST_SOFT_MAX_ROWS = 4096               # WSSDL_POST_SOFT_MAX_ROWS: rows per image of the Soft-NMS op (one segment in LDS)
 POST_AGNOSTIC_MAX_UNION = 12000         # WSSDL_POST_AGNOSTIC_MAX_UNION: (K-1) * rows per image of the class-agnostic op
 
 # every symbol include/wssdl_bus_hip.h declares: (restype, argtypes)
@@ -119,6 +120,8 @@ SYMBOLS = {
     "wssdl_post_detections_agnostic_batched": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _d, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_post_detections_views_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "wssdl_post_detections_views": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _d, _i, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wssdl_post_detections_soft_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wssdl_post_detections_soft": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _f, _i, _d, _d, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "wssdl_decode_detections": (_i,[_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "wssdl_eval_detections_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wssdl_eval_detections": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _d,

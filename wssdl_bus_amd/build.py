@@ -16,8 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("WSSDL_BUS_HIP_LIB") or os.path.join(HERE, "libwssdl_bus_hip.so")
 SOURCES = ["api_common.hip", "bbox_overlaps.hip", "nms.hip", "proposal.hip", "anchor_target.hip",
            "roi_targets.hip", "roi_pool.hip", "roi_pool_compact.hip", "roi_pool_blocks.hip", "roi_pool_walk.hip", "roi_align.hip", "mil.hip", "image.hip", "image_batch.hip", "loss.hip",
-           "post_detect.hip", "order_sort.hip", "eval_detect.hip", "decode_detect.hip", "proposal_recall.hip", "draw_detect.hip"]
-HEADERS = ["common.hip.h", "box_iou.hip.h", "box_code.hip.h", "image_math.hip.h", "nms.hip.h", "select.hip.h", "order_sort.hip.h", "roi_pool.hip.h", os.path.join("..", "..", "include", "wssdl_bus_hip.h")]
+           "post_detect.hip", "soft_nms.hip", "order_sort.hip", "eval_detect.hip", "decode_detect.hip", "proposal_recall.hip", "draw_detect.hip"]
+HEADERS = ["common.hip.h", "box_iou.hip.h", "box_code.hip.h", "image_math.hip.h", "nms.hip.h", "post_views.hip.h", "select.hip.h", "order_sort.hip.h", "roi_pool.hip.h", os.path.join("..", "..", "include", "wssdl_bus_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

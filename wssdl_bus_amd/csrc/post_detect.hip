@@ -30,6 +30,7 @@
 // from the union's kept list and splits that list by class (c = u / P) in order.
 #include "box_iou.hip.h"
 #include "nms.hip.h"
+#include "post_views.hip.h"
 #include "select.hip.h"
 
 namespace wssdl {
@@ -75,19 +76,6 @@ static size_t carve_post(void *ws, int n_images, int P, int nc, PostWs *out) {
 __device__ __forceinline__ int roi_image(const float *__restrict__ rois, int r, int n_images) {
     const float b = rois[(size_t)r * 5];
     return (b >= 0.0f && b < (float)n_images) ? (int)b : -1;
-}
-
-// (start, count) of image img's rows: its run [lo, hi] in the blob, or rows 0 .. R-1 without a blob (lo == NULL)
-__device__ __forceinline__ void image_rows(const int *__restrict__ lo, const int *__restrict__ hi, int img, int R,
-                                           int &start, int &count) {
-    if (!lo) {
-        start = 0;
-        count = R;
-        return;
-    }
-    const int l = lo[img], h = hi[img];
-    start = h >= 0 ? l : 0;
-    count = h >= 0 ? h - l + 1 : 0;
 }
 
 // One workgroup: the first and last row of every image's run (the ends of a run are the rows whose neighbour
@@ -352,21 +340,7 @@ __global__ __launch_bounds__(CAP_BLOCK) void post_union_cap_kernel(const int *__
 // are the two above with the output image in place of the batch index; the key kernel also brings the boxes of a
 // mirrored source back into the image's own frame while it copies them into the workspace (the inputs stay as they
 // are).  Ranking, sweep, union pass and cap then run unchanged on those copies.  Box voting follows the cap: one wave
-// per surviving detection, see post_vote_kernel.
-constexpr int POST_MAX_VIEWS = 8;
-
-// output image of RoI row r and its source image: the batch index b in [0, n_images * views) -> b / views, src = b;
-// -1 otherwise (dead padding rows, NaN, foreign images)
-__device__ __forceinline__ int roi_view_image(const float *__restrict__ rois, int r, int n_images, int views, int &src) {
-    const float b = rois[(size_t)r * 5];
-    if (!(b >= 0.0f && b < (float)(n_images * views))) {
-        src = -1;
-        return -1;
-    }
-    src = (int)b;
-    return src / views;
-}
-
+// per surviving detection, see post_vote_kernel.  (roi_view_image, unmirror_x: post_views.hip.h)
 __global__ __launch_bounds__(SEG_BLOCK) void post_view_segments_kernel(const float *__restrict__ rois, int R, int n_images,
                                                                         int views, int *__restrict__ lo,
                                                                         int *__restrict__ hi) {
@@ -415,13 +389,7 @@ __global__ __launch_bounds__(256) void post_view_keys_kernel(const float *__rest
     const float *b = boxes + (size_t)r * 4 * K + 4 * (c + 1);
     float *o = cboxes + (size_t)i * 4;
     float x1 = b[0], x2 = b[2];
-    const float w = flip_width ? flip_width[src] : -1.0f;
-    if (w >= 0.0f) {
-        float a = w - x2;  a = a - 1.0f;
-        float e = w - x1;  e = e - 1.0f;
-        x1 = fmaxf(a, 0.0f);
-        x2 = e;
-    }
+    unmirror_x(flip_width ? flip_width[src] : -1.0f, x1, x2);
     o[0] = x1;  o[1] = b[1];  o[2] = x2;  o[3] = b[3];
 }
 
@@ -487,10 +455,12 @@ __global__ __launch_bounds__(VOTE_BLOCK) void post_vote_kernel(const float *__re
     }
 }
 
-// Limits of the batched form: the segments' rows are 32-bit item numbers of one select (<= 2^24), and the ranking
-// and mask grids put the segments on a grid dimension of at most 65535 blocks.
-constexpr long long POST_MAX_ITEMS = 1LL << 24;
-constexpr long long POST_MAX_SEGMENTS = 65535;
+int launch_post_view_segments(const float *rois, int R, int n_images, int views, int *lo, int *hi, hipStream_t st) {
+    hipLaunchKernelGGL(post_view_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, views, lo, hi);
+    return check_launch();
+}
+
+// (the limits of the batched form, POST_MAX_ITEMS and POST_MAX_SEGMENTS: post_views.hip.h)
 // The union segment of the class-agnostic form: (K-1) * P items per image in one ranking and one mask + sweep with
 // max_keep = the segment.  12000 is the segment the proposal layer runs both at; the kept list of the general
 // sweep (which takes over beyond 2240 kept) fits LDS up to 15296 entries, the suppression matrix is
@@ -514,9 +484,7 @@ static int post_detections_run(const float *rois, const float *scores, const flo
     const int blocks = cdiv((long long)nseg * P, 256);
     int rc;
     if (views > 0) {            // wssdl_post_detections_views: the output image of a row is its source image / views
-        hipLaunchKernelGGL(post_view_segments_kernel, dim3(1), dim3(SEG_BLOCK), 0, st, rois, R, n_images, views, w.img_lo,
-                           w.img_hi);
-        if ((rc = check_launch())) return rc;
+        if ((rc = launch_post_view_segments(rois, R, n_images, views, w.img_lo, w.img_hi, st))) return rc;
         lo = w.img_lo;
         hi = w.img_hi;
         hipLaunchKernelGGL(post_view_keys_kernel, dim3(blocks), dim3(256), 0, st, rois, lo, hi, scores, boxes, flip_width, R,

@@ -98,6 +98,13 @@ __C.TEST.FUSED_POST_DETECTIONS = True
 __C.TEST.FLIP_AUG = False
 __C.TEST.BBOX_VOTE = False
 __C.TEST.BBOX_VOTE_THRESH = 0.5
+# (addition) Soft-NMS (Bodla et al., 2017), read at every call (fast_rcnn/soft_nms.py; wssdl_post_detections_soft):
+# 'off' | 'linear' | 'gaussian' -- an overlapped box keeps a lowered score (x (1 - IoU) at IoU >= TEST.NMS, or
+# x exp(-IoU^2 / SOFT_NMS_SIGMA)) and leaves once the score is at or below SOFT_NMS_MIN_SCORE.  Not combined with
+# CLS_AGNOSTIC_NMS or BBOX_VOTE (ValueError).
+__C.TEST.SOFT_NMS = 'off'
+__C.TEST.SOFT_NMS_SIGMA = 0.5
+__C.TEST.SOFT_NMS_MIN_SCORE = 0.001
 __C.TEST.RPN_NMS_THRESH = 0.7                       # :257
 __C.TEST.RPN_PRE_NMS_TOP_N = 6000                   # :259
 __C.TEST.RPN_POST_NMS_TOP_N = 300                   # :262

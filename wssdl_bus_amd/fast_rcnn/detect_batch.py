@@ -320,8 +320,15 @@ def postprocess_detections_batch(scores, boxes, rois, n_images, num_classes, thr
     Test-time augmentation: with views > 1 (the blob holds n_images * views source images, source s = view s % views of
     output image s // views; flip_width [n_images * views] marks the mirrored ones with their original width, -1
     otherwise) or under cfg.TEST.BBOX_VOTE the call goes to wssdl_post_detections_views (_postprocess_views), whose
-    fallback is the same statement step by step on the host."""
+    fallback is the same statement step by step on the host.
+
+    Under cfg.TEST.SOFT_NMS = 'linear' | 'gaussian' the call goes to soft_nms.postprocess_soft_batch
+    (wssdl_post_detections_soft, or the host path of the same statement), with or without views."""
     n_images = int(n_images)
+    if cfg.TEST.SOFT_NMS != 'off':
+        from .soft_nms import postprocess_soft_batch
+        return postprocess_soft_batch(scores, boxes, rois, n_images, num_classes, thresh, max_per_image, int(views),
+                                      flip_width)
     if int(views) > 1 or flip_width is not None or cfg.TEST.BBOX_VOTE:
         return _postprocess_views(scores, boxes, rois, n_images, num_classes, thresh, max_per_image, int(views), flip_width)
     if _device_post_detections_apply(scores, num_classes):

@@ -13,7 +13,8 @@ def accumulate_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_
     device op does not take (post_detections_batched_device) raises -- per-class detections are never scored in its
     place.  cfg.TEST.FLIP_AUG (every image also detected mirrored: the forward sees 2 * batch_size images) and
     cfg.TEST.BBOX_VOTE / BBOX_VOTE_THRESH are honoured too: under either the batch goes through
-    post_detections_views_device, whose output the accumulator takes as it stands."""
+    post_detections_views_device, whose output the accumulator takes as it stands.  So it does that of
+    post_detections_soft_device under cfg.TEST.SOFT_NMS = 'linear' | 'gaussian' (with or without FLIP_AUG)."""
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     acc = None
@@ -28,7 +29,11 @@ def accumulate_images(net, planes, net_name, batch_size=8, thresh=0.05, max_per_
         K = int(scores.shape[1])
         if acc is None:
             acc = DetectionAccumulator(K)
-        if flip_width is not None or cfg.TEST.BBOX_VOTE:
+        if cfg.TEST.SOFT_NMS != 'off':
+            from .soft_nms import post_detections_soft_device
+            dets, counts = post_detections_soft_device(scores, boxes, rois, len(chunk), 1 if flip_width is None else 2,
+                                                       flip_width, K, thresh, max_per_image)
+        elif flip_width is not None or cfg.TEST.BBOX_VOTE:
             dets, counts = post_detections_views_device(scores, boxes, rois, len(chunk), 1 if flip_width is None else 2,
                                                         flip_width, K, thresh, max_per_image)
         else:

@@ -56,7 +56,12 @@ def postprocess_detections(scores, boxes, num_classes, thresh=0.05, max_per_imag
     whose union (K-1) * R is within WSSDL_POST_AGNOSTIC_MAX_UNION take wssdl_post_detections_agnostic and ONE
     read-back of the per-class counts.  Everything else -- flag off, CPU tensors, more than 64 classes, a longer
     union, FUSED_POST_DETECTIONS off -- is test_bus.postprocess_detections as it stands (its step-by-step form
-    under the flag).  Returns {j: dets [n,5]} (GPU)."""
+    under the flag).  Returns {j: dets [n,5]} (GPU).
+    Under cfg.TEST.SOFT_NMS = 'linear' | 'gaussian': soft_nms.postprocess_soft (wssdl_post_detections_soft on the image
+    as a batch of one, or the host path of the same statement)."""
+    if cfg.TEST.SOFT_NMS != 'off':
+        from .soft_nms import postprocess_soft
+        return postprocess_soft(scores, boxes, num_classes, thresh, max_per_image)
     if cfg.TEST.CLS_AGNOSTIC_NMS and scores.is_cuda and scores.shape[1] == num_classes and \
             device_post_detections_fit(num_classes, scores.shape[0]):
         dets, counts = post_detections_device(scores, boxes, num_classes, thresh, max_per_image, agnostic=True)

@@ -67,5 +67,11 @@ def validation_detections(layers, im_info, n_images, thresh=0.05, max_per_image=
         bounds = torch.tensor([(float(s[1]) - 1.0, float(s[0]) - 1.0) for s in im_shapes], dtype=torch.float32,
                               device=rois.device).reshape(n, 2)
     boxes = decode_detections_device(rois, deltas, im_info, n, bounds)
+    if cfg.TEST.SOFT_NMS != 'off':                  # (addition) Soft-NMS in place of the hard one, the same layout
+        from .soft_nms import post_detections_soft_device
+        if agnostic:
+            raise ValueError("cfg.TEST.SOFT_NMS cannot be combined with a class-agnostic pass")
+        return post_detections_soft_device(scores, boxes, rois, n, 1, None, int(scores.shape[1]), thresh, max_per_image,
+                                           max_rows_per_image=int(cfg.TRAIN.BATCH_SIZE))
     return post_detections_batched_device(scores, boxes, rois, n, int(scores.shape[1]), thresh, max_per_image,
                                           max_rows_per_image=int(cfg.TRAIN.BATCH_SIZE), agnostic=agnostic)
